@@ -106,7 +106,7 @@ def _bench(extra_env, *flags):
         port = s.getsockname()[1]
     env.update(SSASR_DIST_SINGLE='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), **extra_env)
     env.setdefault('SSASR_DDP_FALLBACK_LOG', os.path.join(os.environ.get('TMPDIR', '/tmp'), 'ssasr_bench_first_attempt_%d.log' % os.getpid()))
-    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '2', '--no-roofline',
+    res = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '3', '--warmup', '2', '--full', '--no-roofline',
                           '--no-config4', '--no-cpu-baseline', '--no-epoch'] + list(flags), env=env, cwd=ROOT,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert res.returncode == 0, (res.stdout + res.stderr)[-3000:]

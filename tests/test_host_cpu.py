@@ -355,22 +355,71 @@ def test_gpu_loader_plans_the_reference_batches_and_refuses_the_cpu(tmp_path):
 
 
 # ------------------------------------------------------- drop-in boundary ----
-REFERENCE_TRAIN = '/root/reference/src/train.py'
+# A training entry point in the form of the reference's src/train.py: its siblings
+# imported by bare name (`import trainer`, src/train.py:9), positional type / name / config / logdir / ckpdir,
+# every generator seeded, then the Seed loop (trainer.asr_seed_train) or the selected trainer's
+# load_data / set_model / exec (src/train.py:66-71).  The test writes it beside sibling modules of the same
+# names that refuse to be imported, as the reference's own trainer.py / asr.py / ... sit beside its train.py.
+ENTRY_SCRIPT = r'''
+import argparse
+import random
+
+import numpy as np
+import torch
+import yaml
+
+import trainer
+
+ap = argparse.ArgumentParser()
+for name in ('type', 'name', 'config', 'logdir', 'ckpdir'):
+    ap.add_argument(name)
+ap.add_argument('--seed', type=int, default=1)
+ap.add_argument('--verbose', type=bool, default=True)
+paras = ap.parse_args()
+with open(paras.config) as f:
+    config = yaml.safe_load(f)
+random.seed(paras.seed)
+np.random.seed(paras.seed)
+torch.manual_seed(paras.seed)
+if torch.cuda.is_available():
+    torch.cuda.manual_seed_all(paras.seed)
+if paras.type == 'Seed':
+    trainer.asr_seed_train(config, paras)
+else:
+    sel = getattr(trainer, paras.type)(config, paras)
+    sel.load_data()
+    sel.set_model()
+    sel.exec()
+'''
+ENTRY_SIBLINGS = ('trainer', 'asr', 'ASRDataset', 'preprocess', 'postprocess', 'LogHandler', 'TrackerHandler',
+                  'discriminator', 'speech_autoencoder', 'text_autoencoder')
 
 
-@pytest.mark.skipif(not os.path.isfile(REFERENCE_TRAIN),
-                    reason='build-container only: the reference tree does not travel to the GPU box')
+def write_entry_script(root):
+    """The entry script in a directory of its own, beside siblings that raise ImportError when imported."""
+    src = os.path.join(root, 'src')
+    os.makedirs(src)
+    for name in ENTRY_SIBLINGS:
+        with open(os.path.join(src, name + '.py'), 'w') as f:
+            f.write('raise ImportError("the script directory\'s own %s module was imported")\n' % name)
+    path = os.path.join(src, 'train.py')
+    with open(path, 'w') as f:
+        f.write(ENTRY_SCRIPT)
+    return path
+
+
 @pytest.mark.parametrize('kind', ['ASRTrainer', 'TAETrainer', 'AdvTrainer', 'SAETrainer', 'Seed'])
 def test_reference_train_script_runs_unchanged_against_this_package(tmp_path, kind):
     """INTEGRATION.md section 1: `python -m ss_asr_amd.run_reference <reference>/src/train.py ...`
-    executes the reference's unmodified entry point with its bare imports (`import trainer`,
-    src/train.py:9) bound to ss_asr_amd.  Without a GPU the run must get all the way through
+    executes an unmodified entry point of the reference's form with its bare imports bound to
+    ss_asr_amd, not to the modules beside it.  Without a GPU the run must get all the way through
     argument parsing, yaml, seeding, ASRTrainer construction, load_data and set_model, and stop at
     the first arithmetic with the product's "no CPU path" error -- never with an ImportError from
-    the reference's own modules (librosa, editdistance, tensorboardX are absent here)."""
+    the script's sibling modules (the reference's own need librosa, editdistance, tensorboardX)."""
     import subprocess
     import yaml
     root = str(tmp_path)
+    entry = write_entry_script(root)
     index, _ = make_corpus(root, n=16, t_max=24, feat=80, seed=2)
     conf = {'asr': {'opt': {'type': 'Adadelta', 'learning_rate': 1.0},
                     'mdl': {'encoder_state_size': 32, 'mlp_out_size': 16, 'decoder_state_size': 32,
@@ -398,7 +447,7 @@ def test_reference_train_script_runs_unchanged_against_this_package(tmp_path, ki
         yaml.safe_dump(conf, f)
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1')
     env.pop('PYTHONPATH', None)
-    res = subprocess.run([sys.executable, '-m', 'ss_asr_amd.run_reference', REFERENCE_TRAIN, kind, 'dropin',
+    res = subprocess.run([sys.executable, '-m', 'ss_asr_amd.run_reference', entry, kind, 'dropin',
                           conf_path, os.path.join(root, 'runs'), os.path.join(root, 'result')],
                          cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
     out = res.stdout
@@ -474,3 +523,31 @@ def test_settle_collector_freezes_once_and_honours_its_switch(monkeypatch):
         del keep
     finally:
         gc.unfreeze()
+
+
+def test_bench_dump_outputs_keeps_a_seeded_sample_within_its_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: loss, logits, the step's verdict and every parameter as <name>.npy in float32 /
+    float64; over the budget the largest arrays are cut to the same seeded sample on every run."""
+    import bench
+    from ss_asr_amd.asr import ASR
+    torch.manual_seed(0)
+    model = ASR(**bench.DIMS)
+    stepper = types.SimpleNamespace(last_done=(0.75, False), last_logits=torch.randn(32, 81, 50))
+    full, cut, again = (str(tmp_path / n) for n in ('full', 'cut', 'again'))
+    bench.dump_outputs(full, model, stepper, torch.tensor(3.5))
+    names = sorted(os.listdir(full))
+    assert len(names) == 4 + len(list(model.parameters()))
+    assert float(np.load(os.path.join(full, 'loss.npy'))[0]) == 3.5
+    assert float(np.load(os.path.join(full, 'grad_norm.npy'))[0]) == 0.75
+    w = dict(model.named_parameters())['decoder.layer_1.weight_ih'].detach().numpy()
+    assert np.array_equal(np.load(os.path.join(full, 'param.decoder.layer_1.weight_ih.npy')), w)
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 8 << 20)
+    for d in (cut, again):
+        bench.dump_outputs(d, model, stepper, torch.tensor(3.5))
+    assert sorted(os.listdir(cut)) == names
+    assert sum(os.path.getsize(os.path.join(cut, n)) for n in names) <= (8 << 20) + 128 * len(names)   # + .npy headers
+    for n in names:
+        a, b = np.load(os.path.join(cut, n)), np.load(os.path.join(again, n))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b)
+    s = np.load(os.path.join(cut, 'param.decoder.layer_1.weight_ih.npy'))
+    assert s.ndim == 1 and s.size < w.size and np.isin(s, w.reshape(-1)).all()

@@ -23,6 +23,9 @@
  *   - return 0 on success, a negative value for an argument error, a positive
  *     hipError_t for a HIP failure.
  *
+ * ABI history.  15: inference -- ssasr_charlm, ssasr_charlm_step, ssasr_infer, ssasr_decode_greedy (nothing
+ * older changed).  14 and before: the training entry points below.
+ *
  * Persistent launches.  Several entry points run a whole layer / decode loop as
  * ONE launch whose workgroups hand data to each other.  Such a grid is only
  * launched when an occupancy query says every workgroup of it can be resident
@@ -534,6 +537,62 @@ int ssasr_logmel_batch(const float* wav, const int64_t* utt, int64_t n_utts, int
 int ssasr_logmel(const float* wav, int64_t n_samples, int64_t n_fft, int64_t hop, int64_t n_mels,
                  const float* window, const float* dft_basis, const float* mel_basis,
                  float* ws_frames, float* ws_spec, float* ws_power, float* out, void* stream);
+
+/* ---- inference (ABI 15) -------------------------------------------------------------------------------------
+ * Parameters of the character language model, CharLM (src/charlm.py:26-44), PyTorch layouts:
+ * emb [V][H]; two nn.GRUCell (gate order r, z, n): w_ih*, w_hh* [3H][H], b_ih*, b_hh* [3H]; out: w_out [V][H],
+ * b_out [V].  H % 4 == 0; every pointer 16-byte aligned. */
+typedef struct ssasr_charlm {
+  int64_t V, H;
+  const float* emb;
+  const float* w_ih1; const float* w_hh1; const float* b_ih1; const float* b_hh1;
+  const float* w_ih2; const float* w_hh2; const float* b_ih2; const float* b_hh2;
+  const float* w_out; const float* b_out;
+} ssasr_charlm;
+
+/* One CharLM.forward (src/charlm.py:46-57) for B rows: x int32 [B] character ids, h1 / h2 [B][H] ->
+ * out [B][V] (the output layer, no softmax), h1_out / h2_out [B][H] (may alias h1 / h2).
+ * GRUCell: r = s(W_ir x + b_ir + W_hr h + b_hr), z likewise, n = tanh(W_in x + b_in + r * (W_hn h + b_hn)),
+ * h' = (1 - z) * n + z * h.  One workgroup per row. */
+int ssasr_charlm_step(const ssasr_charlm* lm, const int32_t* x, const float* h1, const float* h2, int64_t B,
+                      float* out, float* h1_out, float* h2_out, void* stream);
+
+/* The greedy decode loop of ASR.decode (src/asr.py:112-173, driven by ASRTester.exec, src/trainer.py:578-592)
+ * for N encoded utterances as ONE launch: per utterance and step the attention (src/asr.py:383-390), both
+ * Speller cells, char_trans and log_softmax (:149-153), one CharLM step fed with the previously emitted
+ * character (<SOS> = 0 first; :154-155), final = asr + lm_weight * lm and its first maximum (:156-159), whose
+ * embedding feeds the next step (:161-162), until <EOS> (:167-169) or max_steps (:128, :143).
+ * One workgroup owns one utterance for the whole loop; workgroups exchange nothing (no status words, no
+ * workspace to arm), every loop is bounded, and a finished utterance's workgroup exits.  An utterance's
+ * results depend on its own frames and enc_len alone: the same bits in any batch, at any padded T.
+ * Accepted: what ssasr_decoder_fwd accepts (A % 4 == 0, E % 4 == 0, D % 16 == 0, T <= 16384, A <= 2048,
+ * E <= 8192) with V <= 64, as long as the utterance's state fits one CU's LDS
+ * (9 D + E + A + T + 9 H + 2208 floats <= 160 KB); everything else is an argument error before any launch. */
+typedef struct ssasr_infer {
+  /* sizes */
+  int64_t N, T, E, A, D, V, max_steps;
+  /* inputs */
+  const float* feat;        /* [N][T][E] listener outputs, each utterance encoded alone; frames >= enc_len unread */
+  const int32_t* enc_len;   /* [N], clamped to 1 .. T                                                            */
+  float* comp;              /* [N][T][A] workspace: tanh(psi(feat)), computed once by the launch itself          */
+  /* parameters (PyTorch layouts), the fields of ssasr_decoder plus psi */
+  const float* w_psi; const float* b_psi;   /* [A][E], [A]                       */
+  const float* w_phi;       /* [A][D]                                            */
+  const float* w_ih1; const float* w_hh1; const float* b_ih1; const float* b_hh1; /* cell 1: I = D + E */
+  const float* w_ih2; const float* w_hh2; const float* b_ih2; const float* b_hh2; /* cell 2: I = D     */
+  const float* embed;       /* [V][D]                                            */
+  const float* w_ct; const float* b_ct;     /* [V][D], [V]                       */
+  const ssasr_charlm* lm;   /* HOST pointer; NULL: no LM term, lm_weight ignored; lm->V must equal V */
+  float lm_weight;
+  int32_t eos;              /* the character that ends an utterance               */
+  /* outputs, written completely by the launch; rows past an utterance's last executed step are zero */
+  int32_t* chars;           /* [N][max_steps] the winner of every executed step (the <EOS> that ended it included) */
+  int32_t* n_chars;         /* [N] characters emitted before <EOS>; max_steps when the cap ended the loop          */
+  float* scores;            /* [N][max_steps][V] `final` of every executed step                                    */
+  float* att;               /* [N][max_steps][T] attention weights, optional                                       */
+} ssasr_infer;
+
+int ssasr_decode_greedy(const ssasr_infer* d, void* stream);
 
 #ifdef __cplusplus
 }

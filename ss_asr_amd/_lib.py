@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SSASR_LIB') or os.path.join(_HERE, 'libssasr_hip.so')   # SSASR_LIB: A/B builds
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 P = C.c_void_p
 I64 = C.c_int64
@@ -43,6 +43,23 @@ class DecoderGrads(C.Structure):
         'db1_2', 'db2_2')] + [('defer_wgrad', C.c_int32), ('ws_armed', C.c_int32)]
 
 
+class CharLM(C.Structure):
+    """struct ssasr_charlm (include/ssasr.h)."""
+    _fields_ = [('V', I64), ('H', I64)] + [(n, P) for n in (
+        'emb', 'w_ih1', 'w_hh1', 'b_ih1', 'b_hh1', 'w_ih2', 'w_hh2', 'b_ih2', 'b_hh2', 'w_out', 'b_out')]
+
+
+class Infer(C.Structure):
+    """struct ssasr_infer (include/ssasr.h)."""
+    _fields_ = (
+        [(n, I64) for n in ('N', 'T', 'E', 'A', 'D', 'V', 'max_steps')] +
+        [(n, P) for n in ('feat', 'enc_len', 'comp', 'w_psi', 'b_psi', 'w_phi',
+                          'w_ih1', 'w_hh1', 'b_ih1', 'b_hh1', 'w_ih2', 'w_hh2', 'b_ih2', 'b_hh2',
+                          'embed', 'w_ct', 'b_ct')] +
+        [('lm', C.POINTER(CharLM)), ('lm_weight', F32), ('eos', C.c_int32)] +
+        [(n, P) for n in ('chars', 'n_chars', 'scores', 'att')])
+
+
 SIGNATURES = {
     'ssasr_abi_version': (I32, []),
     'ssasr_set_option': (I32, [C.c_char_p, I32]),
@@ -72,6 +89,8 @@ SIGNATURES = {
     'ssasr_decoder_fwd': (I32, [C.POINTER(Decoder), P]),
     'ssasr_decoder_bwd': (I32, [C.POINTER(Decoder), C.POINTER(DecoderGrads), P]),
     'ssasr_decoder_wgrad': (I32, [C.POINTER(Decoder), C.POINTER(DecoderGrads), I32, P]),
+    'ssasr_charlm_step': (I32, [C.POINTER(CharLM), P, P, P, I64, P, P, P, P]),
+    'ssasr_decode_greedy': (I32, [C.POINTER(Infer), P]),
     'ssasr_ce_loss_fwd': (I32, [P, P, I64, I64, I64, I64, I64, P, P, P]),
     'ssasr_ce_loss_bwd': (I32, [P, P, I64, P, P, I64, I64, I64, P, P]),
     'ssasr_ctc_ws_floats': (I64, [I64, I64, I64, I64]),

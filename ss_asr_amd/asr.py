@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .preprocess import EOS_TKN
 
 
 def _dev_i32(values, device):
@@ -252,6 +253,8 @@ class ASR(nn.Module):
         self.att_event = None
         self.last_chars = self.last_modes = self.last_uniforms = None
         self.last_encoded = None
+        # decode_many's device results: (chars [N, steps] int32, n_chars [N] int32, scores [N, steps, V], att [N, steps, T'])
+        self.last_decode = None
         self.init_parameters()
 
     def init_parameters(self):
@@ -325,3 +328,38 @@ class ASR(nn.Module):
         else:
             host = att.detach().cpu()
         return encode_len, logits, host
+
+    def decode(self, x, x_len, rnn_lm, mapper, lm_weight, max_decoding_steps=200):
+        """src/asr.py:112-173: greedy decoding of ONE utterance (x [1, seq, features], x_len from prepare_x)
+        until <EOS> or max_decoding_steps (200 in the reference, :128), every step's character scores being
+        log_softmax(speller) + lm_weight * log_softmax(rnn_lm).  Returns the decoded string.  rnn_lm None: no LM
+        term.  The whole loop is one launch (ssasr_decode_greedy)."""
+        assert len(x.shape) == 3 and x.shape[0] == 1
+        return self.decode_many([x], [x_len], rnn_lm, mapper, lm_weight, max_decoding_steps=max_decoding_steps)[0]
+
+    def decode_many(self, xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=200):
+        """decode() for a list of single utterances in ONE decode launch.  Each utterance is encoded alone
+        (blstm_4 recurs over the utterance axis, src/asr.py:237-238, :262: a batched encoder would change every
+        transcript); the encoder outputs are packed to [N, T'max, E] and every utterance gets a workgroup of its
+        own.  Returns the N strings; last_decode keeps (chars, n_chars, scores, att) on the device."""
+        feats, enc_lens = [], []
+        with torch.no_grad():
+            for x, x_len in zip(xs, x_lens):
+                assert len(x.shape) == 3 and x.shape[0] == 1
+                feat, enc_len = self.encoder(x, x_len)
+                feats.append(feat)
+                enc_lens.append(int(enc_len[0]))
+            dev = feats[0].device
+            tmax = max(f.shape[1] for f in feats)
+            if len(feats) == 1:
+                packed = feats[0]
+            else:
+                packed = torch.zeros(len(feats), tmax, feats[0].shape[2], device=dev, dtype=torch.float32)
+                for n, f in enumerate(feats):
+                    packed[n, :f.shape[1]] = f[0]
+            self.last_decode = ops.decode_greedy(
+                packed, _dev_i32(enc_lens, dev), self._decoder_params(),
+                (self.attention.psi.weight, self.attention.psi.bias), rnn_lm, lm_weight,
+                mapper.char_to_ind(EOS_TKN), max_decoding_steps)
+        chars, n_chars = self.last_decode[0].cpu().tolist(), self.last_decode[1].cpu().tolist()
+        return [''.join(mapper.ind_to_char(c) for c in row[:n]) for row, n in zip(chars, n_chars)]

@@ -1014,3 +1014,67 @@ def adam_update_(param, grad, exp_avg, exp_avg_sq, ws, stats, clipped, grad_scal
 def clip_adadelta_ws(n, device):
     lib = _lib.load()
     return torch.empty(int(lib.ssasr_clip_adadelta_ws(n)), device=device, dtype=torch.float32)
+
+
+# ---------------------------------------------------------------------------
+# inference: CharLM step, single-launch greedy decode (csrc/infer.hip)
+# ---------------------------------------------------------------------------
+def _charlm_struct(lm):
+    """(struct ssasr_charlm, the tensors it points into) of a charlm.CharLM."""
+    names = ('emb.weight', 'layer_1.weight_ih', 'layer_1.weight_hh', 'layer_1.bias_ih', 'layer_1.bias_hh',
+             'layer_2.weight_ih', 'layer_2.weight_hh', 'layer_2.bias_ih', 'layer_2.bias_hh', 'out.weight', 'out.bias')
+    params = dict(lm.named_parameters())
+    keep = [_f32c(params[n].detach()) for n in names]
+    _need_gpu(*keep)
+    s = _lib.CharLM(lm.input_size, lm.hidden_size, *[t.data_ptr() for t in keep])
+    return s, keep
+
+
+def charlm_step(lm, x, h_1, h_2):
+    """CharLM.forward (src/charlm.py:46-57): x [B] character ids, h_1 / h_2 [B, H] -> (out [B, V], h_1', h_2')."""
+    lib = _lib.load()
+    _need_gpu(x, h_1, h_2)
+    s, keep = _charlm_struct(lm)
+    B = x.shape[0]
+    x32, h_1, h_2 = as_i32(x.reshape(B)), _f32c(h_1), _f32c(h_2)
+    out = torch.empty(B, lm.input_size, device=x.device, dtype=torch.float32)
+    n1, n2 = torch.empty_like(h_1), torch.empty_like(h_2)
+    check(lib.ssasr_charlm_step(C.byref(s), _p(x32), _p(h_1), _p(h_2), B, _p(out), _p(n1), _p(n2), _stream()),
+          'ssasr_charlm_step')
+    return out, n1, n2
+
+
+def decode_greedy(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, want_att=True):
+    """ssasr_decode_greedy over feat [N, T, E] (each utterance encoded alone) and enc_len int32 [N]:
+    -> (chars [N, max_steps] int32, n_chars [N] int32, scores [N, max_steps, V], att [N, max_steps, T] or None).
+    params: ASR._decoder_params(); psi: (weight, bias); lm: a charlm.CharLM or None."""
+    lib = _lib.load()
+    feat = _f32c(feat)
+    _need_gpu(feat, enc_len)
+    N, T, E = feat.shape
+    A, D = params['w_phi'].shape
+    V = params['w_ct'].shape[0]
+    dev = feat.device
+    keep = {k: _f32c(v.detach()) for k, v in params.items()}
+    w_psi, b_psi = _f32c(psi[0].detach()), _f32c(psi[1].detach())
+    comp = torch.empty(N, T, A, device=dev, dtype=torch.float32)
+    chars = torch.empty(N, max_steps, device=dev, dtype=torch.int32)
+    n_chars = torch.empty(N, device=dev, dtype=torch.int32)
+    scores = torch.empty(N, max_steps, V, device=dev, dtype=torch.float32)
+    att = torch.empty(N, max_steps, T, device=dev, dtype=torch.float32) if want_att else None
+    d = _lib.Infer()
+    d.N, d.T, d.E, d.A, d.D, d.V, d.max_steps = N, T, E, A, D, V, int(max_steps)
+    d.feat, d.enc_len, d.comp = feat.data_ptr(), enc_len.data_ptr(), comp.data_ptr()
+    d.w_psi, d.b_psi = w_psi.data_ptr(), b_psi.data_ptr()
+    for k, v in keep.items():
+        setattr(d, k, v.data_ptr())
+    lm_struct = None
+    if lm is not None:
+        lm_struct, lm_keep = _charlm_struct(lm)
+        d.lm = C.pointer(lm_struct)
+        d.lm_weight = float(lm_weight)
+    d.eos = int(eos)
+    d.chars, d.n_chars, d.scores = chars.data_ptr(), n_chars.data_ptr(), scores.data_ptr()
+    d.att = att.data_ptr() if want_att else None
+    check(lib.ssasr_decode_greedy(C.byref(d), _stream()), 'ssasr_decode_greedy')
+    return chars, n_chars, scores, att

@@ -1,5 +1,5 @@
 """Solver / ASRTrainer with the surface of the reference's src/trainer.py
-(Solver :33-195, ASRTrainer :374-545, TAETrainer :594-758, SAETrainer :760-907, ADVTrainer :909-1124,
+(Solver :33-195, ASRTrainer :374-545, ASRTester :547-592, TAETrainer :594-758, SAETrainer :760-907, ADVTrainer :909-1124,
 asr_seed_train :1126-1177) so that ``src/train.py`` drives it unchanged:
 ``getattr(trainer, 'ASRTrainer')(config, paras)`` then ``load_data()``, ``set_model()``, ``exec()``.
 
@@ -32,6 +32,7 @@ from .ASRDataset import load_asr_dataset, prepare_x, prepare_y
 from .LogHandler import LogHandler
 from .TrackerHandler import TrackerHandler
 from .asr import ASR
+from .charlm import CharLM
 from .optim import FusedAdadelta
 from .postprocess import calc_acc, calc_err, draw_att
 
@@ -361,6 +362,69 @@ class ASRTrainer(Solver):
         if self.rank == 0:
             sdist.save_atomic(self.asr_model.state_dict(), self.ckppath)
         sdist.barrier()        # the next reader of these files (the Seed loop's next leg) runs on every rank
+
+
+class ASRTester(Solver):
+    """Inference over a test index, src/trainer.py:547-592: the same config keys (asr.test_index,
+    decode_lm_weight, decode_beam_size, decode_jobs, max_decode_step_ratio, char_lm.mdl.hidden_size) and the same
+    `decode_file` name.  Like the reference (its beam search is a TODO, :590) decoding is greedy, here
+    `decode_group` utterances per launch (ASR.decode_many).  The reference constructs a CharLM and never loads
+    it (:567-569); here <ckpdir>/char_lm.cpt is loaded when it exists."""
+    decode_group = 32
+
+    def __init__(self, config, paras):
+        super().__init__(config, paras, 'asr')
+        self.decode_file = "_".join(
+            ['decode', 'beam', str(self.config['asr']['decode_beam_size']),
+             'len', str(self.config['asr']['max_decode_step_ratio'])])
+
+    def load_data(self):
+        (self.mapper, self.ds, self.test_set) = load_asr_dataset(
+            self.config['asr']['test_index'], batch_size=self.test_batch_size,
+            n_jobs=self.set_if_exists('loader_jobs', 8), use_gpu=self.paras.gpu)
+
+    def set_model(self):
+        self.asr_model = self.setup_module(ASR, self.ckppath, self.mapper.get_dim(),
+                                           **self.config['asr']['mdl'])
+        self.asr_model.eval()
+        lm_conf = self.config['char_lm']            # conf/default.yaml:84-89 keeps it under mdl; src/trainer.py:568 reads it beside mdl
+        hidden = lm_conf['mdl']['hidden_size'] if 'mdl' in lm_conf else lm_conf['hidden_size']
+        lm_path = os.path.join(self.ckpdir, 'char_lm.cpt')
+        if os.path.isfile(lm_path):
+            self.lm = self.setup_module(CharLM, lm_path, self.ds.get_char_dim(), hidden)
+        else:
+            self.verbose('No language model found at {}: decoding with a freshly initialised CharLM, '
+                         'as the reference does'.format(lm_path))
+            self.lm = CharLM(self.ds.get_char_dim(), hidden).to(self.device)
+        self.lm.eval()
+        self.lm_weight = self.config['asr']['decode_lm_weight']
+        self.decode_beam_size = self.config['asr']['decode_beam_size']
+        self.njobs = self.config['asr']['decode_jobs']
+        self.decode_step_ratio = self.config['asr']['max_decode_step_ratio']
+        self.decode_file += '_lm{:}'.format(self.config['asr']['decode_lm_weight'])
+
+    def exec(self, lm_weight=None):
+        """-> the decoded strings, one per utterance of the test index, in index order."""
+        if lm_weight is None:
+            lm_weight = self.lm_weight
+        self.verbose('Start decoding (greedy; beam size in the config: {})'.format(self.decode_beam_size))
+        self.verbose('Number of utts to decode : {}, {} per launch.'.format(len(self.test_set), self.decode_group))
+        results, xs, x_lens = [], [], []
+
+        def flush():
+            if xs:
+                results.extend(self.asr_model.decode_many(xs, x_lens, self.lm, self.mapper, lm_weight))
+                del xs[:], x_lens[:]
+
+        for b_ind, (x, y) in enumerate(self.test_set):
+            x, x_len = prepare_x(x, self.device)
+            for i in range(x.shape[0]):              # test_batch_size is 1 in the reference's configs
+                xs.append(x[i:i + 1, :x_len[i]])
+                x_lens.append([x_len[i]])
+            if len(xs) >= self.decode_group:
+                flush()
+        flush()
+        return results
 
 
 class TAETrainer(Solver):

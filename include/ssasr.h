@@ -23,7 +23,8 @@
  *   - return 0 on success, a negative value for an argument error, a positive
  *     hipError_t for a HIP failure.
  *
- * ABI history.  15: inference -- ssasr_charlm, ssasr_charlm_step, ssasr_infer, ssasr_decode_greedy (nothing
+ * ABI history.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
+ * (nothing older changed).  15: inference -- ssasr_charlm, ssasr_charlm_step, ssasr_infer, ssasr_decode_greedy (nothing
  * older changed).  14 and before: the training entry points below.
  *
  * Persistent launches.  Several entry points run a whole layer / decode loop as
@@ -593,6 +594,40 @@ typedef struct ssasr_infer {
 } ssasr_infer;
 
 int ssasr_decode_greedy(const ssasr_infer* d, void* stream);
+
+/* ---- CharLM training (ABI 16) --------------------------------------------------------------------------------
+ * One chunk of CHARLMTrainer.exec (src/trainer.py:229-251) as one forward and one backward launch.  A workgroup
+ * owns 16 batch rows for the whole chunk; workgroups exchange nothing (no status words, nothing to arm), every
+ * loop is bounded by U, B, H or V, and a row's results depend on that row's inputs alone: the same bits at
+ * B = 1 as in any batch.  fp32 throughout (fp32 MFMA, expf, tanhf).
+ * Accepted: V <= 64, H % 16 == 0 with 16 <= H <= 256, any B >= 1 and U >= 1 with U * B < 2^29; every pointer of
+ * `lm` and `ws` 16-byte aligned.  Anything else: a negative code, and the size query returns 0.
+ *
+ * Workspace, ssasr_charlm_train_ws_floats(B, U, H, V) floats, consecutive blocks (R = U * B, row t * B + b):
+ *   G1 [V][3H] rounded up to 16 floats: emb . W_ih1^T + b_ih1 | WT_hh1, WT_ih2, WT_hh2 [H][3H] | WT_out [H][64]
+ *   (written by the forward's prologue kernel) | H1, H2 [U+1][B][H]: the state BEFORE step t in block t |
+ *   S1, S2 [R][4H]: r, z, n, W_hn h + b_hn after the forward; d r_pre, d z_pre, d n_pre, r * d n_pre after the
+ *   backward (d gi = columns [0, 3H), d gh = columns [0, 2H) and [3H, 4H)) | DL [R][64]: softmax after the forward,
+ *   d logits after the backward (classes >= V zero) | OH [R][64]: one-hot of the character fed to the step.
+ * The parameter gradients are products over these blocks (ssasr_gemm_f32, ta = 1, K = R), left to the caller. */
+int64_t ssasr_charlm_train_ws_floats(int64_t B, int64_t U, int64_t H, int64_t V);
+
+/* Forward (src/trainer.py:231-249; per step src/charlm.py:53-56, nn.CrossEntropyLoss(reduction='none'), and on
+ * a sampled step Categorical(softmax).sample(), :245, as the first v with cumsum(exp(l - max))[v] > u * total).
+ * y int32 [B][U] labels; feed int32 [B][U]: the character fed to step t + 1 when step t is teacher-forced
+ * (training passes y); modes int32 [U] (0 teacher, 1 sample); uniforms [U][B] or NULL (every step is then
+ * teacher-forced).  Ids are clamped to [0, V).
+ * -> loss_rows [B]: sum over the steps of -log p[y]; fed int32 [U+1][B]: what each step was fed, row 0 = 0
+ * (<SOS>, :231); logits [U][B][V], optional. */
+int ssasr_charlm_train_fwd(const ssasr_charlm* lm, const int32_t* y, const int32_t* feed, const int32_t* modes,
+                           const float* uniforms, int64_t B, int64_t U, float* loss_rows, int32_t* fed,
+                           float* logits, float* ws, void* stream);
+
+/* Backward through the chunk (loss.backward(), src/trainer.py:250) from the workspace the forward left, with
+ * d loss_rows = dloss for every row (1 / B for the mean of :249).  No gradient flows through a sampled
+ * character.  Rewrites S1, S2 and DL as described above. */
+int ssasr_charlm_train_bwd(const ssasr_charlm* lm, const int32_t* y, int64_t B, int64_t U, float dloss, float* ws,
+                           void* stream);
 
 #ifdef __cplusplus
 }

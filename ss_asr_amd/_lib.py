@@ -8,7 +8,7 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('SSASR_LIB') or os.path.join(_HERE, 'libssasr_hip.so')   # SSASR_LIB: A/B builds
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 P = C.c_void_p
 I64 = C.c_int64
@@ -91,6 +91,9 @@ SIGNATURES = {
     'ssasr_decoder_wgrad': (I32, [C.POINTER(Decoder), C.POINTER(DecoderGrads), I32, P]),
     'ssasr_charlm_step': (I32, [C.POINTER(CharLM), P, P, P, I64, P, P, P, P]),
     'ssasr_decode_greedy': (I32, [C.POINTER(Infer), P]),
+    'ssasr_charlm_train_ws_floats': (I64, [I64, I64, I64, I64]),
+    'ssasr_charlm_train_fwd': (I32, [C.POINTER(CharLM), P, P, P, P, I64, I64, P, P, P, P, P]),
+    'ssasr_charlm_train_bwd': (I32, [C.POINTER(CharLM), P, I64, I64, F32, P, P]),
     'ssasr_ce_loss_fwd': (I32, [P, P, I64, I64, I64, I64, I64, P, P, P]),
     'ssasr_ce_loss_bwd': (I32, [P, P, I64, P, P, I64, I64, I64, P, P]),
     'ssasr_ctc_ws_floats': (I64, [I64, I64, I64, I64]),

@@ -2,8 +2,9 @@
 the same constructor, ``state_dict`` names, order and shapes (``emb.weight``, ``layer_1.*``, ``layer_2.*``,
 ``out.*``), so a reference-trained checkpoint loads strictly.  The nn.Embedding / nn.GRUCell / nn.Linear held
 here are parameter containers only; ``forward`` computes through ``ssasr_charlm_step`` (csrc/infer.hip), and
-``ASR.decode`` fuses the same step into its decode launch (``ssasr_decode_greedy``).  Forward only: this build
-has no LM trainer."""
+``ASR.decode`` fuses the same step into its decode launch (``ssasr_decode_greedy``).  ``forward`` itself carries
+no autograd graph: training runs a whole chunk through ``ssasr_charlm_train_fwd`` / ``_bwd``
+(csrc/charlm_train.hip, ops.charlm_chunk, engine.CharLMTrainStep), driven by ``trainer.CHARLMTrainer``."""
 import torch
 import torch.nn as nn
 

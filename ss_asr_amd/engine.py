@@ -156,6 +156,60 @@ class TAETrainStep:
     finish = ASRTrainStep.finish
 
 
+class CharLMTrainStep:
+    """One CHARLMTrainer step (src/trainer.py:229-251) as a reusable object: the chunk loop as ONE forward
+    launch (ops.charlm_chunk; teacher forcing flipped per step on the host as the reference's random.random()
+    does, :241, the sampled steps drawn in the kernel from device uniforms), ONE backward launch, the parameter
+    gradients as deferred products, then Solver.step -- norm, NaN guard, clip at 5 -- fused with
+    torch.optim.Adam(lr, eps=1e-8) (:215-218) over the model's one flat buffer."""
+
+    def __init__(self, lm, tf_rate, lr=1e-4, eps=1e-8, grad_clip=5.0, opt_type='Adam'):
+        if opt_type != 'Adam':
+            raise NotImplementedError("char_lm.opt.type '%s': the fused CharLM step has Adam only" % opt_type)
+        if not next(lm.parameters()).is_cuda:
+            raise RuntimeError('CharLMTrainStep needs the model on the GPU (no CPU path)')
+        self.lm, self.tf_rate, self.grad_clip = lm, float(tf_rate), grad_clip
+        self.flat = FlatParameters.of(lm)
+        self.optim = FusedAdam([(self.flat.data, self.flat.grad, True)], lr=lr, eps=eps)
+        self._ws = None
+        self.last_done = None
+        self.last_chunk = None
+        self.skipped_steps = 0
+
+    def draw_modes(self, U):
+        """0 teacher / 1 sample per step, the reference's coin (src/trainer.py:241)."""
+        import random
+        return [0 if random.random() <= self.tf_rate else 1 for _ in range(U)]
+
+    def __call__(self, y, modes=None, uniforms=None, feed=None):
+        """y [B, U] labels on the GPU.  Returns the loss tensor (mean over the batch of the per-row sums, :249)."""
+        self._note(self.optim.poll())
+        if not self.flat.clean:
+            self.flat.zero_grad()
+        self.flat.clean = False
+        B, U = y.shape
+        dev = y.device
+        if modes is None:
+            modes = self.draw_modes(U)
+        if not torch.is_tensor(modes):
+            sampled = any(modes)
+            modes = torch.tensor(modes, dtype=torch.int32).to(dev, non_blocking=True)
+            if sampled and uniforms is None:
+                uniforms = torch.rand(U, B, device=dev)
+        chunk = ops.charlm_chunk(self.lm, y, feed=feed, modes=modes, uniforms=uniforms, ws=self._ws)
+        self._ws = chunk.ws
+        ops.charlm_chunk_backward(self.lm, chunk, dloss=1.0 / B)
+        scale = sdist.allreduce_grad(self.flat.grad)
+        self.optim.clip_and_step(self.grad_clip, grad_scale=scale, zero_grad=True)
+        self.flat.clean = True
+        self.last_chunk = chunk
+        settle_collector()
+        return chunk.loss_rows.mean()
+
+    _note = ASRTrainStep._note
+    finish = ASRTrainStep.finish
+
+
 def label_geometry(y_cpu):
     """prepare_y's lengths on the host (src/ASRDataset.py:338): returns
     (y_lens, ans_len)."""

@@ -6,7 +6,7 @@ import importlib
 import sys
 
 NAMES = ('asr', 'trainer', 'ASRDataset', 'preprocess', 'postprocess', 'TrackerHandler', 'LogHandler',
-         'text_autoencoder', 'discriminator', 'speech_autoencoder', 'charlm')
+         'text_autoencoder', 'discriminator', 'speech_autoencoder', 'charlm', 'LMDataset')
 
 
 def install():

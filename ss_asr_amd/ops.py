@@ -1078,3 +1078,110 @@ def decode_greedy(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, wan
     d.att = att.data_ptr() if want_att else None
     check(lib.ssasr_decode_greedy(C.byref(d), _stream()), 'ssasr_decode_greedy')
     return chars, n_chars, scores, att
+
+
+# ---------------------------------------------------------------------------
+# CharLM training: one chunk forward / backward (csrc/charlm_train.hip)
+# ---------------------------------------------------------------------------
+_CHARLM_NAMES = ('emb.weight', 'layer_1.weight_ih', 'layer_1.weight_hh', 'layer_1.bias_ih', 'layer_1.bias_hh',
+                 'layer_2.weight_ih', 'layer_2.weight_hh', 'layer_2.bias_ih', 'layer_2.bias_hh', 'out.weight', 'out.bias')
+
+
+def charlm_ws_layout(B, U, H, V):
+    """{block: (offset, floats)} of the training workspace (include/ssasr.h, ssasr_charlm_train_ws_floats)."""
+    R, out, o = U * B, {}, 0
+    for name, n in (('g1', (V * 3 * H + 15) // 16 * 16), ('wt_hh1', 3 * H * H), ('wt_ih2', 3 * H * H),
+                    ('wt_hh2', 3 * H * H), ('wt_out', 64 * H), ('h1', (U + 1) * B * H), ('h2', (U + 1) * B * H),
+                    ('s1', R * 4 * H), ('s2', R * 4 * H), ('dl', R * 64), ('oh', R * 64)):
+        out[name] = (o, n)
+        o += n
+    out['total'] = o
+    return out
+
+
+class CharLMChunk:
+    """What charlm_chunk returns: loss_rows [B], fed int32 [U+1, B], logits [U, B, V] or None, and what
+    charlm_chunk_backward needs (the workspace, y)."""
+    __slots__ = ('loss_rows', 'fed', 'logits', 'ws', 'y', 'B', 'U')
+
+
+def charlm_chunk(lm, y, feed=None, modes=None, uniforms=None, want_logits=False, ws=None):
+    """The chunk loop of CHARLMTrainer.exec (src/trainer.py:231-249) as one launch: y [B, U] labels, feed [B, U]
+    (default y), modes int32 [U] on the device (default all teacher-forced), uniforms [U, B] for the sampled
+    steps.  ws: a float32 buffer of at least ssasr_charlm_train_ws_floats floats to reuse."""
+    lib = _lib.load()
+    _need_gpu(y, feed, modes, uniforms, ws)
+    s, keep = _charlm_struct(lm)
+    B, U = y.shape
+    H, V = lm.hidden_size, lm.input_size
+    need = int(lib.ssasr_charlm_train_ws_floats(B, U, H, V))
+    if need <= 0:
+        raise RuntimeError('ssasr_charlm_train_fwd: unsupported shape B %d U %d H %d V %d (V <= 64, H %% 16 == 0, '
+                           '16 <= H <= 256)' % (B, U, H, V))
+    assert need == charlm_ws_layout(B, U, H, V)['total']
+    dev = y.device
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, device=dev, dtype=torch.float32)
+    y32 = as_i32(y).contiguous()
+    feed32 = y32 if feed is None else as_i32(feed).contiguous()
+    if modes is None:
+        modes = torch.zeros(U, device=dev, dtype=torch.int32)
+    out = CharLMChunk()
+    out.loss_rows = torch.empty(B, device=dev, dtype=torch.float32)
+    out.fed = torch.empty(U + 1, B, device=dev, dtype=torch.int32)
+    out.logits = torch.empty(U, B, V, device=dev, dtype=torch.float32) if want_logits else None
+    out.ws, out.y, out.B, out.U = ws, y32, B, U
+    check(lib.ssasr_charlm_train_fwd(C.byref(s), _p(y32), _p(feed32), _p(as_i32(modes)),
+                                     _p(None if uniforms is None else _f32c(uniforms)), B, U, _p(out.loss_rows),
+                                     _p(out.fed), _p(out.logits), _p(ws), _stream()), 'ssasr_charlm_train_fwd')
+    return out
+
+
+def charlm_chunk_backward(lm, chunk, dloss=None):
+    """loss.backward() of src/trainer.py:250 for loss = mean(loss_rows) (dloss = 1 / B): the BPTT launch, then
+    every parameter gradient as products over the workspace, ACCUMULATED into the parameters' .grad."""
+    lib = _lib.load()
+    s, keep = _charlm_struct(lm)
+    B, U, H, V = chunk.B, chunk.U, lm.hidden_size, lm.input_size
+    check(lib.ssasr_charlm_train_bwd(C.byref(s), _p(chunk.y), B, U, 1.0 / B if dloss is None else float(dloss),
+                                     _p(chunk.ws), _stream()), 'ssasr_charlm_train_bwd')
+    lay, R = charlm_ws_layout(B, U, H, V), U * B
+    blk = lambda n: chunk.ws[lay[n][0]:lay[n][0] + lay[n][1]]
+    params = dict(lm.named_parameters())
+    for n in _CHARLM_NAMES:
+        if params[n].grad is None:
+            params[n].grad = torch.zeros_like(params[n])
+    g = {n: params[n].grad for n in _CHARLM_NAMES}
+    h1, h2 = blk('h1').view(U + 1, B, H), blk('h2').view(U + 1, B, H)
+    h1_prev, h1_new = h1[:U].reshape(R, H), h1[1:].reshape(R, H)
+    h2_prev, h2_new = h2[:U].reshape(R, H), h2[1:].reshape(R, H)
+    s1, s2 = blk('s1').view(R, 4 * H), blk('s2').view(R, 4 * H)
+    dl, oh = blk('dl').view(R, 64), blk('oh').view(R, 64)
+    ones = torch.ones(R, 1, device=chunk.ws.device, dtype=torch.float32)
+
+    def acc_cols(out, m, lo, hi, b):          # out += m[:, lo:hi]^T . b over the R rows (K = R), rows keep m's stride
+        a = m[:, lo:hi]
+        check(lib.ssasr_gemm_f32(1, 1, hi - lo, b.shape[1], R, 1.0, _p(a), m.stride(0), _p(b), b.stride(0), 1.0,
+                                 _p(out), out.stride(0) if out.dim() == 2 else 1, None, 0, 1, 0, 0, 0, 1, _stream()),
+              'ssasr_gemm_f32')
+
+    col = lambda v: v.view(-1, 1)
+    acc_cols(g['out.weight'], dl, 0, V, h2_new)
+    acc_cols(col(g['out.bias']), dl, 0, V, ones)
+    for cell, sv, x_in, h_prev in (('layer_2', s2, h1_new, h2_prev), ('layer_1', s1, None, h1_prev)):
+        w_hh, b_hh = g[cell + '.weight_hh'], g[cell + '.bias_hh']
+        acc_cols(w_hh[:2 * H], sv, 0, 2 * H, h_prev)
+        acc_cols(w_hh[2 * H:], sv, 3 * H, 4 * H, h_prev)
+        acc_cols(col(b_hh[:2 * H]), sv, 0, 2 * H, ones)
+        acc_cols(col(b_hh[2 * H:]), sv, 3 * H, 4 * H, ones)
+        if x_in is not None:
+            acc_cols(g[cell + '.weight_ih'], sv, 0, 3 * H, x_in)
+            acc_cols(col(g[cell + '.bias_ih']), sv, 0, 3 * H, ones)
+    # layer 1's input side: d gi1 summed per fed character, dG [V, 3H] = onehot^T . d gi1, then through the table
+    dG = torch.empty(V, 3 * H, device=chunk.ws.device, dtype=torch.float32)
+    check(lib.ssasr_gemm_f32(1, 1, V, 3 * H, R, 1.0, _p(oh), 64, _p(s1), 4 * H, 0.0, _p(dG), 3 * H, None, 0, 1, 0, 0, 0,
+                             1, _stream()), 'ssasr_gemm_f32')
+    emb_w, w_ih1 = params['emb.weight'].detach(), params['layer_1.weight_ih'].detach()
+    gemm(dG, emb_w, ta=True, tb=True, out=g['layer_1.weight_ih'], beta=1.0)           # dW_ih1 = dG^T . emb
+    gemm(dG, w_ih1, ta=False, tb=True, out=g['emb.weight'], beta=1.0)                 # d emb = dG . W_ih1
+    gemm(dG, torch.ones(V, 1, device=dG.device), ta=True, tb=True, out=col(g['layer_1.bias_ih']), beta=1.0)

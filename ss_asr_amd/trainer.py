@@ -1,5 +1,5 @@
 """Solver / ASRTrainer with the surface of the reference's src/trainer.py
-(Solver :33-195, ASRTrainer :374-545, ASRTester :547-592, TAETrainer :594-758, SAETrainer :760-907, ADVTrainer :909-1124,
+(Solver :33-195, CHARLMTrainer :197-372, ASRTrainer :374-545, ASRTester :547-592, TAETrainer :594-758, SAETrainer :760-907, ADVTrainer :909-1124,
 asr_seed_train :1126-1177) so that ``src/train.py`` drives it unchanged:
 ``getattr(trainer, 'ASRTrainer')(config, paras)`` then ``load_data()``, ``set_model()``, ``exec()``.
 
@@ -33,6 +33,8 @@ from .LogHandler import LogHandler
 from .TrackerHandler import TrackerHandler
 from .asr import ASR
 from .charlm import CharLM
+from .LMDataset import load_lm_dataset
+from .preprocess import SOS_TKN
 from .optim import FusedAdadelta
 from .postprocess import calc_acc, calc_err, draw_att
 
@@ -154,6 +156,96 @@ class Solver:
 
     def close(self):
         return None
+
+
+class CHARLMTrainer(Solver):
+    """Trains the character language model, src/trainer.py:197-372: the same config keys (char_lm.chunk_size,
+    mdl.tf_rate, mdl.hidden_size, opt.type, opt.learning_rate, train_index), loss per character, tracker best,
+    char_lm_best.cpt / char_lm.cpt (the file ASRTester loads) and text logging.  One iteration of exec() is ONE
+    engine.CharLMTrainStep call fed by the device-resident loader (LMDataset.ResidentLMLoader).  `generate` runs on
+    CharLM.forward, one step per call.  `predict` (:280-317) is left out: only the reference's dead lm_predict.py
+    calls it.  Also reachable as trainer.LMTrainer, the spelling src/train.py:19 offers."""
+
+    def __init__(self, config, paras):
+        super().__init__(config, paras, 'char_lm')
+
+    def load_data(self):
+        self.chunk_size = self.config['char_lm']['chunk_size']
+        self.tf_rate = self.config['char_lm']['mdl']['tf_rate']
+        self.ds, self.train_set = load_lm_dataset(self.config['char_lm']['train_index'], self.chunk_size,
+                                                  self.train_batch_size, shuffle=True, resident=True)
+
+    def set_model(self):
+        from .engine import CharLMTrainStep
+        opt = self.config['char_lm']['opt']
+        if opt['type'] != 'Adam':
+            raise NotImplementedError("char_lm.opt.type '%s': this build trains the CharLM with its fused Adam step "
+                                      "only" % opt['type'])
+        self.lm = self.setup_module(CharLM, self.ckppath, self.ds.get_num_chars(),
+                                    self.config['char_lm']['mdl']['hidden_size'])
+        self.train_step = CharLMTrainStep(self.lm, self.tf_rate, lr=opt['learning_rate'], eps=1e-8, grad_clip=5.0,
+                                          opt_type=opt['type'])
+        self.optim = self.train_step.optim
+
+    def exec(self):
+        self.verbose('Training set total {} batches.'.format(len(self.train_set)))
+        epoch = 0
+        while epoch < self.n_epochs:
+            self.verbose("Starting epoch {} out of {}".format(epoch + 1, self.n_epochs))
+            for b_ind, (_, (_, y)) in enumerate(self.train_set):
+                self.verbose('Batch: {}/{}, global step: {}'.format(b_ind, len(self.train_set), self.tr.step),
+                             progress=True)
+                loss = self.train_step(y)
+                done = self.train_step.last_done
+                if done is not None and done[1]:
+                    self.verbose('Error : grad norm is NaN @ step {}'.format(self.tr.step - 1))
+                wants = (self.tr.step % self.logging_step == 0 or self.tr.step % self.valid_step == 0)
+                if wants:                                     # the only host reads of the loss
+                    loss_by_char = loss.item() / self.chunk_size
+                    self.last_loss_by_char = loss_by_char
+                if self.tr.step % self.logging_step == 0:
+                    self.lg.scalar('train_loss', loss_by_char, self.tr.step)
+                if self.tr.step % self.valid_step == 0:
+                    generated = self.generate()
+                    self.lg.text('text_generate', generated, self.tr.step)
+                    if loss_by_char < self.tr.get_best():
+                        self.tr.set_best(loss_by_char)
+                        torch.save(self.lm.state_dict(), self.best_ckppath)
+                if self.tr.step % self.save_step == 0:
+                    self.verbose("Model saved at step {}".format(self.tr.step))
+                    torch.save(self.lm.state_dict(), self.ckppath)
+                self.tr.do_step()
+            self.verbose('Epoch {} finished'.format(epoch))
+            epoch += 1
+
+    def generate(self, length=100, temp=0.8, start=SOS_TKN):
+        """src/trainer.py:319-364: `length` characters sampled at temperature `temp` after feeding `start`."""
+        with torch.no_grad():
+            h_1, h_2 = self.lm.init_hidden(1, self.device)
+            x = self.ds.s2l(start).to(self.device)
+            out_string = start
+            for i in range(x.shape[0] - 1):
+                out, (h_1, h_2) = self.lm(x[i].view(-1), h_1, h_2)
+            x = x[-1].view(-1)
+            for i in range(length):
+                out, (h_1, h_2) = self.lm(x, h_1, h_2)
+                dist = torch.softmax(out, dim=-1)
+                dist = dist ** (1 / temp)
+                dist = dist / torch.sum(dist, dim=-1)
+                predict = torch.multinomial(dist, 1)[0]
+                predict_str = self.ds.idx2char[predict.item()]
+                out_string += predict_str
+                x = self.ds.s2l(predict_str).to(self.device)
+        return out_string
+
+    def close(self):
+        self.verbose("Finished training! The most recent model will" +
+                     "be saved at step {}".format(self.tr.step))
+        self.train_step.finish()
+        torch.save(self.lm.state_dict(), self.ckppath)
+
+
+LMTrainer = CHARLMTrainer
 
 
 class ASRTrainer(Solver):

@@ -23,7 +23,8 @@
  *   - return 0 on success, a negative value for an argument error, a positive
  *     hipError_t for a HIP failure.
  *
- * ABI history.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
+ * ABI history.  Added under 16 without changing anything older (the version number stays): beam search --
+ * ssasr_beam, ssasr_decode_beam_ws_bytes, ssasr_decode_beam.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
  * (nothing older changed).  15: inference -- ssasr_charlm, ssasr_charlm_step, ssasr_infer, ssasr_decode_greedy (nothing
  * older changed).  14 and before: the training entry points below.
  *
@@ -628,6 +629,59 @@ int ssasr_charlm_train_fwd(const ssasr_charlm* lm, const int32_t* y, const int32
  * character.  Rewrites S1, S2 and DL as described above. */
 int ssasr_charlm_train_bwd(const ssasr_charlm* lm, const int32_t* y, int64_t B, int64_t U, float dloss, float* ws,
                            void* stream);
+
+/* ---- beam search (added under ABI 16) ------------------------------------------------------------------------
+ * The loop of ssasr_decode_greedy as a beam search over K hypotheses per utterance, ONE launch, one workgroup
+ * per utterance for the whole loop; workgroups exchange nothing, nothing spins, every loop is bounded by
+ * max_steps, enc_len, K or a dimension.  Every weight matrix is streamed once per step for all live hypotheses.
+ * Per utterance (row_b = the score row ssasr_decode_greedy computes for hypothesis b):
+ *   start: one live hypothesis, empty prefix, score 0, zero states, input <SOS> = 0;
+ *   step:  width W = K - finished; candidates (b, v), live b, v < V, score_b + row_b[v]; the W best (all of them
+ *          when fewer exist), by score descending, ties to the lower b * V + v.  A chosen candidate with v == eos
+ *          finishes its parent's prefix (<EOS> is not part of the text, its log-probability is part of the
+ *          score); the others are the new live set, in candidate order, each with a copy of its parent's state
+ *          advanced by its own character;
+ *   stop:  no live hypothesis left, or after max_steps steps: what is live then is emitted as it stands;
+ *   output: hypotheses by score descending, ties to the earlier step, then to candidate order; unused slots zero.
+ * No length normalisation, no coverage term, no end-detection heuristic.  K == 1 follows greedy decoding (the
+ * Python surface calls ssasr_decode_greedy for it).  An utterance's results depend on its own frames, enc_len,
+ * K and max_steps alone: the same bits in any batch, at any padded T.
+ * Accepted: the dimensions ssasr_decode_greedy accepts (its LDS bound does not apply: all per-hypothesis state is
+ * in `ws`), 1 <= K <= 32, lm->H <= 4096; ws 16-byte aligned with ws_bytes >= ssasr_decode_beam_ws_bytes(...);
+ * everything else is an argument error before any launch.  `ws` needs no initialisation and is private to the
+ * launch while it runs; a slice per utterance holds, per hypothesis, the Speller and LM states twice
+ * (re-parenting copies from one buffer to the other), the step's intermediates, and the (parent, char)
+ * back-pointers of every step. */
+typedef struct ssasr_beam {
+  /* sizes */
+  int64_t N, T, E, A, D, V, max_steps, K;
+  /* inputs and parameters: the fields of ssasr_infer */
+  const float* feat;
+  const int32_t* enc_len;
+  float* comp;
+  const float* w_psi; const float* b_psi;
+  const float* w_phi;
+  const float* w_ih1; const float* w_hh1; const float* b_ih1; const float* b_hh1;
+  const float* w_ih2; const float* w_hh2; const float* b_ih2; const float* b_hh2;
+  const float* embed;
+  const float* w_ct; const float* b_ct;
+  const ssasr_charlm* lm;   /* HOST pointer; NULL: no LM term */
+  float lm_weight;
+  int32_t eos;
+  /* workspace */
+  float* ws;
+  int64_t ws_bytes;         /* what the caller allocated at ws */
+  /* outputs, written completely by the launch */
+  int32_t* chars;           /* [N][K][max_steps] the hypotheses' characters, best first; zero past n_chars */
+  int32_t* n_chars;         /* [N][K] characters of each hypothesis; max_steps for one the cap ended      */
+  float* hyp_scores;        /* [N][K] summed scores, descending                                           */
+  int32_t* n_hyps;          /* [N] hypotheses emitted, 1 .. K                                             */
+} ssasr_beam;
+
+/* Bytes of `ws` for these sizes (Hl = lm->H, 0 without an LM; S = max_steps); 0 when they are not accepted. */
+int64_t ssasr_decode_beam_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D, int64_t V,
+                                   int64_t Hl, int64_t S);
+int ssasr_decode_beam(const ssasr_beam* d, void* stream);
 
 #ifdef __cplusplus
 }

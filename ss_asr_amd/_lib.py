@@ -60,6 +60,18 @@ class Infer(C.Structure):
         [(n, P) for n in ('chars', 'n_chars', 'scores', 'att')])
 
 
+class Beam(C.Structure):
+    """struct ssasr_beam (include/ssasr.h)."""
+    _fields_ = (
+        [(n, I64) for n in ('N', 'T', 'E', 'A', 'D', 'V', 'max_steps', 'K')] +
+        [(n, P) for n in ('feat', 'enc_len', 'comp', 'w_psi', 'b_psi', 'w_phi',
+                          'w_ih1', 'w_hh1', 'b_ih1', 'b_hh1', 'w_ih2', 'w_hh2', 'b_ih2', 'b_hh2',
+                          'embed', 'w_ct', 'b_ct')] +
+        [('lm', C.POINTER(CharLM)), ('lm_weight', F32), ('eos', C.c_int32)] +
+        [('ws', P), ('ws_bytes', I64)] +
+        [(n, P) for n in ('chars', 'n_chars', 'hyp_scores', 'n_hyps')])
+
+
 SIGNATURES = {
     'ssasr_abi_version': (I32, []),
     'ssasr_set_option': (I32, [C.c_char_p, I32]),
@@ -91,6 +103,8 @@ SIGNATURES = {
     'ssasr_decoder_wgrad': (I32, [C.POINTER(Decoder), C.POINTER(DecoderGrads), I32, P]),
     'ssasr_charlm_step': (I32, [C.POINTER(CharLM), P, P, P, I64, P, P, P, P]),
     'ssasr_decode_greedy': (I32, [C.POINTER(Infer), P]),
+    'ssasr_decode_beam_ws_bytes': (I64, [I64] * 9),
+    'ssasr_decode_beam': (I32, [C.POINTER(Beam), P]),
     'ssasr_charlm_train_ws_floats': (I64, [I64, I64, I64, I64]),
     'ssasr_charlm_train_fwd': (I32, [C.POINTER(CharLM), P, P, P, P, I64, I64, P, P, P, P, P]),
     'ssasr_charlm_train_bwd': (I32, [C.POINTER(CharLM), P, I64, I64, F32, P, P]),

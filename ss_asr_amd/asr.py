@@ -255,6 +255,9 @@ class ASR(nn.Module):
         self.last_encoded = None
         # decode_many's device results: (chars [N, steps] int32, n_chars [N] int32, scores [N, steps, V], att [N, steps, T'])
         self.last_decode = None
+        # decode_nbest's device results for beam_size > 1: (chars [N, K, steps] int32, n_chars [N, K] int32,
+        # hyp_scores [N, K], n_hyps [N] int32)
+        self.last_beam = None
         self.init_parameters()
 
     def init_parameters(self):
@@ -329,37 +332,76 @@ class ASR(nn.Module):
             host = att.detach().cpu()
         return encode_len, logits, host
 
-    def decode(self, x, x_len, rnn_lm, mapper, lm_weight, max_decoding_steps=200):
+    def decode(self, x, x_len, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1):
         """src/asr.py:112-173: greedy decoding of ONE utterance (x [1, seq, features], x_len from prepare_x)
         until <EOS> or max_decoding_steps (200 in the reference, :128), every step's character scores being
         log_softmax(speller) + lm_weight * log_softmax(rnn_lm).  Returns the decoded string.  rnn_lm None: no LM
-        term.  The whole loop is one launch (ssasr_decode_greedy)."""
+        term.  The whole loop is one launch (ssasr_decode_greedy).  beam_size > 1: the best hypothesis of a beam
+        search of that width (decode_many)."""
         assert len(x.shape) == 3 and x.shape[0] == 1
-        return self.decode_many([x], [x_len], rnn_lm, mapper, lm_weight, max_decoding_steps=max_decoding_steps)[0]
+        return self.decode_many([x], [x_len], rnn_lm, mapper, lm_weight, max_decoding_steps=max_decoding_steps,
+                                beam_size=beam_size)[0]
 
-    def decode_many(self, xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=200):
+    def _encode_packed(self, xs, x_lens):
+        """Each utterance encoded alone, packed to ([N, T'max, E], int32 [N] frame counts on the device)."""
+        feats, enc_lens = [], []
+        for x, x_len in zip(xs, x_lens):
+            assert len(x.shape) == 3 and x.shape[0] == 1
+            feat, enc_len = self.encoder(x, x_len)
+            feats.append(feat)
+            enc_lens.append(int(enc_len[0]))
+        dev = feats[0].device
+        tmax = max(f.shape[1] for f in feats)
+        if len(feats) == 1:
+            packed = feats[0]
+        else:
+            packed = torch.zeros(len(feats), tmax, feats[0].shape[2], device=dev, dtype=torch.float32)
+            for n, f in enumerate(feats):
+                packed[n, :f.shape[1]] = f[0]
+        return packed, _dev_i32(enc_lens, dev)
+
+    def decode_many(self, xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1):
         """decode() for a list of single utterances in ONE decode launch.  Each utterance is encoded alone
         (blstm_4 recurs over the utterance axis, src/asr.py:237-238, :262: a batched encoder would change every
         transcript); the encoder outputs are packed to [N, T'max, E] and every utterance gets a workgroup of its
-        own.  Returns the N strings; last_decode keeps (chars, n_chars, scores, att) on the device."""
-        feats, enc_lens = [], []
+        own.  Returns the N strings; last_decode keeps (chars, n_chars, scores, att) on the device.
+        beam_size > 1 (at most 32): beam search of that width in one launch (ssasr_decode_beam; no length
+        normalisation); returns each utterance's best hypothesis and keeps (chars [N, K, steps], n_chars [N, K],
+        hyp_scores [N, K], n_hyps [N]) on the device in last_beam; last_decode is left as it was."""
+        if beam_size != 1:
+            return [nbest[0][0] for nbest in self.decode_nbest(xs, x_lens, rnn_lm, mapper, lm_weight, beam_size,
+                                                               max_decoding_steps=max_decoding_steps)]
         with torch.no_grad():
-            for x, x_len in zip(xs, x_lens):
-                assert len(x.shape) == 3 and x.shape[0] == 1
-                feat, enc_len = self.encoder(x, x_len)
-                feats.append(feat)
-                enc_lens.append(int(enc_len[0]))
-            dev = feats[0].device
-            tmax = max(f.shape[1] for f in feats)
-            if len(feats) == 1:
-                packed = feats[0]
-            else:
-                packed = torch.zeros(len(feats), tmax, feats[0].shape[2], device=dev, dtype=torch.float32)
-                for n, f in enumerate(feats):
-                    packed[n, :f.shape[1]] = f[0]
+            packed, enc_lens = self._encode_packed(xs, x_lens)
             self.last_decode = ops.decode_greedy(
-                packed, _dev_i32(enc_lens, dev), self._decoder_params(),
+                packed, enc_lens, self._decoder_params(),
                 (self.attention.psi.weight, self.attention.psi.bias), rnn_lm, lm_weight,
                 mapper.char_to_ind(EOS_TKN), max_decoding_steps)
         chars, n_chars = self.last_decode[0].cpu().tolist(), self.last_decode[1].cpu().tolist()
         return [''.join(mapper.ind_to_char(c) for c in row[:n]) for row, n in zip(chars, n_chars)]
+
+    def decode_nbest(self, xs, x_lens, rnn_lm, mapper, lm_weight, beam_size, max_decoding_steps=200):
+        """Beam search over a list of single utterances in ONE launch: per utterance the list of (text, score),
+        best first, score = the sum of the chosen characters' log_softmax(speller) + lm_weight *
+        log_softmax(rnn_lm) entries (<EOS>'s included when it ended the hypothesis; no length normalisation).
+        beam_size 1 is greedy decoding (decode_many, last_decode); beam_size 2 .. 32 sets last_beam."""
+        beam_size = int(beam_size)
+        if not 1 <= beam_size <= ops.MAX_BEAM:
+            raise ValueError('beam_size must be in 1..%d, got %d' % (ops.MAX_BEAM, beam_size))
+        if beam_size == 1:
+            texts = self.decode_many(xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=max_decoding_steps)
+            chars, n_chars, scores, _ = self.last_decode
+            steps = torch.clamp(n_chars + 1, max=max_decoding_steps)            # executed steps: <EOS>'s too
+            taken = torch.gather(scores, 2, chars.long().unsqueeze(2)).squeeze(2)
+            mask = torch.arange(chars.shape[1], device=chars.device).unsqueeze(0) < steps.unsqueeze(1)
+            totals = (taken * mask).sum(1).cpu().tolist()
+            return [[(t, s)] for t, s in zip(texts, totals)]
+        with torch.no_grad():
+            packed, enc_lens = self._encode_packed(xs, x_lens)
+            self.last_beam = ops.decode_beam(
+                packed, enc_lens, self._decoder_params(),
+                (self.attention.psi.weight, self.attention.psi.bias), rnn_lm, lm_weight,
+                mapper.char_to_ind(EOS_TKN), max_decoding_steps, beam_size)
+        chars, n_chars, hyp_scores, n_hyps = [t.cpu().tolist() for t in self.last_beam]
+        return [[(''.join(mapper.ind_to_char(c) for c in chars[i][k][:n_chars[i][k]]), hyp_scores[i][k])
+                 for k in range(n_hyps[i])] for i in range(len(xs))]

@@ -1,6 +1,7 @@
 // Inference: the greedy decode loop of ASR.decode (src/asr.py:112-173) with the CharLM term
-// (src/charlm.py:46-57) as ONE launch for N encoded utterances, and one CharLM step for callers
-// that drive the language model themselves.
+// (src/charlm.py:46-57) as ONE launch for N encoded utterances, the same loop as a beam search over up to 32
+// hypotheses per utterance (decode_beam_kernel, below), and one CharLM step for callers that drive the
+// language model themselves.
 //
 // One workgroup owns one utterance for its whole loop.  Nothing is exchanged between workgroups:
 // no status words, no spins, no arena.  Every loop is bounded by max_steps / enc_len / a dimension,
@@ -340,6 +341,424 @@ __global__ __launch_bounds__(kThreads) void decode_greedy_kernel(InferDev p) {
     for (int64_t i = (int64_t)step * T + tid; i < (int64_t)p.max_steps * T; i += kThreads) att[i] = 0.f;
 }
 
+// ---- beam search ------------------------------------------------------------------------------------------------
+// decode_beam_kernel: the loop above for up to K hypotheses of one utterance in ONE workgroup.
+// Layout.  A workgroup owns an utterance for the whole loop, as in decode_greedy_kernel; nothing is exchanged
+// between workgroups, nothing spins, and every loop is bounded by max_steps, enc_len, K or a dimension.
+// comp = tanh(psi(feat)) is computed once and shared by all hypotheses.  Every weight matrix is streamed ONCE
+// per step for all live hypotheses: matmat keeps kRows weight rows against up to kHyps input vectors in flight
+// (kRows * kHyps accumulators per lane); more than kHyps live hypotheses take one pass per kHyps.  feat is
+// streamed once per step for the context sums of all live hypotheses in the same way.
+// Where the state lives (one rule, whatever the sizes): everything that is per hypothesis -- h1, c1, h2, c2 and
+// the LM's two hidden rows (double-buffered: after the selection a new slot's state is a COPY of its parent's
+// row into the other buffer, never an in-place shuffle), the step's inputs and intermediates (embedding |
+// context, q, gates, energies, LM gates, logits) and the back-pointers (parent, char) per step and slot -- is
+// in the caller's workspace in global memory, a slice per workgroup that no other workgroup touches (about
+// 8 KB of state per hypothesis at D 256, E 512, Hl 128: 32 hypotheses do not fit 160 KB of LDS).  The slice is
+// L2 / L1 resident; writer and reader phases are separated by phase_sync(): a workgroup-scope fence and the
+// workgroup barrier.  LDS holds only what the selection needs: the K * 64 candidate scores, the hypotheses'
+// scores, the chosen / finished lists and the reduction scratch (about 10 KB, static).
+// Selection: at most K * V <= 32 * 64 candidates score_b + row_b[v]; W = min(K - finished, live * V) rounds of a
+// block-wide arg-max, ties to the lower flat index b * 64 + v (the order of b * V + v); a chosen candidate is
+// struck out with a NaN, which no score can be (NaN rows are scored -inf).
+// An utterance's results depend on its frames, enc_len, K and max_steps alone, never on N or the padded T.
+constexpr int kHyps = 8;                  // input vectors one pass of matmat holds against a weight row group
+constexpr int kMaxBeam = 32;
+constexpr int kNone = 1 << 30;
+
+__device__ __forceinline__ void phase_sync() {
+  __threadfence_block();
+  __syncthreads();
+}
+
+// out[b * os + r] = act(w1[r] . x1[b * xs1 ..] + w2[r] . x2[b * xs2 ..] + b1[r] + b2[r]) for r < rows, b < nb <= NB;
+// the contract of matvec otherwise (k1 / k2 multiples of 4, 16-byte aligned rows and vectors, k2 = 0: one segment).
+template <int NB>
+__device__ void matmat_n(const float* w1, int64_t ld1, const float* x1, int64_t xs1, int k1,
+                         const float* w2, int64_t ld2, const float* x2, int64_t xs2, int k2,
+                         const float* __restrict__ b1, const float* __restrict__ b2, int rows, int act,
+                         float* out, int64_t os, int nb) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int r0 = wave * kRows; r0 < rows; r0 += kWaves * kRows) {
+    float acc[kRows][NB];
+    const float* p1[kRows];
+    const float* p2[kRows];
+#pragma unroll
+    for (int j = 0; j < kRows; ++j) {
+      const int r = min(r0 + j, rows - 1);          // rows past the end repeat the last one and are dropped
+#pragma unroll
+      for (int b = 0; b < NB; ++b) acc[j][b] = 0.f;
+      p1[j] = w1 + (int64_t)r * ld1;
+      p2[j] = k2 ? w2 + (int64_t)r * ld2 : nullptr;
+    }
+    for (int k = lane * 4; k < k1; k += 256) {
+      float4 w[kRows];
+#pragma unroll
+      for (int j = 0; j < kRows; ++j) w[j] = *reinterpret_cast<const float4*>(p1[j] + k);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {                // vectors past nb repeat the last one and are dropped
+        const float4 x = *reinterpret_cast<const float4*>(x1 + (int64_t)min(b, nb - 1) * xs1 + k);
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) acc[j][b] = dot4(w[j], x, acc[j][b]);
+      }
+    }
+    for (int k = lane * 4; k < k2; k += 256) {
+      float4 w[kRows];
+#pragma unroll
+      for (int j = 0; j < kRows; ++j) w[j] = *reinterpret_cast<const float4*>(p2[j] + k);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        const float4 x = *reinterpret_cast<const float4*>(x2 + (int64_t)min(b, nb - 1) * xs2 + k);
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) acc[j][b] = dot4(w[j], x, acc[j][b]);
+      }
+    }
+    float v = 0.f;                                  // lane j * NB + b keeps the sum of row j, vector b
+#pragma unroll
+    for (int j = 0; j < kRows; ++j)
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        const float s = wave_sum(acc[j][b]);
+        if (lane == j * NB + b) v = s;
+      }
+    const int j = lane / NB, b = lane % NB;
+    if (lane < kRows * NB && r0 + j < rows && b < nb) {
+      const int r = r0 + j;
+      if (b1) v += b1[r];
+      if (b2) v += b2[r];
+      out[(int64_t)b * os + r] = act == 1 ? tanhf(v) : v;
+    }
+  }
+}
+
+// matmat_n over n vectors, kHyps at a time; the last pass takes the narrowest form that holds what is left
+__device__ void matmat(const float* w1, int64_t ld1, const float* x1, int64_t xs1, int k1,
+                       const float* w2, int64_t ld2, const float* x2, int64_t xs2, int k2,
+                       const float* __restrict__ b1, const float* __restrict__ b2, int rows, int act,
+                       float* out, int64_t os, int n) {
+  for (int b0 = 0; b0 < n; b0 += kHyps) {
+    const int nb = min(kHyps, n - b0);
+    const float* y1 = x1 + (int64_t)b0 * xs1;
+    const float* y2 = k2 ? x2 + (int64_t)b0 * xs2 : nullptr;
+    float* o = out + (int64_t)b0 * os;
+    if (nb == 1) matmat_n<1>(w1, ld1, y1, xs1, k1, w2, ld2, y2, xs2, k2, b1, b2, rows, act, o, os, nb);
+    else if (nb == 2) matmat_n<2>(w1, ld1, y1, xs1, k1, w2, ld2, y2, xs2, k2, b1, b2, rows, act, o, os, nb);
+    else if (nb <= 4) matmat_n<4>(w1, ld1, y1, xs1, k1, w2, ld2, y2, xs2, k2, b1, b2, rows, act, o, os, nb);
+    else matmat_n<kHyps>(w1, ld1, y1, xs1, k1, w2, ld2, y2, xs2, k2, b1, b2, rows, act, o, os, nb);
+  }
+}
+
+// workspace slice of one utterance (floats; every block starts on 16 bytes)
+struct BeamWs {
+  int64_t st, xin, lmx, q, gates, en, part, gi, gh, lg, lmlg, bp, total;
+  int Sz, Tp, G;
+};
+__host__ __device__ inline int64_t up4l(int64_t v) { return (v + 3) & ~(int64_t)3; }
+__host__ __device__ inline BeamWs beam_ws_map(int K, int T, int E, int A, int D, int Hl, int S) {
+  BeamWs m;
+  const int ncol4 = E / 4;
+  m.Sz = 4 * D + 2 * Hl;                  // h1 | c1 | h2 | c2 | LM h1 | LM h2 of one hypothesis
+  m.Tp = up4(T);
+  m.G = ncol4 >= kThreads ? 1 : kThreads / ncol4;      // frame groups of the context sum
+  int64_t o = 0;
+  m.st = o; o += 2 * (int64_t)K * m.Sz;   // two buffers of K rows
+  m.xin = o; o += (int64_t)K * (D + E);   // [embedding of the last character | context]
+  m.lmx = o; o += (int64_t)K * Hl;
+  m.q = o; o += (int64_t)K * A;
+  m.gates = o; o += (int64_t)K * 4 * D;
+  m.en = o; o += (int64_t)K * m.Tp;       // energies, then attention weights
+  m.part = o; o += m.G > 1 ? (int64_t)m.G * K * E : 0;   // partial context sums [G][K][E]
+  m.gi = o; o += (int64_t)K * 3 * Hl;
+  m.gh = o; o += (int64_t)K * 3 * Hl;
+  m.lg = o; o += (int64_t)K * 64;
+  m.lmlg = o; o += (int64_t)K * 64;
+  m.bp = o; o += up4l((int64_t)S * K);    // int32 back-pointers [S][K]: parent | char << 8
+  m.total = up4l(o);
+  return m;
+}
+
+struct BeamDev {
+  InferDev in;                            // in.chars [N][K][S], in.n_chars [N][K]; in.scores / in.att unused
+  int K;
+  float* ws;
+  float* hyp_scores;
+  int32_t* n_hyps;
+};
+
+__global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd) {
+  __shared__ float cand[kMaxBeam * 64];            // score_b + row_b[v]; NaN: struck out
+  __shared__ float score[2][kMaxBeam];             // live hypotheses' scores, by step parity
+  __shared__ float redv[kWaves];
+  __shared__ int redi[kWaves];
+  __shared__ int pick[kMaxBeam];                   // chosen flat indices, candidate order
+  __shared__ float pick_score[kMaxBeam];
+  __shared__ int par[kMaxBeam], chr[kMaxBeam];     // new live slots: parent slot, character
+  __shared__ float fin_score[kMaxBeam];            // finished / capped hypotheses in (step, candidate order)
+  __shared__ int fin_len[kMaxBeam], fin_par[kMaxBeam];
+  __shared__ int counts[2];                        // new live slots, finished hypotheses
+
+  const InferDev& p = bd.in;
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int T = p.T, E = p.E, A = p.A, D = p.D, V = p.V, Hl = p.lm.H, K = bd.K, S = p.max_steps;
+  const BeamWs m = beam_ws_map(K, T, E, A, D, Hl, S);
+  float* ws = bd.ws + (int64_t)n * m.total;
+  float *xin = ws + m.xin, *lmx = ws + m.lmx, *q = ws + m.q, *gates = ws + m.gates, *en = ws + m.en,
+        *part = ws + m.part, *gi = ws + m.gi, *gh = ws + m.gh, *lg = ws + m.lg, *lmlg = ws + m.lmlg;
+  int32_t* bp = reinterpret_cast<int32_t*>(ws + m.bp);
+  const int Sz = m.Sz, Tp = m.Tp, G = m.G, XI = D + E, ncol4 = E / 4;
+
+  const int len = min(max(p.enc_len[n], 1), T);      // frames this utterance attends over
+  const float* feat = p.feat + (int64_t)n * T * E;
+  float* comp = p.comp + (int64_t)n * T * A;
+  int32_t* chars = p.chars + (int64_t)n * K * S;
+  int32_t* n_chars = p.n_chars + (int64_t)n * K;
+  float* hyp_scores = bd.hyp_scores + (int64_t)n * K;
+
+  // comp = tanh(psi(feat)) for this utterance's frames, once, shared by every hypothesis: W_psi against the
+  // frames as vectors
+  matmat(p.w_psi, E, feat, E, E, nullptr, 0, nullptr, 0, 0, p.b_psi, nullptr, A, 1, comp, A, len);
+  // one live hypothesis: zero states, score 0, <SOS> = 0 as the input character
+  float* cur = ws + m.st;
+  float* nxt = cur + (int64_t)K * Sz;
+  for (int i = tid; i < Sz; i += kThreads) cur[i] = 0.f;
+  copy_row(xin, p.embed, D);
+  if (Hl) copy_row(lmx, p.lm.emb, Hl);
+  if (tid == 0) score[0][0] = 0.f;
+  phase_sync();
+
+  int live = 1, nfin = 0, step = 0;
+  for (; step < S && live > 0; ++step) {
+    float *h1 = cur, *c1 = cur + D, *h2 = cur + 2 * D, *c2 = cur + 3 * D, *lmh1 = cur + 4 * D, *lmh2 = lmh1 + Hl;
+    const float* sc = score[step & 1];
+    float* sc_new = score[(step + 1) & 1];
+    // 1: q = tanh(phi(h1)) | LM layer 1 products
+    matmat(p.w_phi, D, h1, Sz, D, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, A, 1, q, A, live);
+    if (Hl) {
+      matmat(p.lm.w_ih1, Hl, lmx, Hl, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_ih1, nullptr, 3 * Hl, 0, gi, 3 * Hl, live);
+      matmat(p.lm.w_hh1, Hl, lmh1, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_hh1, nullptr, 3 * Hl, 0, gh, 3 * Hl, live);
+    }
+    phase_sync();
+    // 2: energies over the utterance's frames | LM layer 1 update
+    for (int i = tid; i < live * Hl; i += kThreads) {
+      const int b = i / Hl, u = i % Hl;
+      const float *a = gi + (int64_t)b * 3 * Hl, *c = gh + (int64_t)b * 3 * Hl;
+      float* h = lmh1 + (int64_t)b * Sz;
+      const float r = sigmoid_exact(a[u] + c[u]), z = sigmoid_exact(a[Hl + u] + c[Hl + u]);
+      const float nn = tanhf(a[2 * Hl + u] + r * c[2 * Hl + u]);
+      h[u] = (1.f - z) * nn + z * h[u];
+    }
+    matmat(comp, A, q, A, A, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, len, 0, en, Tp, live);
+    phase_sync();
+    // 3: softmax over the frames, a wave per hypothesis | LM layer 2 products
+    for (int b = wave; b < live; b += kWaves) {
+      float* row = en + (int64_t)b * Tp;
+      float mx = -INFINITY;
+      for (int t = lane; t < len; t += 64) mx = fmaxf(mx, row[t]);
+      mx = wave_max(mx);
+      float sum = 0.f;
+      for (int t = lane; t < len; t += 64) {
+        const float ex = expf(row[t] - mx);
+        row[t] = ex;
+        sum += ex;
+      }
+      sum = wave_sum(sum);
+      for (int t = lane; t < len; t += 64) row[t] = row[t] / sum;
+    }
+    if (Hl) {
+      matmat(p.lm.w_ih2, Hl, lmh1, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_ih2, nullptr, 3 * Hl, 0, gi, 3 * Hl, live);
+      matmat(p.lm.w_hh2, Hl, lmh2, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_hh2, nullptr, 3 * Hl, 0, gh, 3 * Hl, live);
+    }
+    phase_sync();
+    // 4: context = att . feat: a thread sums one float4 column over its group's frames for kHyps hypotheses, so
+    // feat is read once per kHyps of them | LM layer 2 update
+    for (int b0 = 0; b0 < live; b0 += kHyps) {
+      const int nb = min(kHyps, live - b0);
+      const float* att = en + (int64_t)b0 * Tp;
+      const int g = G == 1 ? 0 : tid / ncol4;
+      for (int c = G == 1 ? tid : tid % ncol4; c < ncol4 && g < G; c += kThreads) {
+        float4 s[kHyps];
+#pragma unroll
+        for (int j = 0; j < kHyps; ++j) s[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int t = g; t < len; t += G) {
+          const float4 v = *reinterpret_cast<const float4*>(feat + (int64_t)t * E + c * 4);
+#pragma unroll
+          for (int j = 0; j < kHyps; ++j)
+            if (j < nb) {
+              const float a = att[(int64_t)j * Tp + t];
+              s[j].x = fmaf(a, v.x, s[j].x); s[j].y = fmaf(a, v.y, s[j].y);
+              s[j].z = fmaf(a, v.z, s[j].z); s[j].w = fmaf(a, v.w, s[j].w);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kHyps; ++j)
+          if (j < nb) {
+            float* dst = G == 1 ? xin + (int64_t)(b0 + j) * XI + D + c * 4
+                                : part + ((int64_t)g * K + b0 + j) * E + c * 4;
+            *reinterpret_cast<float4*>(dst) = s[j];
+          }
+      }
+    }
+    for (int i = tid; i < live * Hl; i += kThreads) {
+      const int b = i / Hl, u = i % Hl;
+      const float *a = gi + (int64_t)b * 3 * Hl, *c = gh + (int64_t)b * 3 * Hl;
+      float* h = lmh2 + (int64_t)b * Sz;
+      const float r = sigmoid_exact(a[u] + c[u]), z = sigmoid_exact(a[Hl + u] + c[Hl + u]);
+      const float nn = tanhf(a[2 * Hl + u] + r * c[2 * Hl + u]);
+      h[u] = (1.f - z) * nn + z * h[u];
+    }
+    phase_sync();
+    if (G > 1) {
+      for (int i = tid; i < live * E; i += kThreads) {
+        const int b = i / E, e = i % E;
+        float s = part[(int64_t)b * E + e];
+        for (int g = 1; g < G; ++g) s += part[((int64_t)g * K + b) * E + e];
+        xin[(int64_t)b * XI + D + e] = s;
+      }
+      phase_sync();
+    }
+    // 5: Speller cell 1 on [embedding | context] | LM output layer
+    matmat(p.w_ih1, XI, xin, XI, XI, p.w_hh1, D, h1, Sz, D, p.b_ih1, p.b_hh1, 4 * D, 0, gates, 4 * D, live);
+    if (Hl) matmat(p.lm.w_out, Hl, lmh2, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_out, nullptr, V, 0, lmlg, 64, live);
+    phase_sync();
+    for (int b = 0; b < live; ++b) lstm_update(gates + (int64_t)b * 4 * D, h1 + (int64_t)b * Sz, c1 + (int64_t)b * Sz, D);
+    phase_sync();
+    // 6: cell 2
+    matmat(p.w_ih2, D, h1, Sz, D, p.w_hh2, D, h2, Sz, D, p.b_ih2, p.b_hh2, 4 * D, 0, gates, 4 * D, live);
+    phase_sync();
+    for (int b = 0; b < live; ++b) lstm_update(gates + (int64_t)b * 4 * D, h2 + (int64_t)b * Sz, c2 + (int64_t)b * Sz, D);
+    phase_sync();
+    // 7: char_trans
+    matmat(p.w_ct, D, h2, Sz, D, nullptr, 0, nullptr, 0, 0, p.b_ct, nullptr, V, 0, lg, 64, live);
+    phase_sync();
+    // 8: candidates score_b + log_softmax(asr) + lm_weight * log_softmax(lm), a wave per hypothesis
+    for (int b = wave; b < live; b += kWaves) {
+      const float x = lane < V ? lg[b * 64 + lane] : -INFINITY;
+      const float xm = wave_max(x);
+      const float xs = wave_sum(lane < V ? expf(x - xm) : 0.f);
+      float fin = x - xm - logf(xs);
+      if (Hl) {
+        const float y = lane < V ? lmlg[b * 64 + lane] : -INFINITY;
+        const float ym = wave_max(y);
+        const float ys = wave_sum(lane < V ? expf(y - ym) : 0.f);
+        fin = fin + p.lm_weight * (y - ym - logf(ys));
+      }
+      fin += sc[b];
+      cand[b * 64 + lane] = (lane < V && fin == fin) ? fin : -INFINITY;      // a NaN is never chosen before a number
+    }
+    __syncthreads();
+    // 9: the W best, in order: W rounds of a block-wide arg-max, ties to the lower flat index
+    const int width = min(K - nfin, live * V);
+    for (int i = 0; i < width; ++i) {
+      float bv = -INFINITY;
+      int bi = kNone;
+      for (int c = tid; c < live * 64; c += kThreads) {
+        const float v = cand[c];
+        if ((c & 63) < V && v == v && (bi == kNone || v > bv)) {
+          bv = v;
+          bi = c;
+        }
+      }
+      const float wv = wave_max(bv);
+      const int wi = (int)-wave_max(-(float)((bi != kNone && bv == wv) ? bi : kNone));    // indices < 2^24: exact
+      if (lane == 0) {
+        redv[wave] = wv;
+        redi[wave] = wi;
+      }
+      __syncthreads();
+      float best = -INFINITY;
+      int at = kNone;
+      for (int w = 0; w < kWaves; ++w) {
+        const float v = redv[w];
+        const int c = redi[w];
+        if (c != kNone && (at == kNone || v > best || (v == best && c < at))) {
+          best = v;
+          at = c;
+        }
+      }
+      at = min(at, live * 64 - 1);                  // every round has a candidate left (width <= live * V)
+      if (tid == 0) {
+        pick[i] = at;
+        pick_score[i] = best;
+        cand[at] = __builtin_nanf("");
+      }
+      __syncthreads();
+    }
+    // 10: <EOS> candidates finish their parent's prefix; the others are the new live set, in candidate order
+    if (tid == 0) {
+      int nl = 0, nf = nfin;
+      for (int i = 0; i < width; ++i) {
+        const int b = pick[i] >> 6, v = pick[i] & 63;
+        if (v == p.eos) {
+          fin_score[nf] = pick_score[i];
+          fin_len[nf] = step;                       // a hypothesis live at step s has s characters
+          fin_par[nf] = b;
+          ++nf;
+        } else {
+          par[nl] = b;
+          chr[nl] = v;
+          sc_new[nl] = pick_score[i];
+          bp[(int64_t)step * K + nl] = b | (v << 8);
+          ++nl;
+        }
+      }
+      counts[0] = nl;
+      counts[1] = nf;
+    }
+    __syncthreads();
+    const int nl = counts[0];
+    nfin = counts[1];
+    // 11: a new slot's state is its parent's row, copied into the other buffer; its inputs are its character's
+    for (int i = tid; i < nl * (Sz / 4); i += kThreads) {
+      const int j = i / (Sz / 4), o = i % (Sz / 4);
+      reinterpret_cast<float4*>(nxt + (int64_t)j * Sz)[o] = reinterpret_cast<const float4*>(cur + (int64_t)par[j] * Sz)[o];
+    }
+    for (int i = tid; i < nl * D; i += kThreads) {
+      const int j = i / D, u = i % D;
+      xin[(int64_t)j * XI + u] = p.embed[(int64_t)chr[j] * D + u];
+    }
+    for (int i = tid; i < nl * Hl; i += kThreads) {
+      const int j = i / Hl, u = i % Hl;
+      lmx[(int64_t)j * Hl + u] = p.lm.emb[(int64_t)chr[j] * Hl + u];
+    }
+    phase_sync();
+    float* t = cur;
+    cur = nxt;
+    nxt = t;
+    live = nl;
+  }
+  // the cap: what is still live is emitted as it stands (no <EOS> term), after the finished ones of equal score
+  if (tid == 0) {
+    const float* sc = score[step & 1];
+    for (int j = 0; j < live; ++j) {
+      fin_score[nfin + j] = sc[j];
+      fin_len[nfin + j] = step;
+      fin_par[nfin + j] = j;
+    }
+  }
+  const int total = nfin + live;                    // <= K: finished + width == K at every step, live <= width
+  for (int64_t i = tid; i < (int64_t)K * S; i += kThreads) chars[i] = 0;
+  if (tid < K) {
+    n_chars[tid] = 0;
+    hyp_scores[tid] = 0.f;
+  }
+  if (tid == 0) bd.n_hyps[n] = total;
+  phase_sync();
+  // output order: score descending, ties to the earlier entry of the (step, candidate order) list
+  if (tid < total) {
+    const float s = fin_score[tid];
+    int rank = 0;
+    for (int j = 0; j < total; ++j) rank += (fin_score[j] > s || (fin_score[j] == s && j < tid)) ? 1 : 0;
+    hyp_scores[rank] = s;
+    n_chars[rank] = fin_len[tid];
+    int slot = fin_par[tid];
+    for (int pos = fin_len[tid] - 1; pos >= 0; --pos) {         // trace the back-pointers
+      const int e = bp[(int64_t)pos * K + slot];
+      chars[(int64_t)rank * S + pos] = e >> 8;
+      slot = e & 255;
+    }
+  }
+}
+
 // One CharLM.forward (src/charlm.py:46-57) for B rows, a workgroup per row.
 struct LmStepDev {
   LmDev lm;
@@ -425,6 +844,54 @@ extern "C" int ssasr_decode_greedy(const ssasr_infer* dp, void* stream) {
   p.chars = d.chars; p.n_chars = d.n_chars; p.scores = d.scores; p.att = d.att;
   if (const int rc = allow_lds(reinterpret_cast<const void*>(decode_greedy_kernel), bytes)) return rc;
   hipLaunchKernelGGL(decode_greedy_kernel, dim3((unsigned)d.N), dim3(kThreads), bytes, (hipStream_t)stream, p);
+  SSASR_LAUNCH_CHECK();
+  return SSASR_OK;
+}
+
+namespace {
+// the dimensions ssasr_decode_greedy takes (V <= 64: one wave holds a score row), without its LDS bound: the
+// beam kernel keeps no per-hypothesis state in LDS
+bool beam_dims_ok(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D, int64_t V, int64_t Hl, int64_t S) {
+  return N > 0 && N <= 0x7fffffff && K >= 1 && K <= kMaxBeam && T > 0 && T <= 16384 && E > 0 && E <= 8192 &&
+         E % 4 == 0 && A > 0 && A <= 2048 && A % 4 == 0 && D > 0 && D <= 4096 && D % 16 == 0 && V > 0 && V <= 64 &&
+         Hl >= 0 && Hl <= 4096 && Hl % 4 == 0 && S > 0 && S <= (1 << 20);
+}
+}  // namespace
+
+extern "C" int64_t ssasr_decode_beam_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
+                                              int64_t V, int64_t Hl, int64_t S) {
+  if (!beam_dims_ok(N, K, T, E, A, D, V, Hl, S)) return 0;
+  return N * beam_ws_map((int)K, (int)T, (int)E, (int)A, (int)D, (int)Hl, (int)S).total * (int64_t)sizeof(float);
+}
+
+extern "C" int ssasr_decode_beam(const ssasr_beam* dp, void* stream) {
+  if (!dp) return SSASR_EARG;
+  const ssasr_beam& d = *dp;
+  BeamDev b{};
+  InferDev& p = b.in;
+  if (d.lm) {
+    if (!lm_ok(d.lm, p.lm) || d.lm->V != d.V) return SSASR_EARG;
+  }
+  if (!beam_dims_ok(d.N, d.K, d.T, d.E, d.A, d.D, d.V, p.lm.H, d.max_steps) || d.eos < 0 || d.eos >= d.V)
+    return SSASR_EARG;
+  const void* need[] = {d.feat, d.enc_len, d.comp, d.w_psi, d.b_psi, d.w_phi, d.w_ih1, d.w_hh1, d.b_ih1, d.b_hh1,
+                        d.w_ih2, d.w_hh2, d.b_ih2, d.b_hh2, d.embed, d.w_ct, d.b_ct, d.ws, d.chars, d.n_chars,
+                        d.hyp_scores, d.n_hyps};
+  for (const void* q : need)
+    if (!q) return SSASR_EARG;
+  const void* vec[] = {d.feat, d.comp, d.w_psi, d.w_phi, d.w_ih1, d.w_hh1, d.w_ih2, d.w_hh2, d.embed, d.w_ct, d.ws};
+  for (const void* q : vec)
+    if (!aligned16(q)) return SSASR_EARG;
+  if (d.ws_bytes < ssasr_decode_beam_ws_bytes(d.N, d.K, d.T, d.E, d.A, d.D, d.V, p.lm.H, d.max_steps)) return SSASR_EARG;
+  p.T = (int)d.T; p.E = (int)d.E; p.A = (int)d.A; p.D = (int)d.D; p.V = (int)d.V;
+  p.max_steps = (int)d.max_steps; p.eos = d.eos; p.lm_weight = d.lm ? d.lm_weight : 0.f;
+  p.feat = d.feat; p.enc_len = d.enc_len; p.comp = d.comp; p.w_psi = d.w_psi; p.b_psi = d.b_psi; p.w_phi = d.w_phi;
+  p.w_ih1 = d.w_ih1; p.w_hh1 = d.w_hh1; p.b_ih1 = d.b_ih1; p.b_hh1 = d.b_hh1;
+  p.w_ih2 = d.w_ih2; p.w_hh2 = d.w_hh2; p.b_ih2 = d.b_ih2; p.b_hh2 = d.b_hh2;
+  p.embed = d.embed; p.w_ct = d.w_ct; p.b_ct = d.b_ct;
+  p.chars = d.chars; p.n_chars = d.n_chars;
+  b.K = (int)d.K; b.ws = d.ws; b.hyp_scores = d.hyp_scores; b.n_hyps = d.n_hyps;
+  hipLaunchKernelGGL(decode_beam_kernel, dim3((unsigned)d.N), dim3(kThreads), 0, (hipStream_t)stream, b);
   SSASR_LAUNCH_CHECK();
   return SSASR_OK;
 }

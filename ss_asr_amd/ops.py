@@ -1017,7 +1017,7 @@ def clip_adadelta_ws(n, device):
 
 
 # ---------------------------------------------------------------------------
-# inference: CharLM step, single-launch greedy decode (csrc/infer.hip)
+# inference: CharLM step, single-launch greedy and beam-search decode (csrc/infer.hip)
 # ---------------------------------------------------------------------------
 def _charlm_struct(lm):
     """(struct ssasr_charlm, the tensors it points into) of a charlm.CharLM."""
@@ -1078,6 +1078,65 @@ def decode_greedy(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, wan
     d.att = att.data_ptr() if want_att else None
     check(lib.ssasr_decode_greedy(C.byref(d), _stream()), 'ssasr_decode_greedy')
     return chars, n_chars, scores, att
+
+
+MAX_BEAM = 32
+
+
+def beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws=None):
+    """(struct ssasr_beam, its outputs (chars, n_chars, hyp_scores, n_hyps), the tensors it points into) for
+    decode_beam's arguments; the outputs are allocated, not yet written."""
+    lib = _lib.load()
+    feat = _f32c(feat)
+    _need_gpu(feat, enc_len)
+    N, T, E = feat.shape
+    A, D = params['w_phi'].shape
+    V = params['w_ct'].shape[0]
+    K, S = int(beam_size), int(max_steps)
+    dev = feat.device
+    hl = lm.hidden_size if lm is not None else 0
+    need = int(lib.ssasr_decode_beam_ws_bytes(N, K, T, E, A, D, V, hl, S))
+    if need <= 0:
+        raise RuntimeError('ssasr_decode_beam: invalid argument (beam size %d, sizes N %d T %d E %d A %d D %d V %d '
+                           'H %d steps %d)' % (K, N, T, E, A, D, V, hl, S))
+    if ws is None:
+        ws = torch.empty(need // 4, device=dev, dtype=torch.float32)
+    _need_gpu(ws)
+    keep = {k: _f32c(v.detach()) for k, v in params.items()}
+    w_psi, b_psi = _f32c(psi[0].detach()), _f32c(psi[1].detach())
+    comp = torch.empty(N, T, A, device=dev, dtype=torch.float32)
+    chars = torch.empty(N, K, S, device=dev, dtype=torch.int32)
+    n_chars = torch.empty(N, K, device=dev, dtype=torch.int32)
+    hyp_scores = torch.empty(N, K, device=dev, dtype=torch.float32)
+    n_hyps = torch.empty(N, device=dev, dtype=torch.int32)
+    d = _lib.Beam()
+    d.N, d.T, d.E, d.A, d.D, d.V, d.max_steps, d.K = N, T, E, A, D, V, S, K
+    d.feat, d.enc_len, d.comp = feat.data_ptr(), enc_len.data_ptr(), comp.data_ptr()
+    d.w_psi, d.b_psi = w_psi.data_ptr(), b_psi.data_ptr()
+    for k, v in keep.items():
+        setattr(d, k, v.data_ptr())
+    lm_keep = None
+    if lm is not None:
+        lm_struct, lm_keep = _charlm_struct(lm)
+        lm_keep = (lm_struct, lm_keep)
+        d.lm = C.pointer(lm_struct)
+        d.lm_weight = float(lm_weight)
+    d.eos = int(eos)
+    d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    d.chars, d.n_chars, d.hyp_scores, d.n_hyps = (chars.data_ptr(), n_chars.data_ptr(), hyp_scores.data_ptr(),
+                                                  n_hyps.data_ptr())
+    return d, (chars, n_chars, hyp_scores, n_hyps), (feat, enc_len, keep, w_psi, b_psi, comp, ws, lm_keep)
+
+
+def decode_beam(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws=None):
+    """ssasr_decode_beam over feat [N, T, E] (each utterance encoded alone) and enc_len int32 [N] with
+    1 <= beam_size <= 32 hypotheses per utterance:
+    -> (chars [N, K, max_steps] int32, n_chars [N, K] int32, hyp_scores [N, K], n_hyps [N] int32), hypotheses
+    best first, unused slots zero.  params, psi, lm: as for decode_greedy.  ws: a float32 workspace of at least
+    ssasr_decode_beam_ws_bytes bytes, or None to allocate one."""
+    d, outs, keep = beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws)
+    check(_lib.load().ssasr_decode_beam(C.byref(d), _stream()), 'ssasr_decode_beam')
+    return outs
 
 
 # ---------------------------------------------------------------------------

@@ -459,8 +459,9 @@ class ASRTrainer(Solver):
 class ASRTester(Solver):
     """Inference over a test index, src/trainer.py:547-592: the same config keys (asr.test_index,
     decode_lm_weight, decode_beam_size, decode_jobs, max_decode_step_ratio, char_lm.mdl.hidden_size) and the same
-    `decode_file` name.  Like the reference (its beam search is a TODO, :590) decoding is greedy, here
-    `decode_group` utterances per launch (ASR.decode_many).  The reference constructs a CharLM and never loads
+    `decode_file` name.  asr.decode_beam_size is honoured: 1 decodes greedily, 2 .. 32 runs a beam search of that
+    width (the reference announces one and leaves it a TODO, :590), `decode_group` utterances per launch
+    (ASR.decode_many).  The reference constructs a CharLM and never loads
     it (:567-569); here <ckpdir>/char_lm.cpt is loaded when it exists."""
     decode_group = 32
 
@@ -499,13 +500,18 @@ class ASRTester(Solver):
         """-> the decoded strings, one per utterance of the test index, in index order."""
         if lm_weight is None:
             lm_weight = self.lm_weight
-        self.verbose('Start decoding (greedy; beam size in the config: {})'.format(self.decode_beam_size))
+        beam = self.decode_beam_size
+        if isinstance(beam, bool) or not isinstance(beam, int) or not 1 <= beam <= 32:
+            raise ValueError('asr.decode_beam_size must be an integer in 1..32, got {!r}'.format(beam))
+        self.verbose('Start decoding ({})'.format(
+            'beam search, beam size {}'.format(beam) if beam > 1 else 'greedy, beam size 1'))
         self.verbose('Number of utts to decode : {}, {} per launch.'.format(len(self.test_set), self.decode_group))
         results, xs, x_lens = [], [], []
 
         def flush():
             if xs:
-                results.extend(self.asr_model.decode_many(xs, x_lens, self.lm, self.mapper, lm_weight))
+                results.extend(self.asr_model.decode_many(xs, x_lens, self.lm, self.mapper, lm_weight,
+                                                          beam_size=beam))
                 del xs[:], x_lens[:]
 
         for b_ind, (x, y) in enumerate(self.test_set):

@@ -1,0 +1,80 @@
+"""Microseconds per decode step of the one-launch decoders (csrc/infer.hip) at conf/default.yaml's dimensions:
+32 utterances, T' = 100 encoder frames each, 200 steps, CharLM hidden 128, for beam size 1 (ssasr_decode_greedy)
+and 3, 8 (ssasr_decode_beam).  The encoder outputs are random and encoded once; only the decode launch is timed,
+with events around it, warm, median over --steps launches.  A step's time is the launch time over the steps the
+slowest utterance ran (n_chars + 1 for greedy, the longest hypothesis for a beam, both capped at 200).  The
+comparison that matters: K hypotheses in one workgroup against K x the greedy figure of the same run.
+
+    python tools/beam_time.py [--steps 5] [--warmup 2] [--beams 1,3,8]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b))
+    return float(np.median(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=5)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--beams', default='1,3,8')
+    ap.add_argument('--utts', type=int, default=32)
+    ap.add_argument('--frames', type=int, default=100)
+    ap.add_argument('--max-steps', type=int, default=200)
+    args = ap.parse_args()
+    from ss_asr_amd import ops
+    from ss_asr_amd.asr import ASR
+    from ss_asr_amd.charlm import CharLM
+    dev, V, S, N, T = 'cuda:0', 50, args.max_steps, args.utts, args.frames
+    torch.manual_seed(0)
+    asr = ASR(V, 256, 256, 128, 80, 1.0).to(dev).eval()
+    lm = CharLM(V, 128).to(dev).eval()
+    feat = torch.tanh(torch.randn(N, T, 512, device=dev))          # bounded, as a BiLSTM's outputs are
+    enc_len = torch.full((N,), T, device=dev, dtype=torch.int32)
+    call = (feat, enc_len, asr._decoder_params(), (asr.attention.psi.weight, asr.attention.psi.bias), lm, 0.5, 1, S)
+    res = {'shape': dict(N=N, T=T, S=S, E=512, A=128, D=256, Hl=128, V=V), 'launches': args.steps}
+    for K in [int(k) for k in args.beams.split(',')]:
+        held = {}
+        if K == 1:
+            def fn():
+                held['out'] = ops.decode_greedy(*call, want_att=False)
+        else:
+            ws = torch.empty(int(ops._lib.load().ssasr_decode_beam_ws_bytes(N, K, T, 512, 128, 256, V, 128, S)) // 4,
+                             device=dev)
+
+            def fn(K=K, ws=ws):
+                held['out'] = ops.decode_beam(*call, K, ws=ws)
+        ms = timed(fn, args.steps, args.warmup)
+        n_chars = held['out'][1].cpu().numpy()
+        ran = int(min(n_chars.max() + 1, S))
+        res['K%d' % K] = dict(launch_ms=ms, steps_run=ran, us_per_step=1e3 * ms / ran,
+                              mean_chars=float(n_chars[n_chars > 0].mean()) if (n_chars > 0).any() else 0.0)
+    if 'K1' in res:
+        for k, v in res.items():
+            if k.startswith('K') and k != 'K1':
+                v['vs_K_greedy_workgroups'] = v['us_per_step'] / (int(k[1:]) * res['K1']['us_per_step'])
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()

@@ -49,27 +49,24 @@ class CharLM(C.Structure):
         'emb', 'w_ih1', 'w_hh1', 'b_ih1', 'b_hh1', 'w_ih2', 'w_hh2', 'b_ih2', 'b_hh2', 'w_out', 'b_out')]
 
 
+# what struct ssasr_infer and struct ssasr_beam share, around the beam's K and between each one's own tail
+_DECODE_DIMS = ('N', 'T', 'E', 'A', 'D', 'V', 'max_steps')
+_DECODE_COMMON = ([(n, P) for n in ('feat', 'enc_len', 'comp', 'w_psi', 'b_psi', 'w_phi',
+                                    'w_ih1', 'w_hh1', 'b_ih1', 'b_hh1', 'w_ih2', 'w_hh2', 'b_ih2', 'b_hh2',
+                                    'embed', 'w_ct', 'b_ct')] +
+                  [('lm', C.POINTER(CharLM)), ('lm_weight', F32), ('eos', C.c_int32)])
+
+
 class Infer(C.Structure):
     """struct ssasr_infer (include/ssasr.h)."""
-    _fields_ = (
-        [(n, I64) for n in ('N', 'T', 'E', 'A', 'D', 'V', 'max_steps')] +
-        [(n, P) for n in ('feat', 'enc_len', 'comp', 'w_psi', 'b_psi', 'w_phi',
-                          'w_ih1', 'w_hh1', 'b_ih1', 'b_hh1', 'w_ih2', 'w_hh2', 'b_ih2', 'b_hh2',
-                          'embed', 'w_ct', 'b_ct')] +
-        [('lm', C.POINTER(CharLM)), ('lm_weight', F32), ('eos', C.c_int32)] +
-        [(n, P) for n in ('chars', 'n_chars', 'scores', 'att')])
+    _fields_ = ([(n, I64) for n in _DECODE_DIMS] + _DECODE_COMMON +
+                [(n, P) for n in ('chars', 'n_chars', 'scores', 'att')])
 
 
 class Beam(C.Structure):
     """struct ssasr_beam (include/ssasr.h)."""
-    _fields_ = (
-        [(n, I64) for n in ('N', 'T', 'E', 'A', 'D', 'V', 'max_steps', 'K')] +
-        [(n, P) for n in ('feat', 'enc_len', 'comp', 'w_psi', 'b_psi', 'w_phi',
-                          'w_ih1', 'w_hh1', 'b_ih1', 'b_hh1', 'w_ih2', 'w_hh2', 'b_ih2', 'b_hh2',
-                          'embed', 'w_ct', 'b_ct')] +
-        [('lm', C.POINTER(CharLM)), ('lm_weight', F32), ('eos', C.c_int32)] +
-        [('ws', P), ('ws_bytes', I64)] +
-        [(n, P) for n in ('chars', 'n_chars', 'hyp_scores', 'n_hyps')])
+    _fields_ = ([(n, I64) for n in _DECODE_DIMS + ('K',)] + _DECODE_COMMON + [('ws', P), ('ws_bytes', I64)] +
+                [(n, P) for n in ('chars', 'n_chars', 'hyp_scores', 'n_hyps')])
 
 
 SIGNATURES = {

@@ -12,6 +12,13 @@
 // on the DPP network (common.h, wave_sum).  What a workgroup computes for its utterance depends
 // on that utterance's frames and enc_len alone, never on N or the padded T': an utterance decoded
 // in a batch gives the bits it gives alone.
+//
+// The three kernels are built from one set of step helpers, each over n hypotheses whose rows lie a stride apart
+// (the greedy kernel and the CharLM step pass n = 1): matmat_n / matvec / matmat (weight rows x input vectors, comp =
+// tanh(psi(feat)) included), lstm_update, gru_update, context_partial + context_reduce (att . feat) and score_row
+// (log_softmax(asr) + lm_weight * log_softmax(lm)).  Per kernel: where the state lives, the softmax over the frames
+// (block-wide / a wave per hypothesis: different summation orders) and what follows the score row (the arg-max /
+// the beam's selection, back-pointers and output).
 #include <cmath>
 #include "../../include/ssasr.h"
 #include "common.h"
@@ -21,6 +28,7 @@ namespace {
 constexpr int kThreads = 512;
 constexpr int kWaves = kThreads / 64;
 constexpr int kRows = 4;                 // rows of a matrix-vector product a wave has in flight
+constexpr int kHyps = 8;                 // input vectors one pass of matmat holds against a weight row group
 constexpr size_t kMaxLds = 160 * 1024;   // LDS of one CU
 
 __device__ __forceinline__ float dot4(const float4& a, const float4& b, float acc) {
@@ -31,49 +39,98 @@ __device__ __forceinline__ float dot4(const float4& a, const float4& b, float ac
 }
 __device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// out[r] = act(w1[r][0..k1) . x1 + w2[r][0..k2) . x2 + b1[r] + b2[r]) for r < rows; x1 / x2 in LDS,
-// 16-byte aligned, k1 / k2 multiples of 4 (k2 = 0: one segment); b1 / b2 optional.  act 1 = tanh.
-// Called by every wave of the workgroup; rows are dealt to waves in groups of kRows.
-__device__ void matvec(const float* w1, int64_t ld1, const float* x1, int k1,
-                       const float* w2, int64_t ld2, const float* x2, int k2,
-                       const float* __restrict__ b1, const float* __restrict__ b2, int rows, int act, float* out) {
+// out[b * os + r] = act(w1[r][0..k1) . x1[b * xs1 ..] + w2[r][0..k2) . x2[b * xs2 ..] + b1[r] + b2[r]) for r < rows,
+// b < nb <= NB; rows and vectors 16-byte aligned, k1 / k2 multiples of 4 (k2 = 0: one segment); b1 / b2 optional;
+// act 1 = tanh.  Called by every wave of the workgroup; rows are dealt to waves in groups of kRows.
+template <int NB>
+__device__ void matmat_n(const float* w1, int64_t ld1, const float* x1, int64_t xs1, int k1,
+                         const float* w2, int64_t ld2, const float* x2, int64_t xs2, int k2,
+                         const float* __restrict__ b1, const float* __restrict__ b2, int rows, int act,
+                         float* out, int64_t os, int nb) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int r0 = wave * kRows; r0 < rows; r0 += kWaves * kRows) {
-    float acc[kRows];
+    float acc[kRows][NB];
     const float* p1[kRows];
     const float* p2[kRows];
 #pragma unroll
     for (int j = 0; j < kRows; ++j) {
       const int r = min(r0 + j, rows - 1);          // rows past the end repeat the last one and are dropped
-      acc[j] = 0.f;
+#pragma unroll
+      for (int b = 0; b < NB; ++b) acc[j][b] = 0.f;
       p1[j] = w1 + (int64_t)r * ld1;
       p2[j] = k2 ? w2 + (int64_t)r * ld2 : nullptr;
     }
     for (int k = lane * 4; k < k1; k += 256) {
-      const float4 x = *reinterpret_cast<const float4*>(x1 + k);
+      float4 w[kRows];
 #pragma unroll
-      for (int j = 0; j < kRows; ++j) acc[j] = dot4(*reinterpret_cast<const float4*>(p1[j] + k), x, acc[j]);
+      for (int j = 0; j < kRows; ++j) w[j] = *reinterpret_cast<const float4*>(p1[j] + k);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {                // vectors past nb repeat the last one and are dropped
+        const float4 x = *reinterpret_cast<const float4*>(x1 + (int64_t)min(b, nb - 1) * xs1 + k);
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) acc[j][b] = dot4(w[j], x, acc[j][b]);
+      }
     }
     for (int k = lane * 4; k < k2; k += 256) {
-      const float4 x = *reinterpret_cast<const float4*>(x2 + k);
+      float4 w[kRows];
 #pragma unroll
-      for (int j = 0; j < kRows; ++j) acc[j] = dot4(*reinterpret_cast<const float4*>(p2[j] + k), x, acc[j]);
+      for (int j = 0; j < kRows; ++j) w[j] = *reinterpret_cast<const float4*>(p2[j] + k);
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        const float4 x = *reinterpret_cast<const float4*>(x2 + (int64_t)min(b, nb - 1) * xs2 + k);
+#pragma unroll
+        for (int j = 0; j < kRows; ++j) acc[j][b] = dot4(w[j], x, acc[j][b]);
+      }
     }
+    float v = 0.f;                                  // lane j * NB + b keeps the sum of row j, vector b
 #pragma unroll
-    for (int j = 0; j < kRows; ++j) acc[j] = wave_sum(acc[j]);
-    if (lane < kRows && r0 + lane < rows) {
-      const int r = r0 + lane;
-      float v = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
+    for (int j = 0; j < kRows; ++j)
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        const float s = wave_sum(acc[j][b]);
+        if (lane == j * NB + b) v = s;
+      }
+    const int j = lane / NB, b = lane % NB;
+    if (lane < kRows * NB && r0 + j < rows && b < nb) {
+      const int r = r0 + j;
       if (b1) v += b1[r];
       if (b2) v += b2[r];
-      out[r] = act == 1 ? tanhf(v) : v;
+      out[(int64_t)b * os + r] = act == 1 ? tanhf(v) : v;
     }
   }
 }
 
-// nn.LSTMCell's update from the pre-activations g [4H] (order i, f, g, o; src/asr.py:320-324)
-__device__ void lstm_update(const float* g, float* h, float* c, int H) {
-  for (int u = threadIdx.x; u < H; u += kThreads) {
+// matmat_n over n vectors, kHyps at a time; the last pass takes the narrowest form that holds what is left
+__device__ void matmat(const float* w1, int64_t ld1, const float* x1, int64_t xs1, int k1,
+                       const float* w2, int64_t ld2, const float* x2, int64_t xs2, int k2,
+                       const float* __restrict__ b1, const float* __restrict__ b2, int rows, int act,
+                       float* out, int64_t os, int n) {
+  for (int b0 = 0; b0 < n; b0 += kHyps) {
+    const int nb = min(kHyps, n - b0);
+    const float* y1 = x1 + (int64_t)b0 * xs1;
+    const float* y2 = k2 ? x2 + (int64_t)b0 * xs2 : nullptr;
+    float* o = out + (int64_t)b0 * os;
+    if (nb == 1) matmat_n<1>(w1, ld1, y1, xs1, k1, w2, ld2, y2, xs2, k2, b1, b2, rows, act, o, os, nb);
+    else if (nb == 2) matmat_n<2>(w1, ld1, y1, xs1, k1, w2, ld2, y2, xs2, k2, b1, b2, rows, act, o, os, nb);
+    else if (nb <= 4) matmat_n<4>(w1, ld1, y1, xs1, k1, w2, ld2, y2, xs2, k2, b1, b2, rows, act, o, os, nb);
+    else matmat_n<kHyps>(w1, ld1, y1, xs1, k1, w2, ld2, y2, xs2, k2, b1, b2, rows, act, o, os, nb);
+  }
+}
+
+// one vector: the matrix-vector products of decode_greedy_kernel and charlm_step_kernel
+__device__ void matvec(const float* w1, int64_t ld1, const float* x1, int k1,
+                       const float* w2, int64_t ld2, const float* x2, int k2,
+                       const float* __restrict__ b1, const float* __restrict__ b2, int rows, int act, float* out) {
+  matmat_n<1>(w1, ld1, x1, 0, k1, w2, ld2, x2, 0, k2, b1, b2, rows, act, out, 0, 1);
+}
+
+// nn.LSTMCell's update of n hypotheses from their pre-activations [4H] (order i, f, g, o; src/asr.py:320-324);
+// gs / ss: floats from one hypothesis' gate row / state rows to the next one's
+__device__ void lstm_update(const float* gates, int64_t gs, float* h0, float* c0, int64_t ss, int H, int n) {
+  for (int e = threadIdx.x; e < n * H; e += kThreads) {
+    const int b = e / H, u = e % H;
+    const float* g = gates + b * gs;
+    float *h = h0 + b * ss, *c = c0 + b * ss;
     const float i = sigmoid_exact(g[u]), f = sigmoid_exact(g[H + u]), gg = tanhf(g[2 * H + u]),
                 o = sigmoid_exact(g[3 * H + u]);
     const float cn = f * c[u] + i * gg;
@@ -82,13 +139,80 @@ __device__ void lstm_update(const float* g, float* h, float* c, int H) {
   }
 }
 
-// nn.GRUCell's update from gi = W_ih x + b_ih and gh = W_hh h + b_hh [3H] (order r, z, n)
-__device__ void gru_update(const float* gi, const float* gh, float* h, int H) {
-  for (int u = threadIdx.x; u < H; u += kThreads) {
+// nn.GRUCell's update of n hypotheses from gi = W_ih x + b_ih and gh = W_hh h + b_hh [3H] (order r, z, n);
+// gs / hs: floats from one hypothesis' gi and gh rows / state row to the next one's
+__device__ void gru_update(const float* gi0, const float* gh0, int64_t gs, float* h0, int64_t hs, int H, int n) {
+  for (int e = threadIdx.x; e < n * H; e += kThreads) {
+    const int b = e / H, u = e % H;
+    const float *gi = gi0 + b * gs, *gh = gh0 + b * gs;
+    float* h = h0 + b * hs;
     const float r = sigmoid_exact(gi[u] + gh[u]), z = sigmoid_exact(gi[H + u] + gh[H + u]);
     const float n = tanhf(gi[2 * H + u] + r * gh[2 * H + u]);
     h[u] = (1.f - z) * n + z * h[u];
   }
+}
+
+// frame groups of the context sum: kThreads threads over the E / 4 float4 columns
+__host__ __device__ inline int context_groups(int E) { return E / 4 >= kThreads ? 1 : kThreads / (E / 4); }
+
+// context = att . feat (src/asr.py:389-390) of n hypotheses whose attention rows lie `as` floats apart: a thread
+// sums one float4 column over the frames g, g + G, ... of its group for NH hypotheses at a time, so feat is read
+// once per NH of them.  Group g's sums of hypothesis b go to dst + g * gs + b * ds: with G == 1 that is the context
+// itself, otherwise the partial sums that context_reduce adds up.
+template <int NH>
+__device__ void context_partial(const float* feat, int E, int len, int G, const float* att0, int64_t as, int n,
+                                float* dst, int64_t gs, int64_t ds) {
+  const int tid = threadIdx.x, ncol4 = E / 4;
+  for (int b0 = 0; b0 < n; b0 += NH) {
+    const int nb = min(NH, n - b0);
+    const float* att = att0 + b0 * as;
+    const int g = G == 1 ? 0 : tid / ncol4;
+    for (int c = G == 1 ? tid : tid % ncol4; c < ncol4 && g < G; c += kThreads) {
+      float4 s[NH];
+#pragma unroll
+      for (int j = 0; j < NH; ++j) s[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int t = g; t < len; t += G) {
+        const float4 v = *reinterpret_cast<const float4*>(feat + (int64_t)t * E + c * 4);
+#pragma unroll
+        for (int j = 0; j < NH; ++j)
+          if (j < nb) {
+            const float a = att[j * as + t];
+            s[j].x = fmaf(a, v.x, s[j].x); s[j].y = fmaf(a, v.y, s[j].y);
+            s[j].z = fmaf(a, v.z, s[j].z); s[j].w = fmaf(a, v.w, s[j].w);
+          }
+      }
+#pragma unroll
+      for (int j = 0; j < NH; ++j)
+        if (j < nb) *reinterpret_cast<float4*>(dst + g * gs + (b0 + j) * ds + c * 4) = s[j];
+    }
+  }
+}
+
+// ctx[b * cs + e] = part[b * ps + e] + part[gs + b * ps + e] + ... over the G groups, in that order; b < n, e < E
+__device__ void context_reduce(const float* part, int64_t gs, int64_t ps, int G, float* ctx, int64_t cs, int E, int n) {
+  for (int i = threadIdx.x; i < n * E; i += kThreads) {
+    const int b = i / E, e = i % E;
+    float s = part[b * ps + e];
+    for (int g = 1; g < G; ++g) s += part[g * gs + b * ps + e];
+    ctx[b * cs + e] = s;
+  }
+}
+
+// This lane's log_softmax(asr)[lane] + lm_weight * log_softmax(lm)[lane] (src/asr.py:153-157) from the logit rows
+// lg and lmlg (nullptr: no language model).  Called by a whole wave (V <= 64); what a lane >= V gets is no score.
+__device__ float score_row(const float* lg, const float* lmlg, int V, float lm_weight) {
+  const int lane = threadIdx.x & 63;
+  const float x = lane < V ? lg[lane] : -INFINITY;
+  const float xm = wave_max(x);
+  const float xs = wave_sum(lane < V ? expf(x - xm) : 0.f);
+  float fin = x - xm - logf(xs);
+  if (lmlg) {
+    const float y = lane < V ? lmlg[lane] : -INFINITY;
+    const float ym = wave_max(y);
+    const float ys = wave_sum(lane < V ? expf(y - ym) : 0.f);
+    fin = fin + lm_weight * (y - ym - logf(ys));
+  }
+  return fin;
 }
 
 __device__ void copy_row(float* dst, const float* __restrict__ src, int n) {
@@ -183,32 +307,11 @@ __global__ __launch_bounds__(kThreads) void decode_greedy_kernel(InferDev p) {
   float* scores = p.scores + (int64_t)n * p.max_steps * V;
   float* att = p.att ? p.att + (int64_t)n * p.max_steps * T : nullptr;
 
-  // comp = tanh(psi(feat)) for this utterance's frames, once (src/asr.py:381): a wave takes a row of
-  // W_psi against four frames at a time
-  for (int a = wave; a < A; a += kWaves) {
-    const float* wrow = p.w_psi + (int64_t)a * E;
-    const float bias = p.b_psi[a];
-    for (int t0 = 0; t0 < len; t0 += kRows) {
-      float acc[kRows];
-      const float* f[kRows];
-#pragma unroll
-      for (int j = 0; j < kRows; ++j) {
-        acc[j] = 0.f;
-        f[j] = feat + (int64_t)min(t0 + j, len - 1) * E;
-      }
-      for (int k = lane * 4; k < E; k += 256) {
-        const float4 w = *reinterpret_cast<const float4*>(wrow + k);
-#pragma unroll
-        for (int j = 0; j < kRows; ++j) acc[j] = dot4(*reinterpret_cast<const float4*>(f[j] + k), w, acc[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < kRows; ++j) acc[j] = wave_sum(acc[j]);
-      if (lane < kRows && t0 + lane < len) {
-        const float v = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : acc[3];
-        comp[(int64_t)(t0 + lane) * A + a] = tanhf(v + bias);
-      }
-    }
-  }
+  // comp = tanh(psi(feat)) for this utterance's frames, once (src/asr.py:381): W_psi against the frames as vectors,
+  // kRows of them a pass (matmat's kHyps accumulator sets would cost this kernel scratch memory)
+  for (int t0 = 0; t0 < len; t0 += kRows)
+    matmat_n<kRows>(p.w_psi, E, feat + (int64_t)t0 * E, E, E, nullptr, 0, nullptr, 0, 0, p.b_psi, nullptr, A, 1,
+                    comp + (int64_t)t0 * A, A, min(kRows, len - t0));
   // zero states (src/asr.py:133-134), <SOS> = 0 as the first input character (:137-138)
   for (int i = tid; i < 4 * D; i += kThreads) lds[m.h1 + i] = 0.f;
   for (int i = tid; i < 2 * Hl; i += kThreads) lmh1[i] = 0.f;       // lmh1 and lmh2 are adjacent
@@ -216,8 +319,7 @@ __global__ __launch_bounds__(kThreads) void decode_greedy_kernel(InferDev p) {
   if (Hl) copy_row(lmx, p.lm.emb, Hl);
   __syncthreads();
 
-  const int ncol4 = E / 4;
-  const int G = ncol4 >= kThreads ? 1 : kThreads / ncol4;          // frame groups of the context sum
+  const int G = context_groups(E);
   int step = 0, emitted = p.max_steps;
   for (; step < p.max_steps; ++step) {
     // 1: q = tanh(phi(h1)) (src/asr.py:383) | LM layer 1 products (src/charlm.py:54)
@@ -228,10 +330,12 @@ __global__ __launch_bounds__(kThreads) void decode_greedy_kernel(InferDev p) {
     }
     __syncthreads();
     // 2: energies over the utterance's frames (src/asr.py:385-387) | LM layer 1 update
-    if (Hl) gru_update(gi, gh, lmh1, Hl);
+    if (Hl) gru_update(gi, gh, 0, lmh1, 0, Hl, 1);
     matvec(comp, A, q, A, nullptr, 0, nullptr, 0, nullptr, nullptr, len, 0, en);
     __syncthreads();
-    // 3: softmax over the frames (src/asr.py:388) | LM layer 2 products (src/charlm.py:55)
+    // 3: softmax over the frames (src/asr.py:388) | LM layer 2 products (src/charlm.py:55).  Block-wide here, a wave
+    // per hypothesis in decode_beam_kernel: the two sum in different orders, so one form for both would change the
+    // bits and the time of one of them
     float mx = -INFINITY;
     for (int t = tid; t < len; t += kThreads) mx = fmaxf(mx, en[t]);
     mx = block_max(mx, red);
@@ -252,65 +356,31 @@ __global__ __launch_bounds__(kThreads) void decode_greedy_kernel(InferDev p) {
       matvec(p.lm.w_hh2, Hl, lmh2, Hl, nullptr, 0, nullptr, 0, p.lm.b_hh2, nullptr, 3 * Hl, 0, gh);
     }
     __syncthreads();
-    // 4: context = att . feat (src/asr.py:389-390): a thread sums one float4 column over its group's frames
-    if (G == 1) {
-      for (int c = tid; c < ncol4; c += kThreads) {
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int t = 0; t < len; ++t) {
-          const float4 v = *reinterpret_cast<const float4*>(feat + (int64_t)t * E + c * 4);
-          const float a = en[t];
-          s.x = fmaf(a, v.x, s.x); s.y = fmaf(a, v.y, s.y); s.z = fmaf(a, v.z, s.z); s.w = fmaf(a, v.w, s.w);
-        }
-        *reinterpret_cast<float4*>(xin + D + c * 4) = s;
-      }
-    } else {
-      const int c = tid % ncol4, g = tid / ncol4;
-      if (g < G) {
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int t = g; t < len; t += G) {
-          const float4 v = *reinterpret_cast<const float4*>(feat + (int64_t)t * E + c * 4);
-          const float a = en[t];
-          s.x = fmaf(a, v.x, s.x); s.y = fmaf(a, v.y, s.y); s.z = fmaf(a, v.z, s.z); s.w = fmaf(a, v.w, s.w);
-        }
-        *reinterpret_cast<float4*>(part + (g * ncol4 + c) * 4) = s;
-      }
-    }
-    if (Hl) gru_update(gi, gh, lmh2, Hl);
+    // 4: context = att . feat (src/asr.py:389-390), partial sums in LDS at [g][E] | LM layer 2 update
+    context_partial<1>(feat, E, len, G, en, 0, 1, G == 1 ? xin + D : part, E, 0);
+    if (Hl) gru_update(gi, gh, 0, lmh2, 0, Hl, 1);
     __syncthreads();
     if (G > 1) {
-      for (int e = tid; e < E; e += kThreads) {
-        float s = part[e];
-        for (int g = 1; g < G; ++g) s += part[g * E + e];
-        xin[D + e] = s;
-      }
+      context_reduce(part, E, 0, G, xin + D, 0, E, 1);
       __syncthreads();
     }
     // 5: Speller cell 1 on [embedding | context] (src/asr.py:149-150, :320-321) | LM output layer (src/charlm.py:56)
     matvec(p.w_ih1, D + E, xin, D + E, p.w_hh1, D, h1, D, p.b_ih1, p.b_hh1, 4 * D, 0, gates);
     if (Hl) matvec(p.lm.w_out, Hl, lmh2, Hl, nullptr, 0, nullptr, 0, p.lm.b_out, nullptr, V, 0, lmlg);
     __syncthreads();
-    lstm_update(gates, h1, c1, D);
+    lstm_update(gates, 0, h1, c1, 0, D, 1);
     __syncthreads();
     // 6: cell 2 (src/asr.py:323-324)
     matvec(p.w_ih2, D, h1, D, p.w_hh2, D, h2, D, p.b_ih2, p.b_hh2, 4 * D, 0, gates);
     __syncthreads();
-    lstm_update(gates, h2, c2, D);
+    lstm_update(gates, 0, h2, c2, 0, D, 1);
     __syncthreads();
     // 7: char_trans (src/asr.py:153)
     matvec(p.w_ct, D, h2, D, nullptr, 0, nullptr, 0, p.b_ct, nullptr, V, 0, lg);
     __syncthreads();
     // 8: final = log_softmax(asr) + lm_weight * log_softmax(lm), first maximum wins (src/asr.py:153-159)
     if (wave == 0) {
-      const float x = lane < V ? lg[lane] : -INFINITY;
-      const float xm = wave_max(x);
-      const float xs = wave_sum(lane < V ? expf(x - xm) : 0.f);
-      float fin = x - xm - logf(xs);
-      if (Hl) {
-        const float y = lane < V ? lmlg[lane] : -INFINITY;
-        const float ym = wave_max(y);
-        const float ys = wave_sum(lane < V ? expf(y - ym) : 0.f);
-        fin = fin + p.lm_weight * (y - ym - logf(ys));
-      }
+      float fin = score_row(lg, Hl ? lmlg : nullptr, V, p.lm_weight);
       if (lane >= V) fin = -INFINITY;
       const float best = wave_max(fin);
       unsigned long long hit = __ballot(lane < V && fin == best);
@@ -362,90 +432,12 @@ __global__ __launch_bounds__(kThreads) void decode_greedy_kernel(InferDev p) {
 // block-wide arg-max, ties to the lower flat index b * 64 + v (the order of b * V + v); a chosen candidate is
 // struck out with a NaN, which no score can be (NaN rows are scored -inf).
 // An utterance's results depend on its frames, enc_len, K and max_steps alone, never on N or the padded T.
-constexpr int kHyps = 8;                  // input vectors one pass of matmat holds against a weight row group
 constexpr int kMaxBeam = 32;
 constexpr int kNone = 1 << 30;
 
 __device__ __forceinline__ void phase_sync() {
   __threadfence_block();
   __syncthreads();
-}
-
-// out[b * os + r] = act(w1[r] . x1[b * xs1 ..] + w2[r] . x2[b * xs2 ..] + b1[r] + b2[r]) for r < rows, b < nb <= NB;
-// the contract of matvec otherwise (k1 / k2 multiples of 4, 16-byte aligned rows and vectors, k2 = 0: one segment).
-template <int NB>
-__device__ void matmat_n(const float* w1, int64_t ld1, const float* x1, int64_t xs1, int k1,
-                         const float* w2, int64_t ld2, const float* x2, int64_t xs2, int k2,
-                         const float* __restrict__ b1, const float* __restrict__ b2, int rows, int act,
-                         float* out, int64_t os, int nb) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int r0 = wave * kRows; r0 < rows; r0 += kWaves * kRows) {
-    float acc[kRows][NB];
-    const float* p1[kRows];
-    const float* p2[kRows];
-#pragma unroll
-    for (int j = 0; j < kRows; ++j) {
-      const int r = min(r0 + j, rows - 1);          // rows past the end repeat the last one and are dropped
-#pragma unroll
-      for (int b = 0; b < NB; ++b) acc[j][b] = 0.f;
-      p1[j] = w1 + (int64_t)r * ld1;
-      p2[j] = k2 ? w2 + (int64_t)r * ld2 : nullptr;
-    }
-    for (int k = lane * 4; k < k1; k += 256) {
-      float4 w[kRows];
-#pragma unroll
-      for (int j = 0; j < kRows; ++j) w[j] = *reinterpret_cast<const float4*>(p1[j] + k);
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {                // vectors past nb repeat the last one and are dropped
-        const float4 x = *reinterpret_cast<const float4*>(x1 + (int64_t)min(b, nb - 1) * xs1 + k);
-#pragma unroll
-        for (int j = 0; j < kRows; ++j) acc[j][b] = dot4(w[j], x, acc[j][b]);
-      }
-    }
-    for (int k = lane * 4; k < k2; k += 256) {
-      float4 w[kRows];
-#pragma unroll
-      for (int j = 0; j < kRows; ++j) w[j] = *reinterpret_cast<const float4*>(p2[j] + k);
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        const float4 x = *reinterpret_cast<const float4*>(x2 + (int64_t)min(b, nb - 1) * xs2 + k);
-#pragma unroll
-        for (int j = 0; j < kRows; ++j) acc[j][b] = dot4(w[j], x, acc[j][b]);
-      }
-    }
-    float v = 0.f;                                  // lane j * NB + b keeps the sum of row j, vector b
-#pragma unroll
-    for (int j = 0; j < kRows; ++j)
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        const float s = wave_sum(acc[j][b]);
-        if (lane == j * NB + b) v = s;
-      }
-    const int j = lane / NB, b = lane % NB;
-    if (lane < kRows * NB && r0 + j < rows && b < nb) {
-      const int r = r0 + j;
-      if (b1) v += b1[r];
-      if (b2) v += b2[r];
-      out[(int64_t)b * os + r] = act == 1 ? tanhf(v) : v;
-    }
-  }
-}
-
-// matmat_n over n vectors, kHyps at a time; the last pass takes the narrowest form that holds what is left
-__device__ void matmat(const float* w1, int64_t ld1, const float* x1, int64_t xs1, int k1,
-                       const float* w2, int64_t ld2, const float* x2, int64_t xs2, int k2,
-                       const float* __restrict__ b1, const float* __restrict__ b2, int rows, int act,
-                       float* out, int64_t os, int n) {
-  for (int b0 = 0; b0 < n; b0 += kHyps) {
-    const int nb = min(kHyps, n - b0);
-    const float* y1 = x1 + (int64_t)b0 * xs1;
-    const float* y2 = k2 ? x2 + (int64_t)b0 * xs2 : nullptr;
-    float* o = out + (int64_t)b0 * os;
-    if (nb == 1) matmat_n<1>(w1, ld1, y1, xs1, k1, w2, ld2, y2, xs2, k2, b1, b2, rows, act, o, os, nb);
-    else if (nb == 2) matmat_n<2>(w1, ld1, y1, xs1, k1, w2, ld2, y2, xs2, k2, b1, b2, rows, act, o, os, nb);
-    else if (nb <= 4) matmat_n<4>(w1, ld1, y1, xs1, k1, w2, ld2, y2, xs2, k2, b1, b2, rows, act, o, os, nb);
-    else matmat_n<kHyps>(w1, ld1, y1, xs1, k1, w2, ld2, y2, xs2, k2, b1, b2, rows, act, o, os, nb);
-  }
 }
 
 // workspace slice of one utterance (floats; every block starts on 16 bytes)
@@ -456,10 +448,9 @@ struct BeamWs {
 __host__ __device__ inline int64_t up4l(int64_t v) { return (v + 3) & ~(int64_t)3; }
 __host__ __device__ inline BeamWs beam_ws_map(int K, int T, int E, int A, int D, int Hl, int S) {
   BeamWs m;
-  const int ncol4 = E / 4;
   m.Sz = 4 * D + 2 * Hl;                  // h1 | c1 | h2 | c2 | LM h1 | LM h2 of one hypothesis
   m.Tp = up4(T);
-  m.G = ncol4 >= kThreads ? 1 : kThreads / ncol4;      // frame groups of the context sum
+  m.G = context_groups(E);
   int64_t o = 0;
   m.st = o; o += 2 * (int64_t)K * m.Sz;   // two buffers of K rows
   m.xin = o; o += (int64_t)K * (D + E);   // [embedding of the last character | context]
@@ -505,7 +496,7 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd) {
   float *xin = ws + m.xin, *lmx = ws + m.lmx, *q = ws + m.q, *gates = ws + m.gates, *en = ws + m.en,
         *part = ws + m.part, *gi = ws + m.gi, *gh = ws + m.gh, *lg = ws + m.lg, *lmlg = ws + m.lmlg;
   int32_t* bp = reinterpret_cast<int32_t*>(ws + m.bp);
-  const int Sz = m.Sz, Tp = m.Tp, G = m.G, XI = D + E, ncol4 = E / 4;
+  const int Sz = m.Sz, Tp = m.Tp, G = m.G, XI = D + E;
 
   const int len = min(max(p.enc_len[n], 1), T);      // frames this utterance attends over
   const float* feat = p.feat + (int64_t)n * T * E;
@@ -539,17 +530,11 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd) {
     }
     phase_sync();
     // 2: energies over the utterance's frames | LM layer 1 update
-    for (int i = tid; i < live * Hl; i += kThreads) {
-      const int b = i / Hl, u = i % Hl;
-      const float *a = gi + (int64_t)b * 3 * Hl, *c = gh + (int64_t)b * 3 * Hl;
-      float* h = lmh1 + (int64_t)b * Sz;
-      const float r = sigmoid_exact(a[u] + c[u]), z = sigmoid_exact(a[Hl + u] + c[Hl + u]);
-      const float nn = tanhf(a[2 * Hl + u] + r * c[2 * Hl + u]);
-      h[u] = (1.f - z) * nn + z * h[u];
-    }
+    gru_update(gi, gh, 3 * Hl, lmh1, Sz, Hl, live);
     matmat(comp, A, q, A, A, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, len, 0, en, Tp, live);
     phase_sync();
-    // 3: softmax over the frames, a wave per hypothesis | LM layer 2 products
+    // 3: softmax over the frames, a wave per hypothesis (decode_greedy_kernel's is block-wide and sums in another
+    // order: the two stay apart) | LM layer 2 products
     for (int b = wave; b < live; b += kWaves) {
       float* row = en + (int64_t)b * Tp;
       float mx = -INFINITY;
@@ -569,80 +554,31 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd) {
       matmat(p.lm.w_hh2, Hl, lmh2, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_hh2, nullptr, 3 * Hl, 0, gh, 3 * Hl, live);
     }
     phase_sync();
-    // 4: context = att . feat: a thread sums one float4 column over its group's frames for kHyps hypotheses, so
-    // feat is read once per kHyps of them | LM layer 2 update
-    for (int b0 = 0; b0 < live; b0 += kHyps) {
-      const int nb = min(kHyps, live - b0);
-      const float* att = en + (int64_t)b0 * Tp;
-      const int g = G == 1 ? 0 : tid / ncol4;
-      for (int c = G == 1 ? tid : tid % ncol4; c < ncol4 && g < G; c += kThreads) {
-        float4 s[kHyps];
-#pragma unroll
-        for (int j = 0; j < kHyps; ++j) s[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int t = g; t < len; t += G) {
-          const float4 v = *reinterpret_cast<const float4*>(feat + (int64_t)t * E + c * 4);
-#pragma unroll
-          for (int j = 0; j < kHyps; ++j)
-            if (j < nb) {
-              const float a = att[(int64_t)j * Tp + t];
-              s[j].x = fmaf(a, v.x, s[j].x); s[j].y = fmaf(a, v.y, s[j].y);
-              s[j].z = fmaf(a, v.z, s[j].z); s[j].w = fmaf(a, v.w, s[j].w);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < kHyps; ++j)
-          if (j < nb) {
-            float* dst = G == 1 ? xin + (int64_t)(b0 + j) * XI + D + c * 4
-                                : part + ((int64_t)g * K + b0 + j) * E + c * 4;
-            *reinterpret_cast<float4*>(dst) = s[j];
-          }
-      }
-    }
-    for (int i = tid; i < live * Hl; i += kThreads) {
-      const int b = i / Hl, u = i % Hl;
-      const float *a = gi + (int64_t)b * 3 * Hl, *c = gh + (int64_t)b * 3 * Hl;
-      float* h = lmh2 + (int64_t)b * Sz;
-      const float r = sigmoid_exact(a[u] + c[u]), z = sigmoid_exact(a[Hl + u] + c[Hl + u]);
-      const float nn = tanhf(a[2 * Hl + u] + r * c[2 * Hl + u]);
-      h[u] = (1.f - z) * nn + z * h[u];
-    }
+    // 4: context = att . feat, partial sums in the workspace at [g][K][E] | LM layer 2 update
+    context_partial<kHyps>(feat, E, len, G, en, Tp, live, G == 1 ? xin + D : part, (int64_t)K * E, G == 1 ? XI : E);
+    gru_update(gi, gh, 3 * Hl, lmh2, Sz, Hl, live);
     phase_sync();
     if (G > 1) {
-      for (int i = tid; i < live * E; i += kThreads) {
-        const int b = i / E, e = i % E;
-        float s = part[(int64_t)b * E + e];
-        for (int g = 1; g < G; ++g) s += part[((int64_t)g * K + b) * E + e];
-        xin[(int64_t)b * XI + D + e] = s;
-      }
+      context_reduce(part, (int64_t)K * E, E, G, xin + D, XI, E, live);
       phase_sync();
     }
     // 5: Speller cell 1 on [embedding | context] | LM output layer
     matmat(p.w_ih1, XI, xin, XI, XI, p.w_hh1, D, h1, Sz, D, p.b_ih1, p.b_hh1, 4 * D, 0, gates, 4 * D, live);
     if (Hl) matmat(p.lm.w_out, Hl, lmh2, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_out, nullptr, V, 0, lmlg, 64, live);
     phase_sync();
-    for (int b = 0; b < live; ++b) lstm_update(gates + (int64_t)b * 4 * D, h1 + (int64_t)b * Sz, c1 + (int64_t)b * Sz, D);
+    lstm_update(gates, 4 * D, h1, c1, Sz, D, live);
     phase_sync();
     // 6: cell 2
     matmat(p.w_ih2, D, h1, Sz, D, p.w_hh2, D, h2, Sz, D, p.b_ih2, p.b_hh2, 4 * D, 0, gates, 4 * D, live);
     phase_sync();
-    for (int b = 0; b < live; ++b) lstm_update(gates + (int64_t)b * 4 * D, h2 + (int64_t)b * Sz, c2 + (int64_t)b * Sz, D);
+    lstm_update(gates, 4 * D, h2, c2, Sz, D, live);
     phase_sync();
     // 7: char_trans
     matmat(p.w_ct, D, h2, Sz, D, nullptr, 0, nullptr, 0, 0, p.b_ct, nullptr, V, 0, lg, 64, live);
     phase_sync();
     // 8: candidates score_b + log_softmax(asr) + lm_weight * log_softmax(lm), a wave per hypothesis
     for (int b = wave; b < live; b += kWaves) {
-      const float x = lane < V ? lg[b * 64 + lane] : -INFINITY;
-      const float xm = wave_max(x);
-      const float xs = wave_sum(lane < V ? expf(x - xm) : 0.f);
-      float fin = x - xm - logf(xs);
-      if (Hl) {
-        const float y = lane < V ? lmlg[b * 64 + lane] : -INFINITY;
-        const float ym = wave_max(y);
-        const float ys = wave_sum(lane < V ? expf(y - ym) : 0.f);
-        fin = fin + p.lm_weight * (y - ym - logf(ys));
-      }
-      fin += sc[b];
+      const float fin = score_row(lg + b * 64, Hl ? lmlg + b * 64 : nullptr, V, p.lm_weight) + sc[b];
       cand[b * 64 + lane] = (lane < V && fin == fin) ? fin : -INFINITY;      // a NaN is never chosen before a number
     }
     __syncthreads();
@@ -780,12 +716,12 @@ __global__ __launch_bounds__(kThreads) void charlm_step_kernel(LmStepDev p) {
   matvec(p.lm.w_ih1, H, x, H, nullptr, 0, nullptr, 0, p.lm.b_ih1, nullptr, 3 * H, 0, gi);
   matvec(p.lm.w_hh1, H, h1, H, nullptr, 0, nullptr, 0, p.lm.b_hh1, nullptr, 3 * H, 0, gh);
   __syncthreads();
-  gru_update(gi, gh, h1, H);
+  gru_update(gi, gh, 0, h1, 0, H, 1);
   __syncthreads();
   matvec(p.lm.w_ih2, H, h1, H, nullptr, 0, nullptr, 0, p.lm.b_ih2, nullptr, 3 * H, 0, gi);
   matvec(p.lm.w_hh2, H, h2, H, nullptr, 0, nullptr, 0, p.lm.b_hh2, nullptr, 3 * H, 0, gh);
   __syncthreads();
-  gru_update(gi, gh, h2, H);
+  gru_update(gi, gh, 0, h2, 0, H, 1);
   __syncthreads();
   matvec(p.lm.w_out, H, h2, H, nullptr, 0, nullptr, 0, p.lm.b_out, nullptr, p.V, 0, p.out + (int64_t)b * p.V);
   copy_row(p.h1_out + (int64_t)b * H, h1, H);
@@ -812,77 +748,26 @@ int allow_lds(const void* kernel, size_t bytes) {
   return SSASR_OK;
 }
 
-}  // namespace
-
-extern "C" int ssasr_decode_greedy(const ssasr_infer* dp, void* stream) {
-  if (!dp) return SSASR_EARG;
-  const ssasr_infer& d = *dp;
-  // the dimensions ssasr_decoder_fwd takes, with V <= 64 (one wave holds a score row)
-  if (d.N <= 0 || d.N > 0x7fffffff || d.T <= 0 || d.T > 16384 || d.E <= 0 || d.E > 8192 || d.E % 4 != 0 || d.A <= 0 ||
-      d.A > 2048 || d.A % 4 != 0 || d.D <= 0 || d.D > 4096 || d.D % 16 != 0 || d.V <= 0 || d.V > 64 ||
-      d.max_steps <= 0 || d.max_steps > (1 << 20) || d.eos < 0 || d.eos >= d.V)
-    return SSASR_EARG;
-  const void* need[] = {d.feat, d.enc_len, d.comp, d.w_psi, d.b_psi, d.w_phi, d.w_ih1, d.w_hh1, d.b_ih1, d.b_hh1,
-                        d.w_ih2, d.w_hh2, d.b_ih2, d.b_hh2, d.embed, d.w_ct, d.b_ct, d.chars, d.n_chars, d.scores};
-  for (const void* q : need)
-    if (!q) return SSASR_EARG;
-  const void* vec[] = {d.feat, d.comp, d.w_psi, d.w_phi, d.w_ih1, d.w_hh1, d.w_ih2, d.w_hh2, d.embed, d.w_ct};
-  for (const void* q : vec)
-    if (!aligned16(q)) return SSASR_EARG;
-  InferDev p{};
-  if (d.lm) {
-    if (!lm_ok(d.lm, p.lm) || d.lm->V != d.V) return SSASR_EARG;
-  }
-  const size_t bytes = sizeof(float) * (size_t)lds_map((int)d.T, (int)d.E, (int)d.A, (int)d.D, p.lm.H).total;
-  if (bytes > kMaxLds) return SSASR_EARG;
-  p.T = (int)d.T; p.E = (int)d.E; p.A = (int)d.A; p.D = (int)d.D; p.V = (int)d.V;
-  p.max_steps = (int)d.max_steps; p.eos = d.eos; p.lm_weight = d.lm ? d.lm_weight : 0.f;
-  p.feat = d.feat; p.enc_len = d.enc_len; p.comp = d.comp; p.w_psi = d.w_psi; p.b_psi = d.b_psi; p.w_phi = d.w_phi;
-  p.w_ih1 = d.w_ih1; p.w_hh1 = d.w_hh1; p.b_ih1 = d.b_ih1; p.b_hh1 = d.b_hh1;
-  p.w_ih2 = d.w_ih2; p.w_hh2 = d.w_hh2; p.b_ih2 = d.b_ih2; p.b_hh2 = d.b_hh2;
-  p.embed = d.embed; p.w_ct = d.w_ct; p.b_ct = d.b_ct;
-  p.chars = d.chars; p.n_chars = d.n_chars; p.scores = d.scores; p.att = d.att;
-  if (const int rc = allow_lds(reinterpret_cast<const void*>(decode_greedy_kernel), bytes)) return rc;
-  hipLaunchKernelGGL(decode_greedy_kernel, dim3((unsigned)d.N), dim3(kThreads), bytes, (hipStream_t)stream, p);
-  SSASR_LAUNCH_CHECK();
-  return SSASR_OK;
-}
-
-namespace {
-// the dimensions ssasr_decode_greedy takes (V <= 64: one wave holds a score row), without its LDS bound: the
-// beam kernel keeps no per-hypothesis state in LDS
-bool beam_dims_ok(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D, int64_t V, int64_t Hl, int64_t S) {
+// the dimensions ssasr_decoder_fwd takes, with V <= 64 (one wave holds a score row) and K hypotheses an utterance
+bool decode_dims_ok(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D, int64_t V, int64_t Hl, int64_t S) {
   return N > 0 && N <= 0x7fffffff && K >= 1 && K <= kMaxBeam && T > 0 && T <= 16384 && E > 0 && E <= 8192 &&
          E % 4 == 0 && A > 0 && A <= 2048 && A % 4 == 0 && D > 0 && D <= 4096 && D % 16 == 0 && V > 0 && V <= 64 &&
          Hl >= 0 && Hl <= 4096 && Hl % 4 == 0 && S > 0 && S <= (1 << 20);
 }
-}  // namespace
 
-extern "C" int64_t ssasr_decode_beam_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
-                                              int64_t V, int64_t Hl, int64_t S) {
-  if (!beam_dims_ok(N, K, T, E, A, D, V, Hl, S)) return 0;
-  return N * beam_ws_map((int)K, (int)T, (int)E, (int)A, (int)D, (int)Hl, (int)S).total * (int64_t)sizeof(float);
-}
-
-extern "C" int ssasr_decode_beam(const ssasr_beam* dp, void* stream) {
-  if (!dp) return SSASR_EARG;
-  const ssasr_beam& d = *dp;
-  BeamDev b{};
-  InferDev& p = b.in;
-  if (d.lm) {
-    if (!lm_ok(d.lm, p.lm) || d.lm->V != d.V) return SSASR_EARG;
-  }
-  if (!beam_dims_ok(d.N, d.K, d.T, d.E, d.A, d.D, d.V, p.lm.H, d.max_steps) || d.eos < 0 || d.eos >= d.V)
-    return SSASR_EARG;
+// What ssasr_infer and ssasr_beam (Desc) have in common: checks the dimensions for K hypotheses, the language
+// model and the pointers, and fills p (all of it but scores / att).  false: not a usable description.
+template <class Desc>
+bool infer_dev(const Desc& d, int64_t K, InferDev& p) {
+  if (d.lm && (!lm_ok(d.lm, p.lm) || d.lm->V != d.V)) return false;
+  if (!decode_dims_ok(d.N, K, d.T, d.E, d.A, d.D, d.V, p.lm.H, d.max_steps) || d.eos < 0 || d.eos >= d.V) return false;
   const void* need[] = {d.feat, d.enc_len, d.comp, d.w_psi, d.b_psi, d.w_phi, d.w_ih1, d.w_hh1, d.b_ih1, d.b_hh1,
-                        d.w_ih2, d.w_hh2, d.b_ih2, d.b_hh2, d.embed, d.w_ct, d.b_ct, d.ws, d.chars, d.n_chars,
-                        d.hyp_scores, d.n_hyps};
+                        d.w_ih2, d.w_hh2, d.b_ih2, d.b_hh2, d.embed, d.w_ct, d.b_ct, d.chars, d.n_chars};
   for (const void* q : need)
-    if (!q) return SSASR_EARG;
-  const void* vec[] = {d.feat, d.comp, d.w_psi, d.w_phi, d.w_ih1, d.w_hh1, d.w_ih2, d.w_hh2, d.embed, d.w_ct, d.ws};
+    if (!q) return false;
+  const void* vec[] = {d.feat, d.comp, d.w_psi, d.w_phi, d.w_ih1, d.w_hh1, d.w_ih2, d.w_hh2, d.embed, d.w_ct};
   for (const void* q : vec)
-    if (!aligned16(q)) return SSASR_EARG;
-  if (d.ws_bytes < ssasr_decode_beam_ws_bytes(d.N, d.K, d.T, d.E, d.A, d.D, d.V, p.lm.H, d.max_steps)) return SSASR_EARG;
+    if (!aligned16(q)) return false;
   p.T = (int)d.T; p.E = (int)d.E; p.A = (int)d.A; p.D = (int)d.D; p.V = (int)d.V;
   p.max_steps = (int)d.max_steps; p.eos = d.eos; p.lm_weight = d.lm ? d.lm_weight : 0.f;
   p.feat = d.feat; p.enc_len = d.enc_len; p.comp = d.comp; p.w_psi = d.w_psi; p.b_psi = d.b_psi; p.w_phi = d.w_phi;
@@ -890,6 +775,37 @@ extern "C" int ssasr_decode_beam(const ssasr_beam* dp, void* stream) {
   p.w_ih2 = d.w_ih2; p.w_hh2 = d.w_hh2; p.b_ih2 = d.b_ih2; p.b_hh2 = d.b_hh2;
   p.embed = d.embed; p.w_ct = d.w_ct; p.b_ct = d.b_ct;
   p.chars = d.chars; p.n_chars = d.n_chars;
+  return true;
+}
+
+}  // namespace
+
+extern "C" int ssasr_decode_greedy(const ssasr_infer* dp, void* stream) {
+  InferDev p{};
+  if (!dp || !infer_dev(*dp, 1, p) || !dp->scores) return SSASR_EARG;
+  // what decode_beam_kernel keeps in its workspace is in LDS here
+  const size_t bytes = sizeof(float) * (size_t)lds_map(p.T, p.E, p.A, p.D, p.lm.H).total;
+  if (bytes > kMaxLds) return SSASR_EARG;
+  p.scores = dp->scores; p.att = dp->att;
+  if (const int rc = allow_lds(reinterpret_cast<const void*>(decode_greedy_kernel), bytes)) return rc;
+  hipLaunchKernelGGL(decode_greedy_kernel, dim3((unsigned)dp->N), dim3(kThreads), bytes, (hipStream_t)stream, p);
+  SSASR_LAUNCH_CHECK();
+  return SSASR_OK;
+}
+
+extern "C" int64_t ssasr_decode_beam_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
+                                              int64_t V, int64_t Hl, int64_t S) {
+  if (!decode_dims_ok(N, K, T, E, A, D, V, Hl, S)) return 0;
+  return N * beam_ws_map((int)K, (int)T, (int)E, (int)A, (int)D, (int)Hl, (int)S).total * (int64_t)sizeof(float);
+}
+
+extern "C" int ssasr_decode_beam(const ssasr_beam* dp, void* stream) {
+  BeamDev b{};
+  if (!dp || !infer_dev(*dp, dp->K, b.in)) return SSASR_EARG;
+  const ssasr_beam& d = *dp;
+  if (!d.ws || !aligned16(d.ws) || !d.hyp_scores || !d.n_hyps ||
+      d.ws_bytes < ssasr_decode_beam_ws_bytes(d.N, d.K, d.T, d.E, d.A, d.D, d.V, b.in.lm.H, d.max_steps))
+    return SSASR_EARG;
   b.K = (int)d.K; b.ws = d.ws; b.hyp_scores = d.hyp_scores; b.n_hyps = d.n_hyps;
   hipLaunchKernelGGL(decode_beam_kernel, dim3((unsigned)d.N), dim3(kThreads), 0, (hipStream_t)stream, b);
   SSASR_LAUNCH_CHECK();

@@ -1019,12 +1019,14 @@ def clip_adadelta_ws(n, device):
 # ---------------------------------------------------------------------------
 # inference: CharLM step, single-launch greedy and beam-search decode (csrc/infer.hip)
 # ---------------------------------------------------------------------------
+_CHARLM_NAMES = ('emb.weight', 'layer_1.weight_ih', 'layer_1.weight_hh', 'layer_1.bias_ih', 'layer_1.bias_hh',
+                 'layer_2.weight_ih', 'layer_2.weight_hh', 'layer_2.bias_ih', 'layer_2.bias_hh', 'out.weight', 'out.bias')
+
+
 def _charlm_struct(lm):
     """(struct ssasr_charlm, the tensors it points into) of a charlm.CharLM."""
-    names = ('emb.weight', 'layer_1.weight_ih', 'layer_1.weight_hh', 'layer_1.bias_ih', 'layer_1.bias_hh',
-             'layer_2.weight_ih', 'layer_2.weight_hh', 'layer_2.bias_ih', 'layer_2.bias_hh', 'out.weight', 'out.bias')
     params = dict(lm.named_parameters())
-    keep = [_f32c(params[n].detach()) for n in names]
+    keep = [_f32c(params[n].detach()) for n in _CHARLM_NAMES]
     _need_gpu(*keep)
     s = _lib.CharLM(lm.input_size, lm.hidden_size, *[t.data_ptr() for t in keep])
     return s, keep
@@ -1044,36 +1046,42 @@ def charlm_step(lm, x, h_1, h_2):
     return out, n1, n2
 
 
+def _decode_struct(cls, feat, enc_len, params, psi, lm, lm_weight, eos, max_steps):
+    """What decode_greedy and beam_struct share: a _lib.Infer / _lib.Beam (cls) with the sizes, the inputs, comp,
+    the parameters, the language model and eos filled in -> (struct, the tensors and structs it points into)."""
+    feat = _f32c(feat)
+    _need_gpu(feat, enc_len)
+    N, T, E = feat.shape
+    A, D = params['w_phi'].shape
+    keep = {k: _f32c(v.detach()) for k, v in params.items()}
+    w_psi, b_psi = _f32c(psi[0].detach()), _f32c(psi[1].detach())
+    comp = torch.empty(N, T, A, device=feat.device, dtype=torch.float32)
+    d = cls()
+    d.N, d.T, d.E, d.A, d.D, d.V, d.max_steps = N, T, E, A, D, params['w_ct'].shape[0], int(max_steps)
+    d.feat, d.enc_len, d.comp = feat.data_ptr(), enc_len.data_ptr(), comp.data_ptr()
+    d.w_psi, d.b_psi = w_psi.data_ptr(), b_psi.data_ptr()
+    for k, v in keep.items():
+        setattr(d, k, v.data_ptr())
+    lm_keep = None
+    if lm is not None:
+        lm_keep = _charlm_struct(lm)
+        d.lm = C.pointer(lm_keep[0])
+        d.lm_weight = float(lm_weight)
+    d.eos = int(eos)
+    return d, (feat, enc_len, keep, w_psi, b_psi, comp, lm_keep)
+
+
 def decode_greedy(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, want_att=True):
     """ssasr_decode_greedy over feat [N, T, E] (each utterance encoded alone) and enc_len int32 [N]:
     -> (chars [N, max_steps] int32, n_chars [N] int32, scores [N, max_steps, V], att [N, max_steps, T] or None).
     params: ASR._decoder_params(); psi: (weight, bias); lm: a charlm.CharLM or None."""
     lib = _lib.load()
-    feat = _f32c(feat)
-    _need_gpu(feat, enc_len)
-    N, T, E = feat.shape
-    A, D = params['w_phi'].shape
-    V = params['w_ct'].shape[0]
-    dev = feat.device
-    keep = {k: _f32c(v.detach()) for k, v in params.items()}
-    w_psi, b_psi = _f32c(psi[0].detach()), _f32c(psi[1].detach())
-    comp = torch.empty(N, T, A, device=dev, dtype=torch.float32)
-    chars = torch.empty(N, max_steps, device=dev, dtype=torch.int32)
-    n_chars = torch.empty(N, device=dev, dtype=torch.int32)
-    scores = torch.empty(N, max_steps, V, device=dev, dtype=torch.float32)
-    att = torch.empty(N, max_steps, T, device=dev, dtype=torch.float32) if want_att else None
-    d = _lib.Infer()
-    d.N, d.T, d.E, d.A, d.D, d.V, d.max_steps = N, T, E, A, D, V, int(max_steps)
-    d.feat, d.enc_len, d.comp = feat.data_ptr(), enc_len.data_ptr(), comp.data_ptr()
-    d.w_psi, d.b_psi = w_psi.data_ptr(), b_psi.data_ptr()
-    for k, v in keep.items():
-        setattr(d, k, v.data_ptr())
-    lm_struct = None
-    if lm is not None:
-        lm_struct, lm_keep = _charlm_struct(lm)
-        d.lm = C.pointer(lm_struct)
-        d.lm_weight = float(lm_weight)
-    d.eos = int(eos)
+    d, keep = _decode_struct(_lib.Infer, feat, enc_len, params, psi, lm, lm_weight, eos, max_steps)
+    dev = keep[0].device
+    chars = torch.empty(d.N, d.max_steps, device=dev, dtype=torch.int32)
+    n_chars = torch.empty(d.N, device=dev, dtype=torch.int32)
+    scores = torch.empty(d.N, d.max_steps, d.V, device=dev, dtype=torch.float32)
+    att = torch.empty(d.N, d.max_steps, d.T, device=dev, dtype=torch.float32) if want_att else None
     d.chars, d.n_chars, d.scores = chars.data_ptr(), n_chars.data_ptr(), scores.data_ptr()
     d.att = att.data_ptr() if want_att else None
     check(lib.ssasr_decode_greedy(C.byref(d), _stream()), 'ssasr_decode_greedy')
@@ -1087,45 +1095,25 @@ def beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_
     """(struct ssasr_beam, its outputs (chars, n_chars, hyp_scores, n_hyps), the tensors it points into) for
     decode_beam's arguments; the outputs are allocated, not yet written."""
     lib = _lib.load()
-    feat = _f32c(feat)
-    _need_gpu(feat, enc_len)
-    N, T, E = feat.shape
-    A, D = params['w_phi'].shape
-    V = params['w_ct'].shape[0]
-    K, S = int(beam_size), int(max_steps)
-    dev = feat.device
+    d, keep = _decode_struct(_lib.Beam, feat, enc_len, params, psi, lm, lm_weight, eos, max_steps)
+    N, K, S = d.N, int(beam_size), d.max_steps
+    dev = keep[0].device
     hl = lm.hidden_size if lm is not None else 0
-    need = int(lib.ssasr_decode_beam_ws_bytes(N, K, T, E, A, D, V, hl, S))
+    need = int(lib.ssasr_decode_beam_ws_bytes(N, K, d.T, d.E, d.A, d.D, d.V, hl, S))
     if need <= 0:
         raise RuntimeError('ssasr_decode_beam: invalid argument (beam size %d, sizes N %d T %d E %d A %d D %d V %d '
-                           'H %d steps %d)' % (K, N, T, E, A, D, V, hl, S))
+                           'H %d steps %d)' % (K, N, d.T, d.E, d.A, d.D, d.V, hl, S))
     if ws is None:
         ws = torch.empty(need // 4, device=dev, dtype=torch.float32)
     _need_gpu(ws)
-    keep = {k: _f32c(v.detach()) for k, v in params.items()}
-    w_psi, b_psi = _f32c(psi[0].detach()), _f32c(psi[1].detach())
-    comp = torch.empty(N, T, A, device=dev, dtype=torch.float32)
     chars = torch.empty(N, K, S, device=dev, dtype=torch.int32)
     n_chars = torch.empty(N, K, device=dev, dtype=torch.int32)
     hyp_scores = torch.empty(N, K, device=dev, dtype=torch.float32)
     n_hyps = torch.empty(N, device=dev, dtype=torch.int32)
-    d = _lib.Beam()
-    d.N, d.T, d.E, d.A, d.D, d.V, d.max_steps, d.K = N, T, E, A, D, V, S, K
-    d.feat, d.enc_len, d.comp = feat.data_ptr(), enc_len.data_ptr(), comp.data_ptr()
-    d.w_psi, d.b_psi = w_psi.data_ptr(), b_psi.data_ptr()
-    for k, v in keep.items():
-        setattr(d, k, v.data_ptr())
-    lm_keep = None
-    if lm is not None:
-        lm_struct, lm_keep = _charlm_struct(lm)
-        lm_keep = (lm_struct, lm_keep)
-        d.lm = C.pointer(lm_struct)
-        d.lm_weight = float(lm_weight)
-    d.eos = int(eos)
-    d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+    d.K, d.ws, d.ws_bytes = K, ws.data_ptr(), ws.numel() * ws.element_size()
     d.chars, d.n_chars, d.hyp_scores, d.n_hyps = (chars.data_ptr(), n_chars.data_ptr(), hyp_scores.data_ptr(),
                                                   n_hyps.data_ptr())
-    return d, (chars, n_chars, hyp_scores, n_hyps), (feat, enc_len, keep, w_psi, b_psi, comp, ws, lm_keep)
+    return d, (chars, n_chars, hyp_scores, n_hyps), keep + (ws,)
 
 
 def decode_beam(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws=None):
@@ -1142,10 +1130,6 @@ def decode_beam(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_
 # ---------------------------------------------------------------------------
 # CharLM training: one chunk forward / backward (csrc/charlm_train.hip)
 # ---------------------------------------------------------------------------
-_CHARLM_NAMES = ('emb.weight', 'layer_1.weight_ih', 'layer_1.weight_hh', 'layer_1.bias_ih', 'layer_1.bias_hh',
-                 'layer_2.weight_ih', 'layer_2.weight_hh', 'layer_2.bias_ih', 'layer_2.bias_hh', 'out.weight', 'out.bias')
-
-
 def charlm_ws_layout(B, U, H, V):
     """{block: (offset, floats)} of the training workspace (include/ssasr.h, ssasr_charlm_train_ws_floats)."""
     R, out, o = U * B, {}, 0

@@ -141,6 +141,34 @@ def test_beam_size_one_is_greedy_decoding(golden, name, k):
     assert abs(nbest[0][0][1] - want) <= SCORE_ATOL * steps
 
 
+@pytest.mark.parametrize('k', [0, 1, None])
+@pytest.mark.parametrize('name', SMALL)
+def test_the_beam_kernel_at_width_one_is_the_greedy_kernel(golden, name, k):
+    """ssasr_decode_beam itself at K = 1 (ASR.decode(beam_size=1) never reaches it) against ssasr_decode_greedy on
+    the same encoded input, with each LM weight of the fixture and without an LM.  Every greedy decision of these
+    fixtures has a gap >= MIN_GAP, so the two kernels' different softmax summation orders cannot flip a character."""
+    from ss_asr_amd import ops
+    fx = golden(name)
+    asr, lm = tgd.models(fx)
+    x = torch.from_numpy(fx['x']).to(DEV)
+    with torch.no_grad():
+        feat, enc_lens = asr._encode_packed([x], [[x.shape[1]]])
+    assert feat.shape[1] == 5
+    args = (feat, enc_lens, asr._decoder_params(), (asr.attention.psi.weight, asr.attention.psi.bias),
+            None if k is None else lm, 0.5 if k is None else float(fx['lm_weights'][k]), EOS, STEPS)
+    g_chars, g_n, g_scores, _ = [None if t is None else t.cpu().numpy() for t in ops.decode_greedy(*args)]
+    chars, n_chars, hyp_scores, n_hyps = [t.cpu().numpy() for t in ops.decode_beam(*args, 1)]
+    n = int(g_n[0])
+    steps = min(n + 1, STEPS)
+    want = float(sum(np.float64(g_scores[0, s, g_chars[0, s]]) for s in range(steps)))
+    print('%s lm %s: %d characters, %d steps, beam score %.6f, sum of greedy\'s chosen entries %.6f' % (
+        name, k, n, steps, float(hyp_scores[0, 0]), want))
+    assert chars.shape == (1, 1, STEPS) and int(n_hyps[0]) == 1
+    assert int(n_chars[0, 0]) == n
+    assert np.array_equal(chars[0, 0, :n], g_chars[0, :n]) and not chars[0, 0, n:].any()
+    assert abs(float(hyp_scores[0, 0]) - want) <= SCORE_ATOL * steps
+
+
 def test_beam_search_matches_the_float64_checker(golden):
     pairs = differs = capped = staggered = full = 0
     for name, frames, k in PAIR_CASES:

@@ -24,7 +24,8 @@
  *     hipError_t for a HIP failure.
  *
  * ABI history.  Added under 16 without changing anything older (the version number stays): beam search --
- * ssasr_beam, ssasr_decode_beam_ws_bytes, ssasr_decode_beam.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
+ * ssasr_beam, ssasr_decode_beam_ws_bytes, ssasr_decode_beam; joint CTC / attention decoding -- ssasr_ctc_prefix,
+ * ssasr_decode_beam_ctc_ws_bytes, ssasr_decode_beam_ctc.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
  * (nothing older changed).  15: inference -- ssasr_charlm, ssasr_charlm_step, ssasr_infer, ssasr_decode_greedy (nothing
  * older changed).  14 and before: the training entry points below.
  *
@@ -682,6 +683,45 @@ typedef struct ssasr_beam {
 int64_t ssasr_decode_beam_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D, int64_t V,
                                    int64_t Hl, int64_t S);
 int ssasr_decode_beam(const ssasr_beam* d, void* stream);
+
+/* ---- joint CTC / attention decoding (added under ABI 16) -----------------------------------------------------
+ * BUILD-DEFINED: the reference has no CTC.  ssasr_decode_beam with the CTC prefix score of Watanabe et al. 2017 in
+ * every candidate's score, from the head that joint training leaves on the encoder (ssasr_ctc_loss_fwd's logits:
+ * W_ctc feat_t + b_ctc, blank = class 0 in training).  Per utterance, lp[t][v] = log_softmax(W_ctc feat_t + b_ctc)
+ * for t < enc_len, computed once by the utterance's own workgroup.  For a prefix g, gamma_n^g[t] / gamma_b^g[t] are
+ * the log-probabilities of g over frames 0..t ending in a non-blank / a blank, psi(g) its prefix score:
+ *   empty prefix: gamma_n = -inf, gamma_b[t] = lp[0][blank] + ... + lp[t][blank], psi = 0;
+ *   candidate (b, v), v != blank, v != eos, h = g . v:  psi(h) = logsumexp_t (phi_t + lp[t][v]) with phi_0 = 0 for
+ *     the empty g and -inf otherwise, phi_t = logaddexp(gamma_b^g[t-1], gamma_n^g[t-1]), or gamma_b^g[t-1] alone when
+ *     v equals g's last character (psi(h) needs the parent's gamma only);
+ *   v == eos: psi = logaddexp(gamma_n^g[len-1], gamma_b^g[len-1]);   v == blank: psi = -inf;
+ *   candidate score: score_b + (1 - ctc_weight) * log_softmax(speller)[v] + ctc_weight * (psi(h) - psi(g))
+ *     + lm_weight * log_softmax(lm)[v];
+ *   a candidate whose score is -inf (the blank character, a prefix that no longer fits the utterance's frames) is
+ *     never chosen: the width is min(K - finished, finite candidates).  A live hypothesis with a finite score always
+ *     keeps a finite <EOS> candidate, so the loop still ends;
+ *   a chosen non-eos candidate gets gamma^h from its parent's gamma by the standard recursion
+ *     gamma_n^h[t] = logaddexp(gamma_n^h[t-1], phi_t) + lp[t][v],
+ *     gamma_b^h[t] = logaddexp(gamma_b^h[t-1], gamma_n^h[t-1]) + lp[t][blank]   (gamma^h[-1] = -inf),
+ *     written into the other state buffer beside the copy of the Speller and LM state.
+ * Everything else -- ties, the <EOS> rule, the cap (a live hypothesis is emitted as it stands), the output order,
+ * the unused slots, an utterance's independence of N and the padded T -- is ssasr_decode_beam's.  gamma and psi are
+ * doubles, exp / log run in float on differences from the running maximum (as ssasr_ctc_loss_fwd's lattice).
+ * Accepted: what ssasr_decode_beam accepts, with 0 <= ctc_weight <= 1, 0 <= blank < V, blank != eos, and for
+ * ctc_weight > 0 w_ctc (16-byte aligned) and b_ctc; ws_bytes >= ssasr_decode_beam_ctc_ws_bytes(...), which is never
+ * less than ssasr_decode_beam_ws_bytes(...): the slice also holds lp [T][64] floats, gamma 2 x K x 2 x T doubles and
+ * psi 2 x K doubles.  ctc_weight == 0 launches ssasr_decode_beam's own kernel (the same bits; the head is unread).
+ * Everything else is an argument error before any launch, and the size query returns 0. */
+typedef struct ssasr_ctc_prefix {
+  const float* w_ctc;       /* [V][E] ctc_head.weight */
+  const float* b_ctc;       /* [V]    ctc_head.bias   */
+  float ctc_weight;         /* lambda                 */
+  int32_t blank;
+} ssasr_ctc_prefix;
+
+int64_t ssasr_decode_beam_ctc_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D, int64_t V,
+                                       int64_t Hl, int64_t S);
+int ssasr_decode_beam_ctc(const ssasr_beam* d, const ssasr_ctc_prefix* c, void* stream);
 
 #ifdef __cplusplus
 }

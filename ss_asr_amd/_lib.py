@@ -69,6 +69,11 @@ class Beam(C.Structure):
                 [(n, P) for n in ('chars', 'n_chars', 'hyp_scores', 'n_hyps')])
 
 
+class CtcPrefix(C.Structure):
+    """struct ssasr_ctc_prefix (include/ssasr.h)."""
+    _fields_ = [('w_ctc', P), ('b_ctc', P), ('ctc_weight', F32), ('blank', C.c_int32)]
+
+
 SIGNATURES = {
     'ssasr_abi_version': (I32, []),
     'ssasr_set_option': (I32, [C.c_char_p, I32]),
@@ -102,6 +107,8 @@ SIGNATURES = {
     'ssasr_decode_greedy': (I32, [C.POINTER(Infer), P]),
     'ssasr_decode_beam_ws_bytes': (I64, [I64] * 9),
     'ssasr_decode_beam': (I32, [C.POINTER(Beam), P]),
+    'ssasr_decode_beam_ctc_ws_bytes': (I64, [I64] * 9),
+    'ssasr_decode_beam_ctc': (I32, [C.POINTER(Beam), C.POINTER(CtcPrefix), P]),
     'ssasr_charlm_train_ws_floats': (I64, [I64, I64, I64, I64]),
     'ssasr_charlm_train_fwd': (I32, [C.POINTER(CharLM), P, P, P, P, I64, I64, P, P, P, P, P]),
     'ssasr_charlm_train_bwd': (I32, [C.POINTER(CharLM), P, I64, I64, F32, P, P]),

@@ -332,15 +332,28 @@ class ASR(nn.Module):
             host = att.detach().cpu()
         return encode_len, logits, host
 
-    def decode(self, x, x_len, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1):
+    def _ctc_head(self, ctc_weight):
+        """None for ctc_weight 0 (today's path), else (ctc_head weight, bias, ctc_weight) of a model that has one."""
+        ctc_weight = float(ctc_weight)
+        if not 0.0 <= ctc_weight <= 1.0:
+            raise ValueError('ctc_weight must lie in [0, 1], got %r' % (ctc_weight,))
+        if ctc_weight == 0.0:
+            return None
+        head = getattr(self, 'ctc_head', None)
+        if head is None:
+            raise ValueError('ctc_weight > 0 needs a model with a ctc_head (ctc.JointCTCASR); %s has none'
+                             % type(self).__name__)
+        return head.weight, head.bias, ctc_weight
+
+    def decode(self, x, x_len, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1, ctc_weight=0.0):
         """src/asr.py:112-173: greedy decoding of ONE utterance (x [1, seq, features], x_len from prepare_x)
         until <EOS> or max_decoding_steps (200 in the reference, :128), every step's character scores being
         log_softmax(speller) + lm_weight * log_softmax(rnn_lm).  Returns the decoded string.  rnn_lm None: no LM
         term.  The whole loop is one launch (ssasr_decode_greedy).  beam_size > 1: the best hypothesis of a beam
-        search of that width (decode_many)."""
+        search of that width (decode_many).  ctc_weight > 0: joint CTC / attention decoding (decode_nbest)."""
         assert len(x.shape) == 3 and x.shape[0] == 1
         return self.decode_many([x], [x_len], rnn_lm, mapper, lm_weight, max_decoding_steps=max_decoding_steps,
-                                beam_size=beam_size)[0]
+                                beam_size=beam_size, ctc_weight=ctc_weight)[0]
 
     def _encode_packed(self, xs, x_lens):
         """Each utterance encoded alone, packed to ([N, T'max, E], int32 [N] frame counts on the device)."""
@@ -360,17 +373,20 @@ class ASR(nn.Module):
                 packed[n, :f.shape[1]] = f[0]
         return packed, _dev_i32(enc_lens, dev)
 
-    def decode_many(self, xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1):
+    def decode_many(self, xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1,
+                    ctc_weight=0.0):
         """decode() for a list of single utterances in ONE decode launch.  Each utterance is encoded alone
         (blstm_4 recurs over the utterance axis, src/asr.py:237-238, :262: a batched encoder would change every
         transcript); the encoder outputs are packed to [N, T'max, E] and every utterance gets a workgroup of its
         own.  Returns the N strings; last_decode keeps (chars, n_chars, scores, att) on the device.
         beam_size > 1 (at most 32): beam search of that width in one launch (ssasr_decode_beam; no length
         normalisation); returns each utterance's best hypothesis and keeps (chars [N, K, steps], n_chars [N, K],
-        hyp_scores [N, K], n_hyps [N]) on the device in last_beam; last_decode is left as it was."""
-        if beam_size != 1:
+        hyp_scores [N, K], n_hyps [N]) on the device in last_beam; last_decode is left as it was.
+        ctc_weight > 0: as beam_size > 1, for any beam_size in 1..32 (decode_nbest)."""
+        if beam_size != 1 or self._ctc_head(ctc_weight) is not None:
             return [nbest[0][0] for nbest in self.decode_nbest(xs, x_lens, rnn_lm, mapper, lm_weight, beam_size,
-                                                               max_decoding_steps=max_decoding_steps)]
+                                                               max_decoding_steps=max_decoding_steps,
+                                                               ctc_weight=ctc_weight)]
         with torch.no_grad():
             packed, enc_lens = self._encode_packed(xs, x_lens)
             self.last_decode = ops.decode_greedy(
@@ -380,15 +396,22 @@ class ASR(nn.Module):
         chars, n_chars = self.last_decode[0].cpu().tolist(), self.last_decode[1].cpu().tolist()
         return [''.join(mapper.ind_to_char(c) for c in row[:n]) for row, n in zip(chars, n_chars)]
 
-    def decode_nbest(self, xs, x_lens, rnn_lm, mapper, lm_weight, beam_size, max_decoding_steps=200):
+    def decode_nbest(self, xs, x_lens, rnn_lm, mapper, lm_weight, beam_size, max_decoding_steps=200, *,
+                     ctc_weight=0.0):
         """Beam search over a list of single utterances in ONE launch: per utterance the list of (text, score),
         best first, score = the sum of the chosen characters' log_softmax(speller) + lm_weight *
         log_softmax(rnn_lm) entries (<EOS>'s included when it ended the hypothesis; no length normalisation).
-        beam_size 1 is greedy decoding (decode_many, last_decode); beam_size 2 .. 32 sets last_beam."""
+        beam_size 1 is greedy decoding (decode_many, last_decode); beam_size 2 .. 32 sets last_beam.
+        ctc_weight in (0, 1] (a model with a ctc_head): joint CTC / attention decoding, ssasr_decode_beam_ctc for
+        any beam_size in 1..32 (width 1 is the beam kernel at K = 1); a character's score entry is then
+        (1 - ctc_weight) * log_softmax(speller) + ctc_weight * (the CTC prefix score's increase) + lm_weight *
+        log_softmax(rnn_lm), and characters that the utterance's frames cannot hold are never chosen.  Sets
+        last_beam.  ctc_weight 0 is the path above exactly."""
         beam_size = int(beam_size)
         if not 1 <= beam_size <= ops.MAX_BEAM:
             raise ValueError('beam_size must be in 1..%d, got %d' % (ops.MAX_BEAM, beam_size))
-        if beam_size == 1:
+        ctc = self._ctc_head(ctc_weight)
+        if beam_size == 1 and ctc is None:
             texts = self.decode_many(xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=max_decoding_steps)
             chars, n_chars, scores, _ = self.last_decode
             steps = torch.clamp(n_chars + 1, max=max_decoding_steps)            # executed steps: <EOS>'s too
@@ -398,10 +421,9 @@ class ASR(nn.Module):
             return [[(t, s)] for t, s in zip(texts, totals)]
         with torch.no_grad():
             packed, enc_lens = self._encode_packed(xs, x_lens)
-            self.last_beam = ops.decode_beam(
-                packed, enc_lens, self._decoder_params(),
-                (self.attention.psi.weight, self.attention.psi.bias), rnn_lm, lm_weight,
-                mapper.char_to_ind(EOS_TKN), max_decoding_steps, beam_size)
+            args = (packed, enc_lens, self._decoder_params(), (self.attention.psi.weight, self.attention.psi.bias),
+                    rnn_lm, lm_weight, mapper.char_to_ind(EOS_TKN), max_decoding_steps, beam_size)
+            self.last_beam = ops.decode_beam(*args) if ctc is None else ops.decode_beam_ctc(*args, ctc)
         chars, n_chars, hyp_scores, n_hyps = [t.cpu().tolist() for t in self.last_beam]
         return [[(''.join(mapper.ind_to_char(c) for c in chars[i][k][:n_chars[i][k]]), hyp_scores[i][k])
                  for k in range(n_hyps[i])] for i in range(len(xs))]

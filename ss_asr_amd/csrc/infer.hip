@@ -476,7 +476,127 @@ struct BeamDev {
   int32_t* n_hyps;
 };
 
-__global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd) {
+// ---- CTC prefix scores (joint CTC / attention decoding; semantics in include/ssasr.h) -----------------------------
+// The CTC form of decode_beam_kernel adds, per utterance: lp = log_softmax(W_ctc feat_t + b_ctc) [len][64] (once,
+// before the loop, like comp), per live hypothesis g the two lattice rows gamma_n^g, gamma_b^g [T] (double-buffered
+// like the Speller state: a new slot's rows are written into the other buffer from its parent's) and psi(g).  All of
+// it is in the workspace slice behind what the plain form uses (T goes to 16,384: nothing of it may be assumed to fit
+// LDS); only the step's per-candidate psi (K * 64 doubles) and the hypotheses' last characters are in LDS.
+// gamma and psi are doubles; every exp / log runs in float on a DIFFERENCE from the larger operand / the running
+// maximum (ctc.hip's rule, DESIGN 4.7: a float lattice of magnitude ~ nll loses 2e-4 relative).
+struct CtcDev {
+  const float *w, *b;                     // ctc_head [V][E], [V]
+  float lambda;
+  int blank;
+};
+
+// what the CTC form adds behind BeamWs' blocks (offsets in floats, from the slice's start; the doubles start on
+// 16 bytes); total: the CTC form's slice
+struct CtcWs {
+  int64_t lp, gam, psi, total;
+};
+__host__ __device__ inline CtcWs ctc_ws_map(const BeamWs& m, int K, int T) {
+  CtcWs c;
+  int64_t o = m.total;
+  c.lp = o; o += (int64_t)T * 64;               // float [T][64]
+  c.gam = o; o += 2 * (2 * (int64_t)K * 2 * T); // double [2 buffers][K][gamma_n | gamma_b][T]
+  c.psi = o; o += 2 * (2 * (int64_t)K);         // double [2 buffers][K]
+  c.total = up4l(o);
+  return c;
+}
+
+constexpr int kCtcAhead = 4;              // frames whose loads a lattice loop issues before it needs the first
+
+// log(exp(a) + exp(b))
+__device__ __forceinline__ double log_add(double a, double b) {
+  const double m = fmax(a, b);
+  if (m == (double)-INFINITY) return m;
+  return m + (double)logf(1.f + expf((float)(fmin(a, b) - m)));
+}
+
+// phi_t of a prefix extended by a character: what may precede that character's first frame t, from the parent's
+// lattice at t - 1 (rep: the character repeats the parent's last one, so a blank has to lie between)
+__device__ __forceinline__ double ctc_phi(double pb, double pn, bool rep) { return rep ? pb : log_add(pb, pn); }
+
+// this lane's log_softmax(row)[lane]; called by a whole wave (V <= 64); what a lane >= V gets is no score
+__device__ float log_softmax_lane(const float* row, int V) {
+  const int lane = threadIdx.x & 63;
+  const float x = lane < V ? row[lane] : -INFINITY;
+  const float xm = wave_max(x);
+  const float xs = wave_sum(lane < V ? expf(x - xm) : 0.f);
+  return x - xm - logf(xs);
+}
+
+// psi(g . v), the CTC prefix score of the parent's prefix extended by v, from the parent's lattice rows alone:
+// logsumexp over t of phi_t + lp[t][v], as a running maximum and a sum of float exps of differences from it.
+// empty: the parent is the empty prefix (phi_0 = 0, otherwise -inf).  Called per lane with its own v.
+__device__ double ctc_prefix_score(const float* lp, const double* gn, const double* gb, int len, int v, bool empty,
+                                   bool rep) {
+  double mx = -INFINITY, sum = 0.0;
+  if (empty) {
+    mx = (double)lp[v];
+    sum = 1.0;
+  }
+  for (int t0 = 1; t0 < len; t0 += kCtcAhead) {
+    double pb[kCtcAhead], pn[kCtcAhead];
+    float l[kCtcAhead];
+#pragma unroll
+    for (int i = 0; i < kCtcAhead; ++i) {
+      const int t = min(t0 + i, len - 1);
+      pb[i] = gb[t - 1];
+      pn[i] = gn[t - 1];
+      l[i] = lp[(int64_t)t * 64 + v];
+    }
+#pragma unroll
+    for (int i = 0; i < kCtcAhead; ++i) {
+      if (t0 + i >= len) break;
+      const double x = ctc_phi(pb[i], pn[i], rep) + (double)l[i];
+      if (x > mx) {
+        sum = sum * (double)expf((float)(mx - x)) + 1.0;
+        mx = x;
+      } else if (x > (double)-INFINITY) {
+        sum += (double)expf((float)(x - mx));
+      }
+    }
+  }
+  return mx == (double)-INFINITY ? mx : mx + (double)logf((float)sum);
+}
+
+// The lattice rows of the parent's prefix extended by v, by the standard recursion, for one thread:
+// hn[t] = log_add(hn[t-1], phi_t) + lp[t][v], hb[t] = log_add(hb[t-1], hn[t-1]) + lp[t][blank].
+__device__ void ctc_extend(const float* lp, const double* pn0, const double* pb0, double* hn, double* hb, int len,
+                           int v, int blank, bool empty, bool rep) {
+  double n_ = empty ? (double)lp[v] : (double)-INFINITY, b_ = -INFINITY;
+  hn[0] = n_;
+  hb[0] = b_;
+  for (int t0 = 1; t0 < len; t0 += kCtcAhead) {
+    double pb[kCtcAhead], pn[kCtcAhead];
+    float lv[kCtcAhead], l0[kCtcAhead];
+#pragma unroll
+    for (int i = 0; i < kCtcAhead; ++i) {
+      const int t = min(t0 + i, len - 1);
+      pb[i] = pb0[t - 1];
+      pn[i] = pn0[t - 1];
+      lv[i] = lp[(int64_t)t * 64 + v];
+      l0[i] = lp[(int64_t)t * 64 + blank];
+    }
+#pragma unroll
+    for (int i = 0; i < kCtcAhead; ++i) {
+      if (t0 + i >= len) break;
+      const double nn = log_add(n_, ctc_phi(pb[i], pn[i], rep)) + (double)lv[i];
+      b_ = log_add(b_, n_) + (double)l0[i];
+      n_ = nn;
+      hn[t0 + i] = n_;
+      hb[t0 + i] = b_;
+    }
+  }
+}
+
+// CTC false: ssasr_decode_beam's kernel (cd unread).  CTC true: the same loop with the candidates scored
+// score_b + (1 - lambda) * log_softmax(asr) + lambda * (psi(h) - psi(g)) + lm_weight * log_softmax(lm), candidates
+// at -inf never chosen; only the prologue and phases 8 to 11 differ.
+template <bool CTC>
+__global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDev cd) {
   __shared__ float cand[kMaxBeam * 64];            // score_b + row_b[v]; NaN: struck out
   __shared__ float score[2][kMaxBeam];             // live hypotheses' scores, by step parity
   __shared__ float redv[kWaves];
@@ -487,12 +607,15 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd) {
   __shared__ float fin_score[kMaxBeam];            // finished / capped hypotheses in (step, candidate order)
   __shared__ int fin_len[kMaxBeam], fin_par[kMaxBeam];
   __shared__ int counts[2];                        // new live slots, finished hypotheses
+  __shared__ double cpsi[CTC ? kMaxBeam * 64 : 1]; // CTC: psi of the step's candidates
+  __shared__ int lastc[2][CTC ? kMaxBeam : 1];     // CTC: the live hypotheses' last characters, by step parity
 
   const InferDev& p = bd.in;
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int T = p.T, E = p.E, A = p.A, D = p.D, V = p.V, Hl = p.lm.H, K = bd.K, S = p.max_steps;
   const BeamWs m = beam_ws_map(K, T, E, A, D, Hl, S);
-  float* ws = bd.ws + (int64_t)n * m.total;
+  const CtcWs cm = ctc_ws_map(m, K, T);
+  float* ws = bd.ws + (int64_t)n * (CTC ? cm.total : m.total);
   float *xin = ws + m.xin, *lmx = ws + m.lmx, *q = ws + m.q, *gates = ws + m.gates, *en = ws + m.en,
         *part = ws + m.part, *gi = ws + m.gi, *gh = ws + m.gh, *lg = ws + m.lg, *lmlg = ws + m.lmlg;
   int32_t* bp = reinterpret_cast<int32_t*>(ws + m.bp);
@@ -515,6 +638,35 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd) {
   copy_row(xin, p.embed, D);
   if (Hl) copy_row(lmx, p.lm.emb, Hl);
   if (tid == 0) score[0][0] = 0.f;
+  // CTC: lp = log_softmax(ctc_head(feat)) of this utterance's frames, the head against the frames as vectors, then a
+  // wave per row; the empty prefix: gamma_n = -inf, gamma_b[t] = lp[0][blank] + .. + lp[t][blank], psi = 0
+  float* lp = ws + cm.lp;
+  double* gcur = reinterpret_cast<double*>(ws + cm.gam);
+  double* gnxt = gcur + (int64_t)K * 2 * T;
+  double* psi_cur = reinterpret_cast<double*>(ws + cm.psi);
+  double* psi_nxt = psi_cur + K;
+  if constexpr (CTC) {
+    matmat(cd.w, E, feat, E, E, nullptr, 0, nullptr, 0, 0, cd.b, nullptr, V, 0, lp, 64, len);
+    phase_sync();
+    for (int t = wave; t < len; t += kWaves) {
+      float* row = lp + (int64_t)t * 64;
+      const float x = lane < V ? row[lane] : -INFINITY;
+      const float xm = wave_max(x);
+      const float xs = wave_sum(lane < V ? expf(x - xm) : 0.f);
+      const double l = (double)xm + (double)logf(xs);
+      if (lane < V) row[lane] = (float)((double)x - l);
+    }
+    for (int t = tid; t < len; t += kThreads) gcur[t] = -INFINITY;
+    phase_sync();
+    if (tid == 0) {
+      double s = 0.0;
+      for (int t = 0; t < len; ++t) {
+        s += (double)lp[(int64_t)t * 64 + cd.blank];
+        gcur[T + t] = s;
+      }
+      psi_cur[0] = 0.0;
+    }
+  }
   phase_sync();
 
   int live = 1, nfin = 0, step = 0;
@@ -577,13 +729,37 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd) {
     matmat(p.w_ct, D, h2, Sz, D, nullptr, 0, nullptr, 0, 0, p.b_ct, nullptr, V, 0, lg, 64, live);
     phase_sync();
     // 8: candidates score_b + log_softmax(asr) + lm_weight * log_softmax(lm), a wave per hypothesis
-    for (int b = wave; b < live; b += kWaves) {
-      const float fin = score_row(lg + b * 64, Hl ? lmlg + b * 64 : nullptr, V, p.lm_weight) + sc[b];
-      cand[b * 64 + lane] = (lane < V && fin == fin) ? fin : -INFINITY;      // a NaN is never chosen before a number
+    if constexpr (CTC) {
+      // lane v owns candidate (b, v) and runs the frame loop over its parent's lattice rows
+      for (int b = wave; b < live; b += kWaves) {
+        const float a = log_softmax_lane(lg + b * 64, V);
+        const float l = Hl ? log_softmax_lane(lmlg + b * 64, V) : 0.f;
+        const double *gn = gcur + (int64_t)b * 2 * T, *gb = gn + T;
+        const int v = min(lane, V - 1);
+        double ps = ctc_prefix_score(lp, gn, gb, len, v, step == 0, step > 0 && v == lastc[step & 1][b]);
+        if (v == p.eos) ps = log_add(gn[len - 1], gb[len - 1]);
+        if (v == cd.blank) ps = -INFINITY;
+        cpsi[b * 64 + lane] = ps;
+        float fin = (1.f - cd.lambda) * a + cd.lambda * (float)(ps - psi_cur[b]);
+        if (Hl) fin += p.lm_weight * l;
+        fin += sc[b];
+        cand[b * 64 + lane] = (lane < V && fin == fin) ? fin : -INFINITY;
+      }
+    } else {
+      for (int b = wave; b < live; b += kWaves) {
+        const float fin = score_row(lg + b * 64, Hl ? lmlg + b * 64 : nullptr, V, p.lm_weight) + sc[b];
+        cand[b * 64 + lane] = (lane < V && fin == fin) ? fin : -INFINITY;      // a NaN is never chosen before a number
+      }
     }
     __syncthreads();
     // 9: the W best, in order: W rounds of a block-wide arg-max, ties to the lower flat index
-    const int width = min(K - nfin, live * V);
+    int width = min(K - nfin, live * V);
+    if constexpr (CTC) {                             // a candidate at -inf is never chosen
+      int finite = 0;
+      for (int c0 = 0; c0 < live * 64; c0 += kThreads)
+        finite += __syncthreads_count(c0 + tid < live * 64 && cand[min(c0 + tid, live * 64 - 1)] > -INFINITY);
+      width = min(width, finite);
+    }
     for (int i = 0; i < width; ++i) {
       float bv = -INFINITY;
       int bi = kNone;
@@ -634,6 +810,10 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd) {
           chr[nl] = v;
           sc_new[nl] = pick_score[i];
           bp[(int64_t)step * K + nl] = b | (v << 8);
+          if constexpr (CTC) {
+            psi_nxt[nl] = cpsi[pick[i]];
+            lastc[(step + 1) & 1][nl] = v;
+          }
           ++nl;
         }
       }
@@ -655,6 +835,20 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd) {
     for (int i = tid; i < nl * Hl; i += kThreads) {
       const int j = i / Hl, u = i % Hl;
       lmx[(int64_t)j * Hl + u] = p.lm.emb[(int64_t)chr[j] * Hl + u];
+    }
+    if constexpr (CTC) {                             // and its lattice rows are its parent's, advanced by its character
+      if (tid < nl) {
+        const double* pn = gcur + (int64_t)par[tid] * 2 * T;
+        double* hn = gnxt + (int64_t)tid * 2 * T;
+        ctc_extend(lp, pn, pn + T, hn, hn + T, len, chr[tid], cd.blank, step == 0,
+                   step > 0 && chr[tid] == lastc[step & 1][par[tid]]);
+      }
+      double* g = gcur;
+      gcur = gnxt;
+      gnxt = g;
+      g = psi_cur;
+      psi_cur = psi_nxt;
+      psi_nxt = g;
     }
     phase_sync();
     float* t = cur;
@@ -799,17 +993,48 @@ extern "C" int64_t ssasr_decode_beam_ws_bytes(int64_t N, int64_t K, int64_t T, i
   return N * beam_ws_map((int)K, (int)T, (int)E, (int)A, (int)D, (int)Hl, (int)S).total * (int64_t)sizeof(float);
 }
 
-extern "C" int ssasr_decode_beam(const ssasr_beam* dp, void* stream) {
+extern "C" int64_t ssasr_decode_beam_ctc_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
+                                                  int64_t V, int64_t Hl, int64_t S) {
+  if (!decode_dims_ok(N, K, T, E, A, D, V, Hl, S)) return 0;
+  const BeamWs m = beam_ws_map((int)K, (int)T, (int)E, (int)A, (int)D, (int)Hl, (int)S);
+  return N * ctc_ws_map(m, (int)K, (int)T).total * (int64_t)sizeof(float);
+}
+
+namespace {
+
+// ssasr_decode_beam (cp == nullptr) and ssasr_decode_beam_ctc
+int launch_beam(const ssasr_beam* dp, const ssasr_ctc_prefix* cp, void* stream) {
   BeamDev b{};
   if (!dp || !infer_dev(*dp, dp->K, b.in)) return SSASR_EARG;
   const ssasr_beam& d = *dp;
-  if (!d.ws || !aligned16(d.ws) || !d.hyp_scores || !d.n_hyps ||
-      d.ws_bytes < ssasr_decode_beam_ws_bytes(d.N, d.K, d.T, d.E, d.A, d.D, d.V, b.in.lm.H, d.max_steps))
-    return SSASR_EARG;
+  const int64_t need = (cp ? ssasr_decode_beam_ctc_ws_bytes : ssasr_decode_beam_ws_bytes)(
+      d.N, d.K, d.T, d.E, d.A, d.D, d.V, b.in.lm.H, d.max_steps);
+  if (!d.ws || !aligned16(d.ws) || !d.hyp_scores || !d.n_hyps || d.ws_bytes < need) return SSASR_EARG;
   b.K = (int)d.K; b.ws = d.ws; b.hyp_scores = d.hyp_scores; b.n_hyps = d.n_hyps;
-  hipLaunchKernelGGL(decode_beam_kernel, dim3((unsigned)d.N), dim3(kThreads), 0, (hipStream_t)stream, b);
+  CtcDev c{};
+  if (cp) {
+    if (!(cp->ctc_weight >= 0.f && cp->ctc_weight <= 1.f) || cp->blank < 0 || cp->blank >= d.V || cp->blank == d.eos)
+      return SSASR_EARG;
+    if (cp->ctc_weight > 0.f) {                     // weight 0: the head is unread, 0 * -inf is never formed
+      if (!cp->w_ctc || !cp->b_ctc || !aligned16(cp->w_ctc)) return SSASR_EARG;
+      c = CtcDev{cp->w_ctc, cp->b_ctc, cp->ctc_weight, cp->blank};
+    }
+  }
+  if (c.w)
+    hipLaunchKernelGGL(decode_beam_kernel<true>, dim3((unsigned)d.N), dim3(kThreads), 0, (hipStream_t)stream, b, c);
+  else
+    hipLaunchKernelGGL(decode_beam_kernel<false>, dim3((unsigned)d.N), dim3(kThreads), 0, (hipStream_t)stream, b, c);
   SSASR_LAUNCH_CHECK();
   return SSASR_OK;
+}
+
+}  // namespace
+
+extern "C" int ssasr_decode_beam(const ssasr_beam* dp, void* stream) { return launch_beam(dp, nullptr, stream); }
+
+extern "C" int ssasr_decode_beam_ctc(const ssasr_beam* dp, const ssasr_ctc_prefix* cp, void* stream) {
+  if (!cp) return SSASR_EARG;
+  return launch_beam(dp, cp, stream);
 }
 
 extern "C" int ssasr_charlm_step(const ssasr_charlm* lm, const int32_t* x, const float* h1, const float* h2,

@@ -1091,15 +1091,17 @@ def decode_greedy(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, wan
 MAX_BEAM = 32
 
 
-def beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws=None):
+def beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws=None, ctc=False):
     """(struct ssasr_beam, its outputs (chars, n_chars, hyp_scores, n_hyps), the tensors it points into) for
-    decode_beam's arguments; the outputs are allocated, not yet written."""
+    decode_beam's arguments; the outputs are allocated, not yet written.  ctc: the workspace is sized for
+    ssasr_decode_beam_ctc."""
     lib = _lib.load()
     d, keep = _decode_struct(_lib.Beam, feat, enc_len, params, psi, lm, lm_weight, eos, max_steps)
     N, K, S = d.N, int(beam_size), d.max_steps
     dev = keep[0].device
     hl = lm.hidden_size if lm is not None else 0
-    need = int(lib.ssasr_decode_beam_ws_bytes(N, K, d.T, d.E, d.A, d.D, d.V, hl, S))
+    query = lib.ssasr_decode_beam_ctc_ws_bytes if ctc else lib.ssasr_decode_beam_ws_bytes
+    need = int(query(N, K, d.T, d.E, d.A, d.D, d.V, hl, S))
     if need <= 0:
         raise RuntimeError('ssasr_decode_beam: invalid argument (beam size %d, sizes N %d T %d E %d A %d D %d V %d '
                            'H %d steps %d)' % (K, N, d.T, d.E, d.A, d.D, d.V, hl, S))
@@ -1124,6 +1126,27 @@ def decode_beam(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_
     ssasr_decode_beam_ws_bytes bytes, or None to allocate one."""
     d, outs, keep = beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws)
     check(_lib.load().ssasr_decode_beam(C.byref(d), _stream()), 'ssasr_decode_beam')
+    return outs
+
+
+CTC_BLANK = 0      # class 0, as in training (ctc.BLANK)
+
+
+def ctc_prefix_struct(ctc, blank=CTC_BLANK):
+    """(struct ssasr_ctc_prefix, the tensors it points into) of ctc = (ctc_head weight [V, E], bias [V], ctc_weight)."""
+    w, b = _f32c(ctc[0].detach()), _f32c(ctc[1].detach())
+    _need_gpu(w, b)
+    return _lib.CtcPrefix(w.data_ptr(), b.data_ptr(), float(ctc[2]), int(blank)), (w, b)
+
+
+def decode_beam_ctc(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ctc, ws=None,
+                    blank=CTC_BLANK):
+    """ssasr_decode_beam_ctc: decode_beam with the CTC prefix score of ctc = (ctc_head weight [V, E], bias [V],
+    ctc_weight in [0, 1]) in every candidate's score (include/ssasr.h), for 1 <= beam_size <= 32.  Same results as
+    decode_beam; ws: at least ssasr_decode_beam_ctc_ws_bytes bytes, or None to allocate one."""
+    d, outs, keep = beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws, ctc=True)
+    c, c_keep = ctc_prefix_struct(ctc, blank)
+    check(_lib.load().ssasr_decode_beam_ctc(C.byref(d), C.byref(c), _stream()), 'ssasr_decode_beam_ctc')
     return outs
 
 

@@ -462,7 +462,10 @@ class ASRTester(Solver):
     `decode_file` name.  asr.decode_beam_size is honoured: 1 decodes greedily, 2 .. 32 runs a beam search of that
     width (the reference announces one and leaves it a TODO, :590), `decode_group` utterances per launch
     (ASR.decode_many).  The reference constructs a CharLM and never loads
-    it (:567-569); here <ckpdir>/char_lm.cpt is loaded when it exists."""
+    it (:567-569); here <ckpdir>/char_lm.cpt is loaded when it exists.
+    BUILD-DEFINED: with 'ctc_weight' in asr.mdl the model is ctc.JointCTCASR, as ASRTrainer builds it, and
+    asr.decode_ctc_weight (absent: 0) in (0, 1] decodes with the CTC prefix score at that weight (joint CTC /
+    attention decoding, ssasr_decode_beam_ctc, any beam size); `decode_file` then ends in `_ctc<weight>`."""
     decode_group = 32
 
     def __init__(self, config, paras):
@@ -477,7 +480,11 @@ class ASRTester(Solver):
             n_jobs=self.set_if_exists('loader_jobs', 8), use_gpu=self.paras.gpu)
 
     def set_model(self):
-        self.asr_model = self.setup_module(ASR, self.ckppath, self.mapper.get_dim(),
+        asr_cls = ASR
+        if 'ctc_weight' in self.config['asr']['mdl']:
+            from .ctc import JointCTCASR
+            asr_cls = JointCTCASR
+        self.asr_model = self.setup_module(asr_cls, self.ckppath, self.mapper.get_dim(),
                                            **self.config['asr']['mdl'])
         self.asr_model.eval()
         lm_conf = self.config['char_lm']            # conf/default.yaml:84-89 keeps it under mdl; src/trainer.py:568 reads it beside mdl
@@ -495,6 +502,9 @@ class ASRTester(Solver):
         self.njobs = self.config['asr']['decode_jobs']
         self.decode_step_ratio = self.config['asr']['max_decode_step_ratio']
         self.decode_file += '_lm{:}'.format(self.config['asr']['decode_lm_weight'])
+        self.decode_ctc_weight = self.config['asr'].get('decode_ctc_weight', 0)
+        if self.decode_ctc_weight > 0:
+            self.decode_file += '_ctc{:}'.format(self.decode_ctc_weight)
 
     def exec(self, lm_weight=None):
         """-> the decoded strings, one per utterance of the test index, in index order."""
@@ -503,15 +513,19 @@ class ASRTester(Solver):
         beam = self.decode_beam_size
         if isinstance(beam, bool) or not isinstance(beam, int) or not 1 <= beam <= 32:
             raise ValueError('asr.decode_beam_size must be an integer in 1..32, got {!r}'.format(beam))
-        self.verbose('Start decoding ({})'.format(
-            'beam search, beam size {}'.format(beam) if beam > 1 else 'greedy, beam size 1'))
+        ctc_weight = self.decode_ctc_weight
+        if isinstance(ctc_weight, bool) or not isinstance(ctc_weight, (int, float)) or not 0 <= ctc_weight <= 1:
+            raise ValueError('asr.decode_ctc_weight must be a number in [0, 1], got {!r}'.format(ctc_weight))
+        self.verbose('Start decoding ({}{})'.format(
+            'beam search, beam size {}'.format(beam) if beam > 1 else 'greedy, beam size 1',
+            ', joint CTC / attention scores, CTC weight {}'.format(ctc_weight) if ctc_weight > 0 else ''))
         self.verbose('Number of utts to decode : {}, {} per launch.'.format(len(self.test_set), self.decode_group))
         results, xs, x_lens = [], [], []
 
         def flush():
             if xs:
                 results.extend(self.asr_model.decode_many(xs, x_lens, self.lm, self.mapper, lm_weight,
-                                                          beam_size=beam))
+                                                          beam_size=beam, ctc_weight=ctc_weight))
                 del xs[:], x_lens[:]
 
         for b_ind, (x, y) in enumerate(self.test_set):

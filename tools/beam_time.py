@@ -5,7 +5,10 @@ with events around it, warm, median over --steps launches.  A step's time is the
 slowest utterance ran (n_chars + 1 for greedy, the longest hypothesis for a beam, both capped at 200).  The
 comparison that matters: K hypotheses in one workgroup against K x the greedy figure of the same run.
 
-    python tools/beam_time.py [--steps 5] [--warmup 2] [--beams 1,3,8]
+--ctc W adds, per K, the same launch through ssasr_decode_beam_ctc with a random ctc_head at CTC weight W (K = 1
+then is the beam kernel at width 1), and with weight 0 (the plain kernel through the new entry).
+
+    python tools/beam_time.py [--steps 5] [--warmup 2] [--beams 1,3,8] [--ctc 0.3]
 """
 import argparse
 import json
@@ -41,6 +44,7 @@ def main():
     ap.add_argument('--utts', type=int, default=32)
     ap.add_argument('--frames', type=int, default=100)
     ap.add_argument('--max-steps', type=int, default=200)
+    ap.add_argument('--ctc', type=float, default=0.0, help='CTC weight of the additional joint-decoding rows')
     args = ap.parse_args()
     from ss_asr_amd import ops
     from ss_asr_amd.asr import ASR
@@ -69,9 +73,20 @@ def main():
         ran = int(min(n_chars.max() + 1, S))
         res['K%d' % K] = dict(launch_ms=ms, steps_run=ran, us_per_step=1e3 * ms / ran,
                               mean_chars=float(n_chars[n_chars > 0].mean()) if (n_chars > 0).any() else 0.0)
+        if args.ctc > 0:
+            head = torch.nn.Linear(512, V).to(dev)
+            ws = torch.empty(int(ops._lib.load().ssasr_decode_beam_ctc_ws_bytes(N, K, T, 512, 128, 256, V, 128, S)) // 4,
+                             device=dev)
+            for tag, weight in (('ctc', args.ctc), ('ctc_entry_weight0', 0.0)):
+                def fn(K=K, ws=ws, weight=weight):
+                    held['out'] = ops.decode_beam_ctc(*call, K, (head.weight, head.bias, weight), ws=ws)
+                ms = timed(fn, args.steps, args.warmup)
+                n_chars = held['out'][1].cpu().numpy()
+                ran = int(min(n_chars.max() + 1, S))
+                res['K%d_%s' % (K, tag)] = dict(launch_ms=ms, steps_run=ran, us_per_step=1e3 * ms / ran)
     if 'K1' in res:
         for k, v in res.items():
-            if k.startswith('K') and k != 'K1':
+            if k.startswith('K') and k != 'K1' and '_' not in k:
                 v['vs_K_greedy_workgroups'] = v['us_per_step'] / (int(k[1:]) * res['K1']['us_per_step'])
     print(json.dumps(res))
 

@@ -362,7 +362,7 @@ struct EncPersist {
   int delay;             // initial pacing delay (PersistPacer)
   int ys_s, ys_n;
   int S, N, H;
-  // KI > 0 (template): the helper wave computes the input->hidden pre-activations itself
+  // KI > 0 (template): the kernel forms the input->hidden pre-activations itself from x
   // (small input widths: I = 16 * KI) instead of streaming them from `gates`
   const float* x;        // logical [S][N][I] through xs_s / xs_n (floats)
   int64_t xs_s, xs_n;
@@ -492,10 +492,9 @@ struct PersistPacer {
 // so that no HBM latency, no scattered store and no address arithmetic for
 // them sits in the recurrence waves.
 // KI > 0: the layer's input is narrow (I = 16 * KI floats, the 80 mel bins of the first layer) and
-// the helper wave forms the pre-activations W_ih x_s + b itself, one step ahead, with KI * 4 MFMAs
-// per column tile while the recurrence waves wait for their operand loads: the input projection
-// GEMM and its 2 x 0.4 GB of pre-activation traffic disappear.  A fragment: row 4 * unit + gate of
-// this workgroup's 16 gate rows, so that D leaves unit q's four gates in lane (q, column).
+// W_ih x_s joins the recurrence waves' K-split product (below): the input projection GEMM and its
+// 2 x 0.4 GB of pre-activation traffic disappear.  The helper wave streams x instead of the
+// pre-activations: two steps ahead from HBM into its registers, one step ahead into an LDS ring.
 #ifndef SSASR_FWD_HELPER_WAVE
 #define SSASR_FWD_HELPER_WAVE 5
 #endif
@@ -510,6 +509,12 @@ __global__ __launch_bounds__(FWD_THREADS) void lstm_enc_fwd_persistent_kernel(En
   // step results staged for the helper wave: [i, f, g, o, c, h][column][4 units]
   __shared__ __attribute__((aligned(16))) float stage[6][16 * NB][4];
   __shared__ float addbuf[2][NB][4][64];     // [parity][epilogue wave][gate][lane]
+  // KI > 0: x of steps i (being read) and i + 1 (being written), [parity][k-block j][wave w][column tile][lane]:
+  // lane (q, r) of recurrence wave w finds feature 16 j + 4 q + w of column 16 t + r, its B operand of MFMA j,
+  // at dword lane of plane (j, w, t).  Every access, the helper's writes too (lane (q, r) holds features
+  // 16 j + 4 q .. + 3 of column r: element w goes to plane (j, w, t)), is 64 consecutive dwords by lane, so the 32
+  // lanes of a half-wave (the group that shares LDS cycles for b32 reads and writes) fall on 32 different banks.
+  __shared__ float xring[KI > 0 ? 2 : 1][KI > 0 ? KI : 1][4][NB][KI > 0 ? 64 : 1];
   __shared__ int missed;                         // a wave of this step had to re-fetch (feeds the pacer)
   float* sH = &stage[5][0][0];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -534,51 +539,47 @@ __global__ __launch_bounds__(FWD_THREADS) void lstm_enc_fwd_persistent_kernel(En
     // ------------------------------ helper wave ------------------------------
     PersistPacer pacer{e.delay, 0};
     float nadd[NB][4];
-    constexpr int KIN = KI > 0 ? KI : 1;
-    float4 wA[KIN], xb[NB][KIN];
-    float bsum[4] = {0.f, 0.f, 0.f, 0.f};
-    if (KI > 0) {
-      const int rowA = (r & 3) * H + 4 * tile + (r >> 2);       // A row r = 4 * unit + gate
-      const float* wp = e.wih[d] + (int64_t)rowA * (16 * KI) + 4 * q;
-#pragma unroll
-      for (int j = 0; j < KIN; ++j) wA[j] = ld4(wp + 16 * j);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) bsum[g] = e.bih[d][g * H + u] + e.bhh[d][g * H + u];
-    }
     auto fetch = [&](int i) {
       const int s = d ? S - 1 - i : i;
 #pragma unroll
       for (int bt = 0; bt < NB; ++bt) {
         const int n = n0 + 16 * bt + r;
-        if (KI > 0) {
-          const float* xp = e.x + (int64_t)s * e.xs_s + (int64_t)(n < N ? n : N - 1) * e.xs_n + 4 * q;
+        const int64_t g0 = ((int64_t)s * NT + (n < N ? n : N - 1)) * 4 * H + u;
 #pragma unroll
-          for (int j = 0; j < KIN; ++j) xb[bt][j] = ld4(xp + 16 * j);
-        } else {
-          const int64_t g0 = ((int64_t)s * NT + (n < N ? n : N - 1)) * 4 * H + u;
-#pragma unroll
-          for (int g = 0; g < 4; ++g) nadd[bt][g] = gbase[g0 + (int64_t)g * H];
-        }
+        for (int g = 0; g < 4; ++g) nadd[bt][g] = gbase[g0 + (int64_t)g * H];
       }
     };
     auto publish = [&](int i) {
 #pragma unroll
-      for (int bt = 0; bt < NB; ++bt) {
-        if (KI > 0) {
-          f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-          for (int j = 0; j < KIN; ++j) {
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wA[j].x, xb[bt][j].x, a0, 0, 0, 0);
-            a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wA[j].y, xb[bt][j].y, a1, 0, 0, 0);
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wA[j].z, xb[bt][j].z, a0, 0, 0, 0);
-            a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wA[j].w, xb[bt][j].w, a1, 0, 0, 0);
-          }
-#pragma unroll
-          for (int g = 0; g < 4; ++g) nadd[bt][g] = a0[g] + a1[g] + bsum[g];
-        }
+      for (int bt = 0; bt < NB; ++bt)
 #pragma unroll
         for (int g = 0; g < 4; ++g) addbuf[i & 1][bt][g][lane] = nadd[bt][g];
+    };
+    // KI > 0: x of step i travels HBM -> registers (lane (q, r): features 16 j + 4 q .. + 3 of column r, fetched
+    // two steps ahead) -> xring[i & 1] (one step ahead): the schedule of the pre-activations above.
+    constexpr int KIN = KI > 0 ? KI : 1;
+    float4 xb[NB][KIN];
+    auto fetch_x = [&](int i) {
+      const int s = d ? S - 1 - i : i;
+#pragma unroll
+      for (int bt = 0; bt < NB; ++bt) {
+        const int n = n0 + 16 * bt + r;
+        const float* xp = e.x + (int64_t)s * e.xs_s + (int64_t)(n < N ? n : N - 1) * e.xs_n + 4 * q;
+#pragma unroll
+        for (int j = 0; j < KIN; ++j) xb[bt][j] = ld4(xp + 16 * j);
       }
+    };
+    auto put_x = [&](int i) {
+      float* slot = &xring[i & 1][0][0][0][lane];
+#pragma unroll
+      for (int bt = 0; bt < NB; ++bt)
+#pragma unroll
+        for (int j = 0; j < KIN; ++j) {
+          slot[((j * 4 + 0) * NB + bt) * 64] = xb[bt][j].x;
+          slot[((j * 4 + 1) * NB + bt) * 64] = xb[bt][j].y;
+          slot[((j * 4 + 2) * NB + bt) * 64] = xb[bt][j].z;
+          slot[((j * 4 + 3) * NB + bt) * 64] = xb[bt][j].w;
+        }
     };
     // Row-major copies of a step's results (activated gates, c, h, y) leave
     // through this wave one step later, as 16-byte stores: 7 arrays x 32 columns
@@ -607,11 +608,14 @@ __global__ __launch_bounds__(FWD_THREADS) void lstm_enc_fwd_persistent_kernel(En
         }
       }
     };
-    // KI > 0: the recurrence waves form the input projection themselves (below): nothing to stream here
     const int i0 = 0, i1 = S;
     if (KI == 0) {
       fetch(i0); publish(i0);
       if (i0 + 1 < i1) fetch(i0 + 1);
+    } else {
+      fetch_x(i0); put_x(i0);
+      if (i0 + 1 < i1) fetch_x(i0 + 1);
+      __syncthreads();                                // x of step 0 is in the ring
     }
     for (int i = i0; i < i1; ++i) {
       if (i > 0) {
@@ -620,8 +624,11 @@ __global__ __launch_bounds__(FWD_THREADS) void lstm_enc_fwd_persistent_kernel(En
         SSASR_PTRACE_H(i, 9);
         __syncthreads();                              // operand loads released
       }
-      // addbuf[(i + 1) & 1] was last read in step i - 1
-      if (KI == 0 && i + 1 < i1) { publish(i + 1); if (i + 2 < i1) fetch(i + 2); }
+      // addbuf[(i + 1) & 1] and xring[(i + 1) & 1] were last read in step i - 1
+      if (i + 1 < i1) {
+        if (KI == 0) { publish(i + 1); if (i + 2 < i1) fetch(i + 2); }
+        else { put_x(i + 1); if (i + 2 < i1) fetch_x(i + 2); }
+      }
       if (i > i0) flush(i - 1);                       // stage is rewritten after the next barrier
       __syncthreads();                                // product done
       if (i > i0) { pacer.update(missed != 0); missed = 0; }
@@ -648,20 +655,17 @@ __global__ __launch_bounds__(FWD_THREADS) void lstm_enc_fwd_persistent_kernel(En
   float cstate = 0.f;
   // KI > 0 (narrow input, the 80 mel bins of the first layer): W_ih x_s is part of the SAME K-split
   // product.  Wave w multiplies the features 16 j + 4 q + w (one MFMA per j) into its accumulators
-  // while its exchange loads are in flight -- the matrix pipe is idle then -- so the pre-activations
-  // never pass through LDS and the helper wave's 4 KI MFMAs per step (which shared a SIMD with wave 1)
-  // are gone.  x is fetched two steps ahead (first touch comes from HBM); the biases join in the epilogue.
+  // while its exchange loads are in flight -- the matrix pipe is idle then.  The operands come from
+  // xring, read before the barrier that releases the exchange loads: no load of x shares the
+  // vector-memory queue (and its in-order return) with the exchange loads.  The biases join in the epilogue.
   constexpr int KIN = KI > 0 ? KI : 1;
-  float wiq[KIN], xcur[NB][KIN], xnxt[NB][KIN], xnn[NB][KIN], bsum[4] = {0.f, 0.f, 0.f, 0.f};
-  auto load_x = [&](int i, float (&dst)[NB][KIN]) {
-    const int s = d ? S - 1 - i : i;
+  float wiq[KIN], xcur[NB][KIN], bsum[4] = {0.f, 0.f, 0.f, 0.f};
+  auto read_x = [&](int i) {
+    const float* slot = &xring[i & 1][0][wave][0][lane];
 #pragma unroll
-    for (int t = 0; t < NB; ++t) {
-      const int nn = n0 + 16 * t + r;
-      const float* xp = e.x + (int64_t)s * e.xs_s + (int64_t)(nn < N ? nn : N - 1) * e.xs_n + 4 * q + wave;
+    for (int t = 0; t < NB; ++t)
 #pragma unroll
-      for (int j = 0; j < KIN; ++j) dst[t][j] = xp[16 * j];
-    }
+      for (int j = 0; j < KIN; ++j) xcur[t][j] = slot[((j * 4) * NB + t) * 64];
   };
   if (KI > 0) {
     const int rowA = (r & 3) * H + 4 * tile + (r >> 2);       // A row r = 4 * unit + gate
@@ -672,9 +676,7 @@ __global__ __launch_bounds__(FWD_THREADS) void lstm_enc_fwd_persistent_kernel(En
 #pragma unroll
       for (int g = 0; g < 4; ++g) bsum[g] = e.bih[d][g * H + u] + e.bhh[d][g * H + u];
     }
-    load_x(i0, xcur);
-    load_x(i0 + 1 < S ? i0 + 1 : i0, xnxt);
-    load_x(i0 + 2 < S ? i0 + 2 : i0, xnn);
+    __syncthreads();                                  // x of step 0 is in the ring
   }
   const int len = (epi && e.lens) ? e.lens[n] : 0x7fffffff;
   // lane part of the h_{s-1} operand address.  Columns past N read this chunk's OWN first column
@@ -698,6 +700,7 @@ __global__ __launch_bounds__(FWD_THREADS) void lstm_enc_fwd_persistent_kernel(En
 #pragma unroll
     for (int t = 0; t < NB; ++t) { acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; acc2[t] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     SSASR_PTRACE(i, 0);
+    if (KI > 0) read_x(i);       // written by the helper before the previous step's "product done"
     if (i > 0) {
       const unsigned sbase = (unsigned)((int64_t)sp * Np * H * 4);   // step offset in bytes
       __syncthreads();                                // released by the helper wave
@@ -757,13 +760,6 @@ __global__ __launch_bounds__(FWD_THREADS) void lstm_enc_fwd_persistent_kernel(En
       for (int j = 0; j < KIN; ++j)
 #pragma unroll
         for (int t = 0; t < NB; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(wiq[j], xcur[t][j], acc[t], 0, 0, 0);
-    }
-    if (KI > 0) {                // rotate the sets that have arrived (x of steps i + 1, i + 2), then x of step i + 3 on its way
-#pragma unroll
-      for (int t = 0; t < NB; ++t)
-#pragma unroll
-        for (int j = 0; j < KIN; ++j) { xcur[t][j] = xnxt[t][j]; xnxt[t][j] = xnn[t][j]; }
-      if (i + 3 < S) load_x(i + 3, xnn);
     }
 #pragma unroll
     for (int t = 0; t < NB; ++t) red[(wave * NB + t) * 64 + lane] = acc[t] + acc2[t];

@@ -119,6 +119,19 @@ int main(int argc, char** argv) {
   pb.status = sync + 4; pb.delay = getenv("DELAY_B") ? atoi(getenv("DELAY_B")) : 16;
   pb.ys_s = (int)ys_s; pb.ys_n = (int)ys_n; pb.S = (int)S; pb.N = (int)N; pb.H = (int)H;
   const int nbF = getenv("NB_F") ? atoi(getenv("NB_F")) : 2;
+  // FUSED=1: the first layer's form (80 input features projected inside the kernel) instead of layers 2-4's
+  const bool fused = getenv("FUSED") != nullptr;
+  if (fused) {
+    float *x, *wih, *bias;
+    CK(hipMalloc(&x, sizeof(float) * rows * 80));
+    CK(hipMalloc(&wih, sizeof(float) * 2 * 4 * H * 80));
+    CK(hipMalloc(&bias, sizeof(float) * 4 * H));
+    CK(hipMemset(x, 0, sizeof(float) * rows * 80));
+    CK(hipMemset(wih, 0, sizeof(float) * 2 * 4 * H * 80));
+    CK(hipMemset(bias, 0, sizeof(float) * 4 * H));
+    pf.x = x; pf.xs_s = N * 80; pf.xs_n = 80;
+    for (int d = 0; d < 2; ++d) { pf.wih[d] = wih + d * 4 * H * 80; pf.bih[d] = bias; pf.bhh[d] = bias; }
+  }
   const int chF = (int)((N + 16 * nbF - 1) / (16 * nbF)), chB = (int)((N + 15) / 16);
 
   float ms; int status;
@@ -127,7 +140,9 @@ int main(int argc, char** argv) {
     CK(hipMemsetD32Async((hipDeviceptr_t)hx, (int)PERSIST_SENTINEL, (size_t)(2 * S * NpF * H), st));
     CK(hipEventRecord(e0, st));
     const dim3 gridF = dim3(H / 4, 2, chF);
-    if (nbF == 1) hipLaunchKernelGGL((lstm_enc_fwd_persistent_kernel<4, 1>), gridF, dim3(FWD_THREADS), 0, st, pf);
+    if (fused && nbF == 1) hipLaunchKernelGGL((lstm_enc_fwd_persistent_kernel<4, 1, 5>), gridF, dim3(FWD_THREADS), 0, st, pf);
+    else if (fused) hipLaunchKernelGGL((lstm_enc_fwd_persistent_kernel<4, 2, 5>), gridF, dim3(FWD_THREADS), 0, st, pf);
+    else if (nbF == 1) hipLaunchKernelGGL((lstm_enc_fwd_persistent_kernel<4, 1>), gridF, dim3(FWD_THREADS), 0, st, pf);
     else hipLaunchKernelGGL((lstm_enc_fwd_persistent_kernel<4, 2>), gridF, dim3(FWD_THREADS), 0, st, pf);
     CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
     CK(hipEventElapsedTime(&ms, e0, e1));
@@ -138,6 +153,7 @@ int main(int argc, char** argv) {
   // not exact, so calibrate s_memtime against the wall clock with a sleep kernel instead
   double us_per_tick = 0.01;   // 100 MHz
   if (report("fwd", (int)(H / 4) * 2 * chF, us_per_tick, (int)(H / 4))) return 1;
+  if (getenv("FWD_ONLY")) return 0;
   CK(hipMemset(gates, 0, sizeof(float) * 2 * rows * 4 * H));
   for (int rep = 0; rep < 3; ++rep) {
     CK(hipMemsetAsync(sync, 0, 32, st));

@@ -39,9 +39,10 @@ static int persist_delay(int opt, int dflt) {
 // A persistent grid is only launched when every workgroup of it can be resident at once on this
 // device (occupancy query x CU count, ssasr_resident_capacity): its workgroups wait for each other,
 // and one that is queued behind the others would never start.  capacity 0 = no device / unknown.
-static bool grid_fits(const void* kernel, int threads, size_t dyn_lds, int64_t workgroups) {
+template <class P>
+static bool grid_fits(void (*kernel)(P), int threads, size_t dyn_lds, int64_t workgroups) {
   if (ssasr_options().no_residency_check) return true;
-  const int64_t cap = ssasr_resident_capacity(kernel, threads, dyn_lds);
+  const int64_t cap = ssasr_resident_capacity(reinterpret_cast<const void*>(kernel), threads, dyn_lds);
   return cap <= 0 || workgroups <= cap;
 }
 
@@ -54,35 +55,65 @@ constexpr int64_t PERSIST_WINDOW = 128;
 static int64_t window_count(int64_t N) { return (N + PERSIST_WINDOW - 1) / PERSIST_WINDOW; }
 static int64_t window_width(int64_t N, int64_t w) { return std::min<int64_t>(PERSIST_WINDOW, N - w * PERSIST_WINDOW); }
 
-// forward kernel instance for k-blocks per wave kpw (H / 64), nb x 16 columns per workgroup, fused first-layer input
-static const void* fwd_fn(int kpw, int nb, bool fuse) {
-#define SSASR_FN(K, NBT) reinterpret_cast<const void*>(lstm_enc_fwd_persistent_kernel<K, NBT>)
-  if (fuse) return nb == 1 ? reinterpret_cast<const void*>(lstm_enc_fwd_persistent_kernel<4, 1, 5>)
-                           : reinterpret_cast<const void*>(lstm_enc_fwd_persistent_kernel<4, 2, 5>);
-  return nb == 1 ? (kpw == 1 ? SSASR_FN(1, 1) : kpw == 2 ? SSASR_FN(2, 1) : kpw == 4 ? SSASR_FN(4, 1) : SSASR_FN(8, 1))
-                 : (kpw == 1 ? SSASR_FN(1, 2) : kpw == 2 ? SSASR_FN(2, 2) : kpw == 4 ? SSASR_FN(4, 2) : SSASR_FN(8, 2));
-#undef SSASR_FN
+// Element offsets of a layer's buffers at a window's first column n0 (a multiple of 16): a window's launch takes
+// the layer's pointers advanced by these and the layer's width as their row stride (EncPersist::nt).
+struct WindowOffsets { int64_t cols, gates, state, tsave; };    // lens (x stride: x, y, dy) | gates | cs, hs, dc_state | tsave
+static WindowOffsets window_offsets(int64_t n0, int64_t H) { return {n0, n0 * 4 * H, n0 * H, (n0 / 16) * (H / 16) * 5 * 256}; }
+template <class T> static T* at(T* p, int64_t off) { return p ? p + off : nullptr; }    // optional buffers stay null
+
+// THE forward kernel instance for k-blocks per wave kpw (H / 64), nb x 16 columns per workgroup, fused first-layer
+// input: the residency check and the launch both take it from here
+using FwdKernel = void (*)(EncPersist);
+static FwdKernel fwd_kernel(int kpw, int nb, bool fuse) {
+  if (fuse) { if (nb == 1) return lstm_enc_fwd_persistent_kernel<4, 1, 5>; return lstm_enc_fwd_persistent_kernel<4, 2, 5>; }
+  switch (kpw) {
+    case 1: if (nb == 1) return lstm_enc_fwd_persistent_kernel<1, 1>; return lstm_enc_fwd_persistent_kernel<1, 2>;
+    case 2: if (nb == 1) return lstm_enc_fwd_persistent_kernel<2, 1>; return lstm_enc_fwd_persistent_kernel<2, 2>;
+    case 4: if (nb == 1) return lstm_enc_fwd_persistent_kernel<4, 1>; return lstm_enc_fwd_persistent_kernel<4, 2>;
+    default: if (nb == 1) return lstm_enc_fwd_persistent_kernel<8, 1>; return lstm_enc_fwd_persistent_kernel<8, 2>;
+  }
 }
-static void fwd_launch(int kpw, int nb, bool fuse, dim3 grid, hipStream_t st, const EncPersist& p) {
-  const dim3 block(FWD_THREADS);
-#define SSASR_L(K, NBT) hipLaunchKernelGGL((lstm_enc_fwd_persistent_kernel<K, NBT>), grid, block, 0, st, p)
-  if (fuse && nb == 1) hipLaunchKernelGGL((lstm_enc_fwd_persistent_kernel<4, 1, 5>), grid, block, 0, st, p);
-  else if (fuse) hipLaunchKernelGGL((lstm_enc_fwd_persistent_kernel<4, 2, 5>), grid, block, 0, st, p);
-  else if (nb == 1) { if (kpw == 1) SSASR_L(1, 1); else if (kpw == 2) SSASR_L(2, 1); else if (kpw == 4) SSASR_L(4, 1); else SSASR_L(8, 1); }
-  else { if (kpw == 1) SSASR_L(1, 2); else if (kpw == 2) SSASR_L(2, 2); else if (kpw == 4) SSASR_L(4, 2); else SSASR_L(8, 2); }
-#undef SSASR_L
-}
+
+// One column window of the persistent forward recurrence: columns [n0, n0 + Nw), Npw = Nw rounded up to whole
+// 128-byte lines of the exchange image, nb x 16 columns per workgroup, a grid of (H / 4, 2, chunks) workgroups.
+struct FwdWindow { int64_t n0, Nw, Npw, chunks, workgroups; int nb; };
 // 16 columns per workgroup spreads a window over twice the workgroups (shorter product, half the exchange read
 // per workgroup) when they all fit the chip at one per CU; else 32 columns
 static int fwd_nb(int64_t Nw, int64_t H) { return (H / 4) * 2 * ((Nw + 15) / 16) <= 256 ? 1 : 2; }
-static int64_t fwd_hx_floats_window(int64_t S, int64_t Nw, int64_t H) { return 2 * S * (H / 4) * ((Nw + 7) & ~(int64_t)7) * 4; }
+static FwdWindow fwd_window(int64_t N, int64_t H, int64_t w) {
+  FwdWindow f{};
+  f.n0 = w * PERSIST_WINDOW; f.Nw = window_width(N, w); f.Npw = (f.Nw + 7) & ~(int64_t)7;
+  f.nb = fwd_nb(f.Nw, H);
+  f.chunks = (f.Nw + 16 * f.nb - 1) / (16 * f.nb);
+  f.workgroups = (H / 4) * 2 * f.chunks;
+  return f;
+}
+static int64_t fwd_hx_floats_window(int64_t S, const FwdWindow& f, int64_t H) { return 2 * S * (H / 4) * f.Npw * 4; }
+
+// The shape half of the test for the persistent forward (S, N, H > 0): H and the switches allow it, and every
+// window's grid is within the kernel's limits and wholly resident (<= 2 workgroups per CU) for the instances asked
+// for -- the plain one and / or the one with the fused input projection.
+static bool fwd_windows_fit(int64_t S, int64_t N, int64_t H, bool plain, bool fused) {
+  const SsasrOptions& opt = ssasr_options();
+  const int kpw = (int)(H / 64);
+  if (H % 64 != 0 || !(kpw == 1 || kpw == 2 || kpw == 4 || kpw == 8) || opt.no_persistent ||
+      (opt.no_windows && N > PERSIST_WINDOW))
+    return false;
+  for (int64_t w = 0; w < window_count(N); ++w) {
+    const FwdWindow f = fwd_window(N, H, w);
+    if (f.workgroups > 512 || S * f.Npw * H * 4 >= (1ll << 31)) return false;
+    if (plain && !grid_fits(fwd_kernel(kpw, f.nb, false), FWD_THREADS, 0, f.workgroups)) return false;
+    if (fused && !grid_fits(fwd_kernel(kpw, f.nb, true), FWD_THREADS, 0, f.workgroups)) return false;
+  }
+  return true;
+}
 
 // Floats of the forward recurrence's exchange images, one [2][S][H/4][Np][4] per column window back to back,
 // Np = the window's columns rounded up to whole 128-byte lines (0: the shape has no persistent form).
 extern "C" int64_t ssasr_bilstm_fwd_hx_floats(int64_t S, int64_t N, int64_t H) {
   if (S <= 0 || N <= 0 || H <= 0 || H % 64 != 0 || (ssasr_options().no_windows && N > PERSIST_WINDOW)) return 0;
   int64_t total = 0;
-  for (int64_t w = 0; w < window_count(N); ++w) total += fwd_hx_floats_window(S, window_width(N, w), H);
+  for (int64_t w = 0; w < window_count(N); ++w) total += fwd_hx_floats_window(S, fwd_window(N, H, w), H);
   return total;
 }
 
@@ -140,25 +171,16 @@ extern "C" int ssasr_bilstm_fwd(const float* x, int64_t xs_s, int64_t xs_n, int6
   {
     const int kpw = (int)(H / 64);
     const int64_t nwin = window_count(N);
-    bool fits = hx && sync_ws && H % 64 == 0 && (kpw == 1 || kpw == 2 || kpw == 4 || kpw == 8) &&
-                aligned16(hx) && aligned16(gates) && aligned16(cs) && aligned16(y) && ys_s % 4 == 0 &&
-                ys_n % 4 == 0 && !opt.no_persistent && !(opt.no_windows && nwin > 1);
+    bool fits = hx && sync_ws && aligned16(hx) && aligned16(gates) && aligned16(cs) && aligned16(y) && ys_s % 4 == 0 &&
+                ys_n % 4 == 0;
     // status words are zero on entry (caller's contract)
     // narrow input (the 80 mel bins of the first layer): the recurrence waves form the
     // pre-activations themselves; no input projection GEMM (rnn_kernels.h, KI)
     bool fuse_in = fits && kpw == 4 && I == 80 && bih[0] && bhh[0] && bih[1] && bhh[1] &&
                    aligned16(x) && aligned16(w_ih_f) && aligned16(w_ih_r) && xs_s % 4 == 0 && xs_n % 4 == 0 &&
                    !opt.no_fused_input;
-    // every window's kernel instance must have its whole grid resident (<= 2 workgroups per CU)
-    for (int64_t w = 0; w < nwin && fits; ++w) {
-      const int64_t Nw = window_width(N, w), Npw = (Nw + 7) & ~(int64_t)7;
-      const int nb = fwd_nb(Nw, H);
-      const int64_t chunks = (Nw + 16 * nb - 1) / (16 * nb);
-      if ((H / 4) * 2 * chunks > 512 || S * Npw * H * 4 >= (1ll << 31) ||
-          !grid_fits(fwd_fn(kpw, nb, fuse_in), FWD_THREADS, 0, (H / 4) * 2 * chunks)) {
-        fits = false; fuse_in = false;
-      }
-    }
+    // every window's grid must be resident for the instance that is launched
+    if (!(fits && fwd_windows_fit(S, N, H, !fuse_in, fuse_in))) fits = fuse_in = false;
     // tile-major saves exist in the persistent form only: a caller that passes the buffer was told
     // by ssasr_bilstm_tsave_floats that this shape takes it
     if (tsave && !fits) return SSASR_EARG;
@@ -171,24 +193,24 @@ extern "C" int ssasr_bilstm_fwd(const float* x, int64_t xs_s, int64_t xs_n, int6
         SSASR_HIP(hipMemsetD32Async((hipDeviceptr_t)hx, (int)PERSIST_SENTINEL, (size_t)ssasr_bilstm_fwd_hx_floats(S, N, H), st));
       float* hxw = hx;
       for (int64_t w = 0; w < nwin; ++w) {
-        const int64_t n0 = w * PERSIST_WINDOW, Nw = window_width(N, w);
-        const int nb = fwd_nb(Nw, H);
-        const int64_t chunks = (Nw + 16 * nb - 1) / (16 * nb);
+        const FwdWindow f = fwd_window(N, H, w);
+        const WindowOffsets o = window_offsets(f.n0, H);
         EncPersist p{};
         // (the pointers of a window start at its first column; nt = the layer's width = their row stride)
-        p.tsave = tsave ? tsave + (n0 / 16) * (H / 16) * 5 * 256 : nullptr;
+        p.tsave = at(tsave, o.tsave);
         p.drop_tile = opt.test_drop_tile;
         p.whh[0] = w_hh_f; p.whh[1] = w_hh_r;
-        p.x = x + n0 * xs_n; p.xs_s = xs_s; p.xs_n = xs_n;
+        p.x = x + o.cols * xs_n; p.xs_s = xs_s; p.xs_n = xs_n;
         for (int d = 0; d < 2; ++d) { p.wih[d] = wih[d]; p.bih[d] = bih[d]; p.bhh[d] = bhh[d]; }
-        p.gates = gates + n0 * 4 * H; p.cs = cs ? cs + n0 * H : nullptr; p.hs = hs + n0 * H; p.hx = hxw;
-        p.y = y + n0 * ys_n; p.lens = lens ? lens + n0 : nullptr;
+        p.gates = gates + o.gates; p.cs = at(cs, o.state); p.hs = hs + o.state; p.hx = hxw;
+        p.y = y + o.cols * ys_n; p.lens = at(lens, o.cols);
         p.status = sync_ws + 4;
         p.delay = persist_delay(opt.delay_fwd, 24);
-        p.ys_s = (int)ys_s; p.ys_n = (int)ys_n; p.S = (int)S; p.N = (int)Nw; p.H = (int)H;
+        p.ys_s = (int)ys_s; p.ys_n = (int)ys_n; p.S = (int)S; p.N = (int)f.Nw; p.H = (int)H;
         p.nt = nwin > 1 ? (int)N : 0;
-        fwd_launch(kpw, nb, fuse_in, dim3((unsigned)(H / 4), 2, (unsigned)chunks), st, p);   // 4 recurrence waves + the helper
-        hxw += fwd_hx_floats_window(S, Nw, H);
+        hipLaunchKernelGGL(fwd_kernel(kpw, f.nb, fuse_in), dim3((unsigned)(H / 4), 2, (unsigned)f.chunks),
+                           dim3(FWD_THREADS), 0, st, p);   // 4 recurrence waves + the helper
+        hxw += fwd_hx_floats_window(S, f, H);
       }
       SSASR_LAUNCH_CHECK();
       return SSASR_OK;
@@ -209,54 +231,54 @@ extern "C" int ssasr_bilstm_fwd(const float* x, int64_t xs_s, int64_t xs_n, int6
 // The shape half of ssasr_bilstm_fwd's test for its persistent form (the pointer-alignment half is
 // the caller's: torch allocations are 256-byte aligned), residency of the grid included.
 static bool fwd_persistent_shape_ok(int64_t S, int64_t N, int64_t H) {
-  const SsasrOptions& opt = ssasr_options();
-  if (S <= 0 || N <= 0 || H <= 0 || H % 64 != 0 || opt.no_persistent || (opt.no_windows && N > PERSIST_WINDOW)) return false;
-  const int kpw = (int)(H / 64);
-  if (!(kpw == 1 || kpw == 2 || kpw == 4 || kpw == 8)) return false;
-  for (int64_t w = 0; w < window_count(N); ++w) {
-    const int64_t Nw = window_width(N, w), Npw = (Nw + 7) & ~(int64_t)7;
-    const int nb = fwd_nb(Nw, H);
-    const int64_t chunks = (Nw + 16 * nb - 1) / (16 * nb);
-    if ((H / 4) * 2 * chunks > 512 || S * Npw * H * 4 >= (1ll << 31)) return false;
-    if (!grid_fits(fwd_fn(kpw, nb, false), FWD_THREADS, 0, (H / 4) * 2 * chunks)) return false;
-    // the first layer's variant (fused input projection) is the larger kernel
-    if (kpw == 4 && !grid_fits(fwd_fn(kpw, nb, true), FWD_THREADS, 0, (H / 4) * 2 * chunks)) return false;
-  }
-  return true;
+  // the first layer's variant (fused input projection, H = 256) is the larger kernel
+  return S > 0 && N > 0 && H > 0 && fwd_windows_fit(S, N, H, true, H / 64 == 4);
+}
+
+// Geometry of the K-split persistent BPTT: one workgroup per (16-unit tile, direction, 16-column chunk) of a column
+// window, and a ring of BWD_RS_RING steps of partial dh tiles per (direction, chunk) (rnn_kernels.h); the windows'
+// rings lie back to back, dirs x chunks of the window each (N = a window's first column: the floats in front of it).
+static int64_t bptt_ring_floats(int64_t N, int64_t H, int64_t dirs) {
+  return dirs * ((N + 15) / 16) * BWD_RS_RING * (H / 16) * (H / 16) * 256;
+}
+static int64_t bptt_workgroups(int64_t Nw, int64_t H, int dirs) { return (H / 16) * dirs * ((Nw + 15) / 16); }
+// every workgroup of a window must be resident: at most one per CU (the widest window is the first)
+static bool bptt_grid_ok(int64_t N, int64_t H, int dirs) {
+  return bptt_workgroups(std::min<int64_t>(N, PERSIST_WINDOW), H, dirs) <= 256;
 }
 
 // Exchange workspace of the persistent BPTT: the K-split form's ring (0: no persistent form for this shape).
 extern "C" int64_t ssasr_bilstm_bwd_gx_floats(int64_t S, int64_t N, int64_t H) {
   if (S <= 0 || N <= 0 || (H != 64 && H != 128 && H != 256)) return 0;
-  const int64_t chunks = (N + 15) / 16;
-  return 2 * chunks * BWD_RS_RING * (H / 16) * (H / 16) * 256;
+  return bptt_ring_floats(N, H, 2);
 }
 
 // Floats of the ring, 0 when the shape (or the environment) does not take the persistent form:
 // what a caller that arms several exchange workspaces with one fill has to reserve.
 extern "C" int64_t ssasr_bilstm_bwd_ring_floats(int64_t S, int64_t N, int64_t H, int64_t dirs) {
   if (dirs < 1 || dirs > 2 || !ssasr_bptt_ksplit_ok(S, N, H, (int)dirs)) return 0;
-  return dirs * ((N + 15) / 16) * BWD_RS_RING * (H / 16) * (H / 16) * 256;
+  return bptt_ring_floats(N, H, dirs);
 }
 
-// the K-split kernel instance for H (and halves), for the residency check and the launch
-static const void* bptt_rs_fn(int kpw, bool halves) {
-  if (kpw == 4) return reinterpret_cast<const void*>(lstm_enc_bwd_rs_kernel<1, 1>);
-  if (kpw == 8) return halves ? reinterpret_cast<const void*>(lstm_enc_bwd_rs_kernel<2, 2>)
-                              : reinterpret_cast<const void*>(lstm_enc_bwd_rs_kernel<2, 1>);
-  return halves ? reinterpret_cast<const void*>(lstm_enc_bwd_rs_kernel<4, 2>)
-                : reinterpret_cast<const void*>(lstm_enc_bwd_rs_kernel<4, 1>);
+// THE K-split kernel instance for tiles per wave x 4 = kpw (H / 16) and halves: the residency check, the LDS
+// reservation and the launch all take it from here
+using BpttKernel = void (*)(EncPersistBwd);
+static BpttKernel bptt_kernel(int kpw, bool halves) {
+  if (kpw == 4) return lstm_enc_bwd_rs_kernel<1, 1>;
+  if (kpw == 8) { if (halves) return lstm_enc_bwd_rs_kernel<2, 2>; return lstm_enc_bwd_rs_kernel<2, 1>; }
+  if (halves) return lstm_enc_bwd_rs_kernel<4, 2>;
+  return lstm_enc_bwd_rs_kernel<4, 1>;
 }
 
 // Dynamic LDS the launch of THAT instance reserves (and never touches) so that no side-stream GEMM workgroup
-// fits beside it on its CU (see "Placement" in ssasr_launch_bptt_persistent).  The option gives the size
+// fits beside it on its CU (see "Placement" in launch_bptt_window).  The option gives the size
 // (SSASR_BPTT_RESERVE_KB, 0 = off); it is RAISED to what the invariant needs -- the instance's own static LDS +
 // reservation + the smallest GEMM workgroup's LDS > 160 KB -- and the instance is the one that is launched:
 // HV = 1 and HV = 2 keep different numbers of gate-derivative stages in LDS.
-static int bptt_reserve_bytes(int kpw, bool halves) {
+static int bptt_reserve_bytes(BpttKernel kernel) {
   int reserve = ssasr_options().bptt_reserve_kb * 1024;
   if (reserve) {
-    const size_t need = ssasr_lds_reservation_against_gemm(bptt_rs_fn(kpw, halves));
+    const size_t need = ssasr_lds_reservation_against_gemm(reinterpret_cast<const void*>(kernel));
     if ((size_t)reserve < need) reserve = (int)need;
   }
   return reserve;
@@ -271,53 +293,36 @@ extern "C" int64_t ssasr_bilstm_tsave_floats(int64_t S, int64_t N, int64_t H) {
 
 bool ssasr_bptt_ksplit_ok(int64_t S, int64_t N, int64_t H, int dirs) {
   const SsasrOptions& opt = ssasr_options();
-  // (per column window: the widest is the first)
-  const int64_t chunks = (std::min<int64_t>(N, PERSIST_WINDOW) + 15) / 16;
-  if (!(S > 0 && N > 0 && (H == 64 || H == 128 || H == 256) && (H / 16) * dirs * chunks <= 256 && !opt.no_persistent) ||
+  if (!(S > 0 && N > 0 && (H == 64 || H == 128 || H == 256) && bptt_grid_ok(N, H, dirs) && !opt.no_persistent) ||
       (opt.no_windows && N > PERSIST_WINDOW))
     return false;
   // every workgroup of the one-per-(tile, chunk) grid must be resident (the two-halves grid is checked at launch)
-  const int kpw = (int)(H / 16);
-  return grid_fits(bptt_rs_fn(kpw, false), 320, (size_t)bptt_reserve_bytes(kpw, false), (H / 16) * dirs * chunks);
+  const BpttKernel kernel = bptt_kernel((int)(H / 16), false);
+  return grid_fits(kernel, 320, (size_t)bptt_reserve_bytes(kernel), bptt_workgroups(std::min<int64_t>(N, PERSIST_WINDOW), H, dirs));
 }
 
-// One column window [n0, n0 + Nw) of a layer of NT columns (NT = 0: the launch covers the layer, Nw = its width)
 // progress words of a one-launch layer: words[k] receives one count per row-writing workgroup when iteration bound[k] - 1 is done
 struct BpttProgress { unsigned* words; int n; int bound[7]; };
 
-static int launch_bptt_window(const float* whhT, float* gates, const float* cs, const float* dy, int64_t ys_s,
-                              int64_t ys_n, const int32_t* lens, float* gx, int32_t* sync_ws, int64_t S, int64_t Nw,
-                              int64_t NT, int64_t H, int dirs, hipStream_t st, int64_t i0, int64_t i1, float* dc_state,
-                              const float* whh_f, const float* whh_r, const float* tsave, void* stop_event,
-                              const BpttProgress* prog = nullptr) {
-  const int64_t chunks = (Nw + 15) / 16;
-  const int kpw = (int)(H / 16);
-  const SsasrOptions& opt = ssasr_options();
-  const bool ranged = i0 != 0 || i1 != S;
-  EncPersistBwd p{};
-  p.i0 = (int)i0; p.i1 = (int)i1; p.dc_state = dc_state;
-  if (whh_f && (dirs == 1 || whh_r)) { p.whh[0] = whh_f; p.whh[1] = whh_r; }
-  p.whhT = whhT; p.gates = gates; p.cs = cs; p.dy = dy; p.gx = gx; p.lens = lens; p.tsave = tsave;
-  p.status = sync_ws + 4;
-  p.delay = persist_delay(opt.delay_bwd_ksplit, 40);
-  p.ys_s = (int)ys_s; p.ys_n = (int)ys_n; p.S = (int)S; p.N = (int)Nw; p.H = (int)H; p.nt = (int)NT;
-  if (prog) {
-    p.progress = prog->words; p.nbound = prog->n;
-    for (int k = 0; k < prog->n; ++k) p.bound[k] = prog->bound[k];
-  }
-  dim3 pgrid((unsigned)(H / 16), (unsigned)dirs, (unsigned)chunks), pblock(320);   // 4 recurrence waves + 1 helper
+// One column window of a layer: p holds the window's pointers, its width p.N and the layer's width p.nt (0: the
+// launch covers the layer), and iterations [p.i0, p.i1) of the p.S steps.
+static int launch_bptt_window(const EncPersistBwd& p, int dirs, hipStream_t st, void* stop_event) {
+  const int kpw = p.H / 16;
+  const int64_t workgroups = bptt_workgroups(p.N, p.H, dirs);
+  const bool ranged = p.i0 != 0 || p.i1 != p.S;
   // two workgroups per (unit tile, chunk) halve the product on the critical path (H >= 128)
   // (not for launches of fewer than three steps: see the note on in-place rows in rnn_kernels.h)
-  bool halves = kpw >= 8 && (H / 16) * dirs * chunks * 2 <= 256 && i1 - i0 >= 3 && !opt.bptt_halves_off;
-  int reserve = bptt_reserve_bytes(kpw, halves);
-  if (halves && !grid_fits(bptt_rs_fn(kpw, true), 320, (size_t)reserve, (H / 16) * dirs * chunks * 2)) {
+  bool halves = kpw >= 8 && workgroups * 2 <= 256 && p.i1 - p.i0 >= 3 && !ssasr_options().bptt_halves_off;
+  BpttKernel kernel = bptt_kernel(kpw, halves);
+  int reserve = bptt_reserve_bytes(kernel);
+  if (halves && !grid_fits(kernel, 320, (size_t)reserve, workgroups * 2)) {
     halves = false;
-    reserve = bptt_reserve_bytes(kpw, false);
+    kernel = bptt_kernel(kpw, false);
+    reserve = bptt_reserve_bytes(kernel);
   }
-  if (!halves && !grid_fits(bptt_rs_fn(kpw, false), 320, (size_t)reserve, (H / 16) * dirs * chunks)) return SSASR_EARG;
-  if (halves) pgrid.z *= 2;
+  if (!halves && !grid_fits(kernel, 320, (size_t)reserve, workgroups)) return SSASR_EARG;
   // (a range shorter than the hand-off distance between the two halves could rewrite dc_state early)
-  if (halves && ranged && i1 < S && i1 - i0 < 4) return SSASR_EARG;
+  if (halves && ranged && p.i1 < p.S && p.i1 - p.i0 < 4) return SSASR_EARG;
   // Placement: the weight-gradient GEMMs of the previous range / layer run beside this kernel on
   // the second stream.  A GEMM workgroup that shares a CU with a recurrence workgroup slows every
   // step of it (shared MFMA pipe, LDS and memory pipeline): 2.4 -> 3.3 us per step.  The launch
@@ -326,17 +331,12 @@ static int launch_bptt_window(const float* whhT, float* gates, const float* cs, 
   // its standalone speed (+4-5 % on the train step).  SSASR_BPTT_SHARED_CU=1 turns it off.
   // (the attribute is a property of the loaded code object: setting it again is idempotent and costs
   // no device work)
-  if (reserve) SSASR_HIP(hipFuncSetAttribute(bptt_rs_fn(kpw, halves), hipFuncAttributeMaxDynamicSharedMemorySize, reserve));
+  if (reserve)
+    SSASR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, reserve));
   // stop_event: the range's completion event rides on the dispatch's own completion signal instead of a
   // hipEventRecord behind it (a barrier packet between two ranges cost 6-7 us of idle stream each)
-  hipEvent_t stop = (hipEvent_t)stop_event;
-#define SSASR_RS_LAUNCH(TPW_, HV_) hipExtLaunchKernelGGL((lstm_enc_bwd_rs_kernel<TPW_, HV_>), pgrid, pblock, (unsigned)reserve, st, nullptr, stop, 0u, p)
-  if (kpw == 4) SSASR_RS_LAUNCH(1, 1);
-  else if (kpw == 8 && halves) SSASR_RS_LAUNCH(2, 2);
-  else if (kpw == 8) SSASR_RS_LAUNCH(2, 1);
-  else if (halves) SSASR_RS_LAUNCH(4, 2);
-  else SSASR_RS_LAUNCH(4, 1);
-#undef SSASR_RS_LAUNCH
+  const dim3 grid((unsigned)(p.H / 16), (unsigned)dirs, (unsigned)((p.N + 15) / 16 * (halves ? 2 : 1)));
+  hipExtLaunchKernelGGL(kernel, grid, dim3(320), (unsigned)reserve, st, nullptr, (hipEvent_t)stop_event, 0u, p);   // 4 recurrence waves + 1 helper
   SSASR_LAUNCH_CHECK();
   return SSASR_OK;
 }
@@ -350,55 +350,85 @@ int ssasr_launch_bptt_persistent(const float* whhT, float* gates, const float* c
   if (i1 <= 0) i1 = S;
   const bool ranged = i0 != 0 || i1 != S;
   if (i0 < 0 || i0 >= i1 || i1 > S || (ranged && !dc_state)) return SSASR_EARG;
-  const int64_t wchunks = (std::min<int64_t>(N, PERSIST_WINDOW) + 15) / 16;
-  // every workgroup of a window must be resident: at most one per CU
   if ((!whhT && !whh_f) || !gx || !sync_ws || !(kpw == 4 || kpw == 8 || kpw == 16) || dirs < 1 || dirs > 2 ||
-      (H / 16) * dirs * wchunks > 256 || !aligned16(gx) || !aligned16(gates) ||
+      !bptt_grid_ok(N, H, dirs) || !aligned16(gx) || !aligned16(gates) ||
       (!tsave && !aligned16(cs)) || !aligned16(dy) || ys_s % 4 || ys_n % 4 || ys_s >= (1ll << 31) || ys_n >= (1ll << 31))
     return SSASR_EARG;
-  // ring of BWD_RS_RING steps of partial dh tiles per (direction, 16-column chunk) (rnn_kernels.h); the windows'
-  // rings lie back to back, dirs x chunks of the window each
-  const size_t ring_chunk = (size_t)BWD_RS_RING * (H / 16) * (H / 16) * 256;   // floats
   if (i0 == 0 && !armed)
-    SSASR_HIP(hipMemsetD32Async((hipDeviceptr_t)gx, (int)PERSIST_SENTINEL, (size_t)dirs * ((N + 15) / 16) * ring_chunk, st));
+    SSASR_HIP(hipMemsetD32Async((hipDeviceptr_t)gx, (int)PERSIST_SENTINEL, (size_t)bptt_ring_floats(N, H, dirs), st));
   const int64_t nwin = window_count(N);
+  EncPersistBwd layer{};
+  layer.i0 = (int)i0; layer.i1 = (int)i1;
+  if (whh_f && (dirs == 1 || whh_r)) { layer.whh[0] = whh_f; layer.whh[1] = whh_r; }
+  layer.whhT = whhT;
+  layer.status = sync_ws + 4;
+  layer.delay = persist_delay(ssasr_options().delay_bwd_ksplit, 40);
+  layer.ys_s = (int)ys_s; layer.ys_n = (int)ys_n; layer.S = (int)S; layer.H = (int)H;
+  layer.nt = nwin > 1 ? (int)N : 0;
+  if (progress && nwin == 1) {
+    const BpttProgress* prog = static_cast<const BpttProgress*>(progress);
+    layer.progress = prog->words; layer.nbound = prog->n;
+    for (int k = 0; k < prog->n; ++k) layer.bound[k] = prog->bound[k];
+  }
   for (int64_t w = 0; w < nwin; ++w) {
-    // (the pointers of a window start at its first column; NT = the layer's width = their row stride)
-    const int64_t n0 = w * PERSIST_WINDOW, Nw = window_width(N, w);
-    const int rc = launch_bptt_window(whhT, gates + n0 * 4 * H, cs ? cs + n0 * H : nullptr, dy + n0 * ys_n, ys_s, ys_n,
-                                      lens ? lens + n0 : nullptr, gx + (size_t)dirs * (n0 / 16) * ring_chunk, sync_ws, S, Nw,
-                                      nwin > 1 ? N : 0, H, dirs, st, i0, i1, dc_state ? dc_state + n0 * H : nullptr, whh_f, whh_r,
-                                      tsave ? tsave + (n0 / 16) * (H / 16) * 5 * 256 : nullptr,
-                                      w == nwin - 1 ? stop_event : nullptr,
-                                      nwin == 1 ? static_cast<const BpttProgress*>(progress) : nullptr);
+    // (the pointers of a window start at its first column; nt = the layer's width = their row stride)
+    const int64_t n0 = w * PERSIST_WINDOW;
+    const WindowOffsets o = window_offsets(n0, H);
+    EncPersistBwd p = layer;
+    p.N = (int)window_width(N, w);
+    p.gates = gates + o.gates; p.cs = at(cs, o.state); p.dy = dy + o.cols * ys_n; p.lens = at(lens, o.cols);
+    p.gx = gx + bptt_ring_floats(n0, H, dirs); p.dc_state = at(dc_state, o.state); p.tsave = at(tsave, o.tsave);
+    const int rc = launch_bptt_window(p, dirs, st, w == nwin - 1 ? stop_event : nullptr);
     if (rc) return rc;
   }
   return SSASR_OK;
 }
 
+// input gradient (critical path: the layer below needs it): dX = dG_f W_ih_f + dG_r W_ih_r.  On the
+// split-bf16 kernel both directions are the two K segments of ONE launch (GemmDesc::kcat): dX is written
+// once instead of written, read back and written again, and the second launch's tail is gone
+static int launch_input_grad(const float* dgates, const float* w_ih_f, const float* w_ih_r, float* dx, int64_t dxs_s,
+                             int64_t dxs_n, int64_t S, int64_t N, int64_t I, int64_t H, hipStream_t st) {
+  if (!dx) return SSASR_OK;
+  const int64_t rows = S * N;
+  const bool kcat = ssasr_options().gemm_x6 != 0 && ssasr_options().gemm_kcat != 0 && (4 * H) % 32 == 0;
+  for (int d = 0; d < (kcat ? 1 : 2); ++d) {
+    GemmDesc g{};
+    g.A = dgates + d * rows * 4 * H; g.ma = rm_dense(4 * H);
+    g.B = d ? w_ih_r : w_ih_f; g.mb = rm_dense(I);
+    g.C = dx; g.mc = RowMap{0, N, dxs_s, dxs_n};
+    g.M = (int)rows; g.N = (int)I; g.K = (int)(4 * H);
+    g.ta = 0; g.tb = 1; g.alpha = 1.f; g.beta = d ? 1.f : 0.f; g.splitk = 1; g.batch = 1;
+    if (kcat) { g.kcat = 2; g.ska = rows * 4 * H; g.skb = w_ih_r - w_ih_f; }
+    const int rc = ssasr_launch_gemm(g, st);
+    if (rc) return rc;
+  }
+  return SSASR_OK;
+}
+
+// the arguments every form of the layer's backward needs
+static bool bwd_args_ok(int64_t S, int64_t N, int64_t I, int64_t H, const float* dy, const float* x, const float* gates,
+                        const float* cs, const float* tsave, const float* hs, const float* ws_whhT, const float* ws_dc) {
+  return S > 0 && N > 0 && I > 0 && H > 0 && H % 16 == 0 && dy && x && gates && (cs || tsave) && hs && ws_whhT && ws_dc;
+}
+
 // Backward of the layer.  `gates` is consumed: on return it holds the gate
-// pre-activation derivatives.  dw_* / db_* are overwritten.
-static int bilstm_bwd_impl(bool armed, const float* tsave, const float* dy, int64_t ys_s, int64_t ys_n, const float* x,
-                                int64_t xs_s, int64_t xs_n, int64_t S, int64_t N, int64_t I,
-                                int64_t H, const int32_t* lens, const float* w_ih_f,
-                                const float* w_hh_f, const float* w_ih_r, const float* w_hh_r,
-                                float* gates, const float* cs, const float* hs, float* dx,
-                                int64_t dxs_s, int64_t dxs_n, float* dw_ih_f, float* dw_hh_f,
-                                float* db_f, float* dw_ih_r, float* dw_hh_r, float* db_r,
-                                float* ws_whhT /* [2][H][4H] */, float* ws_dc /* [2][2][N][H] */,
-                                float* gx, int32_t* sync_ws, void* stream) {
-  if (S <= 0 || N <= 0 || I <= 0 || H <= 0 || H % 16 != 0) return SSASR_EARG;
-  if (!dy || !x || !gates || (!cs && !tsave) || !hs || !ws_whhT || !ws_dc) return SSASR_EARG;
+// pre-activation derivatives.  dw_* / db_* are overwritten (dw_ih_f null: the weight
+// gradients are deferred to ssasr_bilstm_wgrad).
+extern "C" int ssasr_bilstm_bwd(const float* dy, int64_t ys_s, int64_t ys_n, const float* x, int64_t xs_s,
+                                int64_t xs_n, int64_t S, int64_t N, int64_t I, int64_t H, const int32_t* lens,
+                                const float* w_ih_f, const float* w_hh_f, const float* w_ih_r, const float* w_hh_r,
+                                float* gates, const float* cs, const float* hs, float* dx, int64_t dxs_s,
+                                int64_t dxs_n, float* dw_ih_f, float* dw_hh_f, float* db_f, float* dw_ih_r,
+                                float* dw_hh_r, float* db_r, float* ws_whhT /* [2][H][4H] */,
+                                float* ws_dc /* [2][2][N][H] */, float* gx, int32_t* sync_ws, int armed,
+                                const float* tsave, void* stream) {
+  if (!bwd_args_ok(S, N, I, H, dy, x, gates, cs, tsave, hs, ws_whhT, ws_dc)) return SSASR_EARG;
   // the gate epilogue of the backward kernel uses 16-byte accesses
   if (!aligned16(dy) || !aligned16(gates) || (!tsave && !aligned16(cs)) || !aligned16(ws_dc) || ys_s % 4 || ys_n % 4)
     return SSASR_EARG;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t rows = S * N;
-  const float* wih[2] = {w_ih_f, w_ih_r};
   const float* whh[2] = {w_hh_f, w_hh_r};
-  float* dwih[2] = {dw_ih_f, dw_ih_r};
-  float* dwhh[2] = {dw_hh_f, dw_hh_r};
-  float* db[2] = {db_f, db_r};
   int rc;
 
   // the persistent kernel reads W_hh as it is; the per-step form wants the transposed copy
@@ -420,7 +450,7 @@ static int bilstm_bwd_impl(bool armed, const float* tsave, const float* dy, int6
   bool persistent = false;
   if (direct) {
     rc = ssasr_launch_bptt_persistent(nullptr, gates, cs, dy, ys_s, ys_n, lens, gx, sync_ws, S, N, H,
-                                      2, st, 0, 0, nullptr, w_hh_f, w_hh_r, armed, tsave);
+                                      2, st, 0, 0, nullptr, w_hh_f, w_hh_r, armed != 0, tsave);
     if (rc == SSASR_OK) persistent = true;
     else if (rc != SSASR_EARG) return rc;
   }
@@ -434,35 +464,10 @@ static int bilstm_bwd_impl(bool armed, const float* tsave, const float* dy, int6
     hipLaunchKernelGGL(lstm_enc_bwd_kernel, grid, block, 0, st, e, (int)i);
   SSASR_LAUNCH_CHECK();
 
-  // Input gradient (critical path: the layer below needs it).
-  const bool kcat = dx && ssasr_options().gemm_x6 != 0 && ssasr_options().gemm_kcat != 0 && (4 * H) % 32 == 0;      // both directions as the two K segments of one launch
-  for (int d = 0; d < (kcat ? 1 : 2) && dx; ++d) {
-    const float* dG = gates + d * rows * 4 * H;
-    GemmDesc g{};
-    g.A = dG; g.ma = rm_dense(4 * H);
-    g.B = wih[d]; g.mb = rm_dense(I);
-    g.C = dx; g.mc = RowMap{0, N, dxs_s, dxs_n};
-    g.M = (int)rows; g.N = (int)I; g.K = (int)(4 * H);
-    g.ta = 0; g.tb = 1; g.alpha = 1.f; g.beta = d ? 1.f : 0.f; g.splitk = 1; g.batch = 1;
-    if (kcat) { g.kcat = 2; g.ska = rows * 4 * H; g.skb = wih[1] - wih[0]; }
-    rc = ssasr_launch_gemm(g, st);
-    if (rc) return rc;
-  }
+  if ((rc = launch_input_grad(gates, w_ih_f, w_ih_r, dx, dxs_s, dxs_n, S, N, I, H, st))) return rc;
   if (!dw_ih_f) return SSASR_OK;      // weight gradients deferred to ssasr_bilstm_wgrad
   return ssasr_bilstm_wgrad(gates, x, xs_s, xs_n, hs, S, N, I, H, dw_ih_f, dw_hh_f, db_f, nullptr, dw_ih_r,
                             dw_hh_r, db_r, nullptr, 0, stream);
-}
-
-extern "C" int ssasr_bilstm_bwd(const float* dy, int64_t ys_s, int64_t ys_n, const float* x, int64_t xs_s,
-                                int64_t xs_n, int64_t S, int64_t N, int64_t I, int64_t H, const int32_t* lens,
-                                const float* w_ih_f, const float* w_hh_f, const float* w_ih_r, const float* w_hh_r,
-                                float* gates, const float* cs, const float* hs, float* dx, int64_t dxs_s,
-                                int64_t dxs_n, float* dw_ih_f, float* dw_hh_f, float* db_f, float* dw_ih_r,
-                                float* dw_hh_r, float* db_r, float* ws_whhT, float* ws_dc, float* gx,
-                                int32_t* sync_ws, int armed, const float* tsave, void* stream) {
-  return bilstm_bwd_impl(armed != 0, tsave, dy, ys_s, ys_n, x, xs_s, xs_n, S, N, I, H, lens, w_ih_f, w_hh_f, w_ih_r,
-                         w_hh_r, gates, cs, hs, dx, dxs_s, dxs_n, dw_ih_f, dw_hh_f, db_f, dw_ih_r, dw_hh_r, db_r,
-                         ws_whhT, ws_dc, gx, sync_ws, stream);
 }
 
 // Weight gradients of a layer from the gate derivatives left in `gates` by
@@ -530,47 +535,17 @@ extern "C" int ssasr_events_destroy(void* handle) {
 // two products and the column sums each streamed dG again, ~3 x its bytes on the stream that shares the memory
 // system with the BPTT): dG^T . [X | H_prev] as the two column segments of a split-bf16 GEMM launch
 // (GemmDesc::nseg), the bias gradients as column sums formed by the workgroups of the first column tile from
-// the dG rows they stream anyway.  nb = 1 (one direction: lo / hi / the outputs of index 0) or 2 (both
-// directions as the launch's two batches; ranges of equal length).  Returns SSASR_EARG when the form does not
-// apply (options, alignment): the caller then takes the separate launches.
-static int wgrad_fused(int nb, const int d_of[2], const int64_t lo[2], const int64_t hi[2], const float* dgates,
-                       const float* x, int64_t xs_s, int64_t xs_n, const float* hs, int64_t S, int64_t N, int64_t I,
-                       int64_t H, float* const dwih[2], float* const dwhh[2], float* const db[2], float* const db2[2],
-                       hipStream_t st) {
+// the dG rows they stream anyway.  seg[0 .. ns) are wgrad_range's products, nb its batches.  Returns SSASR_EARG
+// when the form does not apply (options, alignment): the caller then takes the separate launches.
+static int wgrad_fused(int nb, const GemmDesc::Seg seg[2], int ns, int64_t I, int64_t H, float* const db[2],
+                       float* const db2[2], hipStream_t st) {
   const SsasrOptions& opt = ssasr_options();
-  if (!opt.wgrad_fused || !opt.gemm_x6 || nb < 1 || nb > 2) return SSASR_EARG;
-  const int64_t rows = S * N;
-  if (hi[0] <= lo[0] || (nb == 2 && hi[1] - lo[1] != hi[0] - lo[0])) return SSASR_EARG;
-  // the recurrent product skips the step without a predecessor: s = 0 (forward) / s = S - 1 (reverse)
-  int64_t a0[2], a1[2];
-  for (int b = 0; b < nb; ++b) {
-    a0[b] = d_of[b] ? lo[b] : (lo[b] > 1 ? lo[b] : 1);
-    a1[b] = d_of[b] ? (hi[b] < S - 1 ? hi[b] : S - 1) : hi[b];
-  }
-  if (nb == 2 && a1[1] - a0[1] != a1[0] - a0[0]) return SSASR_EARG;
+  if (!opt.wgrad_fused || !opt.gemm_x6) return SSASR_EARG;
   GemmDesc g{};
   g.ma = rm_dense(4 * H);
   g.M = (int)(4 * H); g.ta = 1; g.tb = 1; g.alpha = 1.f; g.beta = 1.f; g.batch = nb;
-  int ns = 0;
-  {           // dW_ih[d] += dG_d[range]^T . X[range]
-    GemmDesc::Seg& sg = g.seg[ns++];
-    for (int b = 0; b < nb; ++b) {
-      sg.A[b] = dgates + d_of[b] * rows * 4 * H + lo[b] * N * 4 * H;
-      sg.B[b] = x + lo[b] * xs_s;
-      sg.C[b] = dwih[b];
-    }
-    sg.mb = RowMap{0, N, xs_s, xs_n}; sg.ldc = I; sg.N = (int)I; sg.K = (int)((hi[0] - lo[0]) * N);
-  }
-  if (a1[0] > a0[0]) {           // dW_hh[d] += sum_s dG_d[s]^T . h_d[s_prev]
-    GemmDesc::Seg& sg = g.seg[ns++];
-    for (int b = 0; b < nb; ++b) {
-      sg.A[b] = dgates + d_of[b] * rows * 4 * H + a0[b] * N * 4 * H;
-      sg.B[b] = hs + d_of[b] * rows * H + (d_of[b] ? a0[b] + 1 : a0[b] - 1) * N * H;
-      sg.C[b] = dwhh[b];
-    }
-    sg.mb = rm_dense(H); sg.ldc = H; sg.N = (int)H; sg.K = (int)((a1[0] - a0[0]) * N);
-  }
   g.nseg = ns;
+  for (int k = 0; k < ns; ++k) g.seg[k] = seg[k];
   for (int b = 0; b < nb; ++b) { g.colsum[b] = db[b]; g.colsum2[b] = db2[b]; }
   // K slices.  The products are compute bound and run beside a recurrence that keeps half of the CUs, i.e. on
   // ~512 workgroup slots (128 CUs x 4 workgroups of 64 x 64 tiles): a launch costs rounds x K steps per
@@ -591,117 +566,70 @@ static int wgrad_fused(int nb, const int d_of[2], const int64_t lo[2], const int
   return ssasr_launch_gemm(g, st);
 }
 
-// Weight / bias gradients of direction d from the time steps [s_lo, s_hi) only, added to the
-// outputs (which the caller zeroed if needed).
-static int wgrad_dir_range(int d, int64_t s_lo, int64_t s_hi, const float* dgates, const float* x, int64_t xs_s,
-                           int64_t xs_n, const float* hs, int64_t S, int64_t N, int64_t I, int64_t H,
-                           float* dwih, float* dwhh, float* db, float* db2, hipStream_t st) {
-  const int64_t rows = S * N;
-  const float* dG = dgates + d * rows * 4 * H;
-  int rc;
-  if (s_hi <= s_lo) return SSASR_OK;
-  {
-    const int d_of[2] = {d, d};
-    const int64_t lo[2] = {s_lo, s_lo}, hi[2] = {s_hi, s_hi};
-    float* const w1[2] = {dwih, nullptr};
-    float* const w2[2] = {dwhh, nullptr};
-    float* const b1[2] = {db, nullptr};
-    float* const b2[2] = {db2, nullptr};
-    rc = wgrad_fused(1, d_of, lo, hi, dgates, x, xs_s, xs_n, hs, S, N, I, H, w1, w2, b1, b2, st);
-    if (rc != SSASR_EARG) return rc;
-  }
-  {           // dW_ih += dG[s_lo:s_hi]^T . X[s_lo:s_hi]
-    GemmDesc g{};
-    g.A = dG + s_lo * N * 4 * H; g.ma = rm_dense(4 * H);
-    g.B = x + s_lo * xs_s; g.mb = RowMap{0, N, xs_s, xs_n};
-    g.C = dwih; g.mc = rm_dense(I);
-    g.M = (int)(4 * H); g.N = (int)I; g.K = (int)((s_hi - s_lo) * N);
-    g.ta = 1; g.tb = 1; g.alpha = 1.f; g.beta = 1.f; g.batch = 1;
-    const int64_t tiles = ((4 * H + 63) / 64) * ((I + 63) / 64);
-    int sk = (int)(512 / tiles); if (sk < 1) sk = 1; if (sk > 32) sk = 32;
-    if (g.K < 64 * sk) sk = 1;
-    g.splitk = sk;
-    if ((rc = ssasr_launch_gemm(g, st))) return rc;
-  }
-  {           // dW_hh += sum_s dG[s]^T . h[s_prev],  s_prev = s - 1 (forward direction) or s + 1 (reverse)
-    const int64_t a0 = d ? s_lo : (s_lo > 1 ? s_lo : 1);            // first s that has a predecessor in range
-    const int64_t a1 = d ? (s_hi < S - 1 ? s_hi : S - 1) : s_hi;
-    if (a1 > a0) {
-      GemmDesc g{};
-      g.A = dG + a0 * N * 4 * H; g.ma = rm_dense(4 * H);
-      g.B = hs + d * rows * H + (d ? a0 + 1 : a0 - 1) * N * H; g.mb = rm_dense(H);
-      g.C = dwhh; g.mc = rm_dense(H);
-      g.M = (int)(4 * H); g.N = (int)H; g.K = (int)((a1 - a0) * N);
-      g.ta = 1; g.tb = 1; g.alpha = 1.f; g.beta = 1.f; g.batch = 1;
-      const int64_t tiles = ((4 * H + 63) / 64) * ((H + 63) / 64);
-      int sk = (int)(512 / tiles); if (sk < 1) sk = 1; if (sk > 32) sk = 32;
-      if (g.K < 64 * sk) sk = 1;
-      g.splitk = sk;
-        if ((rc = ssasr_launch_gemm(g, st))) return rc;
-    }
-  }
-  return ssasr_launch_colsum(dG + s_lo * N * 4 * H, (s_hi - s_lo) * N, (int)(4 * H), 4 * H, db, st, db2);
+// One of wgrad_range's products as a launch of its own: C[b] += A[b]^T . B[b], b < nb as the launch's batches
+// (strides: the distances between the two batches' operands), K slices to fill ~512 workgroup slots.
+static int wgrad_product(int nb, const GemmDesc::Seg& sg, int64_t H, hipStream_t st) {
+  GemmDesc g{};
+  g.A = sg.A[0]; g.ma = rm_dense(4 * H);
+  g.B = sg.B[0]; g.mb = sg.mb;
+  g.C = sg.C[0]; g.mc = rm_dense(sg.ldc);
+  g.M = (int)(4 * H); g.N = sg.N; g.K = sg.K;
+  g.ta = 1; g.tb = 1; g.alpha = 1.f; g.beta = 1.f; g.batch = nb;
+  if (nb == 2) { g.sa = sg.A[1] - sg.A[0]; g.sb = sg.B[1] - sg.B[0]; g.sc = sg.C[1] - sg.C[0]; }
+  const int64_t tiles = nb * ((4 * H + 63) / 64) * ((sg.N + 63) / 64);
+  int sk = (int)(512 / tiles); if (sk < 1) sk = 1; if (sk > 32) sk = 32;
+  if (g.K < 64 * sk) sk = 1;
+  g.splitk = sk;
+  return ssasr_launch_gemm(g, st);
 }
 
-// Both directions' weight gradients of one step range each ([lo0, hi0) of the forward direction,
-// [lo1, hi1) of the reverse one, equal lengths) as the two batches of ONE launch per product: these
-// products are short (a BPTT segment of the first layer: 17 us each, mostly latency), and what
-// follows the last segment of a layer is exposed time at the end of the step.
-static int wgrad_pair_range(int64_t lo0, int64_t hi0, int64_t lo1, int64_t hi1, const float* dgates, const float* x,
-                            int64_t xs_s, int64_t xs_n, const float* hs, int64_t S, int64_t N, int64_t I, int64_t H,
-                            float* const dwih[2], float* const dwhh[2], float* const db[2], float* const db2[2],
-                            hipStream_t st) {
+// Steps [*a0, *a1) of [lo, hi) that have a predecessor in direction d: the recurrent product skips
+// s = 0 (forward) / s = S - 1 (reverse)
+static void wgrad_recurrent_steps(int d, int64_t lo, int64_t hi, int64_t S, int64_t* a0, int64_t* a1) {
+  *a0 = d ? lo : std::max<int64_t>(lo, 1);
+  *a1 = d ? std::min<int64_t>(hi, S - 1) : hi;
+}
+
+// Weight / bias gradients from the time steps [lo[b], hi[b]) of direction d_of[b] only, ADDED to the outputs of
+// index b (which the caller zeroed if needed).  nb = 1: one direction.  nb = 2: both directions' ranges as the two
+// batches of ONE launch per product: these products are short (a BPTT segment of the first layer: 17 us each,
+// mostly latency), and what follows the last segment of a layer is exposed time at the end of the step.  Batches
+// need ranges of equal length; others go one by one.
+static int wgrad_range(int nb, const int d_of[2], const int64_t lo[2], const int64_t hi[2], const float* dgates,
+                       const float* x, int64_t xs_s, int64_t xs_n, const float* hs, int64_t S, int64_t N, int64_t I,
+                       int64_t H, float* const dwih[2], float* const dwhh[2], float* const db[2], float* const db2[2],
+                       hipStream_t st) {
   const int64_t rows = S * N;
-  // the recurrent product skips the step without a predecessor: s = 0 (forward) / s = S - 1 (reverse)
-  const int64_t a0f = lo0 > 1 ? lo0 : 1, a1f = hi0;
-  const int64_t a0r = lo1, a1r = hi1 < S - 1 ? hi1 : S - 1;
-  const bool same = hi0 - lo0 == hi1 - lo1 && a1f - a0f == a1r - a0r && hi0 > lo0;
-  if (!same) {
-    int rc = wgrad_dir_range(0, lo0, hi0, dgates, x, xs_s, xs_n, hs, S, N, I, H, dwih[0], dwhh[0], db[0], db2[0], st);
-    if (rc) return rc;
-    return wgrad_dir_range(1, lo1, hi1, dgates, x, xs_s, xs_n, hs, S, N, I, H, dwih[1], dwhh[1], db[1], db2[1], st);
-  }
+  int64_t a0[2], a1[2];
+  for (int b = 0; b < nb; ++b) wgrad_recurrent_steps(d_of[b], lo[b], hi[b], S, &a0[b], &a1[b]);
   int rc;
-  {
-    const int d_of[2] = {0, 1};
-    const int64_t lo[2] = {lo0, lo1}, hi[2] = {hi0, hi1};
-    rc = wgrad_fused(2, d_of, lo, hi, dgates, x, xs_s, xs_n, hs, S, N, I, H, dwih, dwhh, db, db2, st);
-    if (rc != SSASR_EARG) return rc;
+  if (nb == 2 && (hi[1] - lo[1] != hi[0] - lo[0] || a1[1] - a0[1] != a1[0] - a0[0])) {
+    if ((rc = wgrad_range(1, d_of, lo, hi, dgates, x, xs_s, xs_n, hs, S, N, I, H, dwih, dwhh, db, db2, st))) return rc;
+    return wgrad_range(1, d_of + 1, lo + 1, hi + 1, dgates, x, xs_s, xs_n, hs, S, N, I, H, dwih + 1, dwhh + 1, db + 1, db2 + 1, st);
   }
-  {           // dW_ih[d] += dG_d[range_d]^T . X[range_d]
-    GemmDesc g{};
-    g.A = dgates + lo0 * N * 4 * H; g.ma = rm_dense(4 * H);
-    g.sa = rows * 4 * H + (lo1 - lo0) * N * 4 * H;
-    g.B = x + lo0 * xs_s; g.mb = RowMap{0, N, xs_s, xs_n};
-    g.sb = (lo1 - lo0) * xs_s;
-    g.C = dwih[0]; g.mc = rm_dense(I);
-    g.sc = dwih[1] - dwih[0];
-    g.M = (int)(4 * H); g.N = (int)I; g.K = (int)((hi0 - lo0) * N);
-    g.ta = 1; g.tb = 1; g.alpha = 1.f; g.beta = 1.f; g.batch = 2;
-    const int64_t tiles = 2 * ((4 * H + 63) / 64) * ((I + 63) / 64);
-    int sk = (int)(512 / tiles); if (sk < 1) sk = 1; if (sk > 32) sk = 32;
-    if (g.K < 64 * sk) sk = 1;
-    g.splitk = sk;
-    if ((rc = ssasr_launch_gemm(g, st))) return rc;
+  if (hi[0] <= lo[0]) return SSASR_OK;
+  GemmDesc::Seg seg[2] = {};
+  const int ns = a1[0] > a0[0] ? 2 : 1;
+  for (int b = 0; b < nb; ++b) {
+    const float* dG = dgates + d_of[b] * rows * 4 * H;
+    // dW_ih[d] += dG_d[range]^T . X[range]
+    seg[0].A[b] = dG + lo[b] * N * 4 * H;
+    seg[0].B[b] = x + lo[b] * xs_s;
+    seg[0].C[b] = dwih[b];
+    // dW_hh[d] += sum_s dG_d[s]^T . h_d[s_prev],  s_prev = s - 1 (forward direction) or s + 1 (reverse)
+    seg[1].A[b] = dG + a0[b] * N * 4 * H;
+    seg[1].B[b] = hs + d_of[b] * rows * H + (d_of[b] ? a0[b] + 1 : a0[b] - 1) * N * H;
+    seg[1].C[b] = dwhh[b];
   }
-  if (a1f > a0f) {           // dW_hh[d] += sum_s dG_d[s]^T . h_d[s_prev]
-    GemmDesc g{};
-    g.A = dgates + a0f * N * 4 * H; g.ma = rm_dense(4 * H);
-    g.sa = rows * 4 * H + (a0r - a0f) * N * 4 * H;
-    g.B = hs + (a0f - 1) * N * H; g.mb = rm_dense(H);
-    g.sb = rows * H + ((a0r + 1) - (a0f - 1)) * N * H;
-    g.C = dwhh[0]; g.mc = rm_dense(H);
-    g.sc = dwhh[1] - dwhh[0];
-    g.M = (int)(4 * H); g.N = (int)H; g.K = (int)((a1f - a0f) * N);
-    g.ta = 1; g.tb = 1; g.alpha = 1.f; g.beta = 1.f; g.batch = 2;
-    const int64_t tiles = 2 * ((4 * H + 63) / 64) * ((H + 63) / 64);
-    int sk = (int)(512 / tiles); if (sk < 1) sk = 1; if (sk > 32) sk = 32;
-    if (g.K < 64 * sk) sk = 1;
-    g.splitk = sk;
-    if ((rc = ssasr_launch_gemm(g, st))) return rc;
-  }
-  if ((rc = ssasr_launch_colsum(dgates + lo0 * N * 4 * H, (hi0 - lo0) * N, (int)(4 * H), 4 * H, db[0], st, db2[0]))) return rc;
-  return ssasr_launch_colsum(dgates + rows * 4 * H + lo1 * N * 4 * H, (hi1 - lo1) * N, (int)(4 * H), 4 * H, db[1], st, db2[1]);
+  seg[0].mb = RowMap{0, N, xs_s, xs_n}; seg[0].ldc = I; seg[0].N = (int)I; seg[0].K = (int)((hi[0] - lo[0]) * N);
+  seg[1].mb = rm_dense(H); seg[1].ldc = H; seg[1].N = (int)H; seg[1].K = (int)((a1[0] - a0[0]) * N);
+  rc = wgrad_fused(nb, seg, ns, I, H, db, db2, st);
+  if (rc != SSASR_EARG) return rc;
+  for (int k = 0; k < ns; ++k)
+    if ((rc = wgrad_product(nb, seg[k], H, st))) return rc;
+  for (int b = 0; b < nb; ++b)
+    if ((rc = ssasr_launch_colsum(seg[0].A[b], (hi[b] - lo[b]) * N, (int)(4 * H), 4 * H, db[b], st, db2[b]))) return rc;
+  return SSASR_OK;
 }
 
 extern "C" int ssasr_bilstm_wgrad(const float* dgates, const float* x, int64_t xs_s, int64_t xs_n,
@@ -716,6 +644,7 @@ extern "C" int ssasr_bilstm_wgrad(const float* dgates, const float* x, int64_t x
   float* dwhh[2] = {dw_hh_f, dw_hh_r};
   float* db[2] = {db_f, db_r};
   float* db2[2] = {db2_f, db2_r};
+  const int64_t lo = 0;
   for (int d = 0; d < 2; ++d) {
     if (!accumulate) {
       SSASR_HIP(hipMemsetAsync(dwih[d], 0, sizeof(float) * 4 * H * I, st));
@@ -723,7 +652,7 @@ extern "C" int ssasr_bilstm_wgrad(const float* dgates, const float* x, int64_t x
       SSASR_HIP(hipMemsetAsync(db[d], 0, sizeof(float) * 4 * H, st));
       if (db2[d]) SSASR_HIP(hipMemsetAsync(db2[d], 0, sizeof(float) * 4 * H, st));
     }
-    const int rc = wgrad_dir_range(d, 0, S, dgates, x, xs_s, xs_n, hs, S, N, I, H, dwih[d], dwhh[d], db[d], db2[d], st);
+    const int rc = wgrad_range(1, &d, &lo, &S, dgates, x, xs_s, xs_n, hs, S, N, I, H, dwih + d, dwhh + d, db + d, db2 + d, st);
     if (rc) return rc;
   }
   return SSASR_OK;
@@ -793,9 +722,8 @@ extern "C" int ssasr_bilstm_bwd_overlapped(const float* dy, int64_t ys_s, int64_
                                            int64_t dxs_s, int64_t dxs_n, float* dw_ih_f, float* dw_hh_f,
                                            float* db_f, float* db2_f, float* dw_ih_r, float* dw_hh_r,
                                            float* db_r, float* db2_r, float* ws_whhT, float* ws_dc, float* gx,
-                                           int32_t* sync_ws, int armed_in, const float* tsave, int segments,
+                                           int32_t* sync_ws, int armed, const float* tsave, int segments,
                                            void* events, void* stream, void* side_stream) {
-  const bool armed = armed_in != 0;
   if (!dw_ih_f || !dw_hh_f || !db_f || !dw_ih_r || !dw_hh_r || !db_r || !side_stream || !events) return SSASR_EARG;
   SsasrEvents* evs = static_cast<SsasrEvents*>(events);
   hipStream_t st = (hipStream_t)stream, side = (hipStream_t)side_stream;
@@ -809,9 +737,9 @@ extern "C" int ssasr_bilstm_bwd_overlapped(const float* dy, int64_t ys_s, int64_
   int rc;
   if (nseg == 1) {
     // plain form: the whole backward on `stream`, then every weight gradient on the second stream
-    rc = bilstm_bwd_impl(armed, tsave, dy, ys_s, ys_n, x, xs_s, xs_n, S, N, I, H, lens, w_ih_f, w_hh_f, w_ih_r, w_hh_r, gates,
-                         cs, hs, dx, dxs_s, dxs_n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ws_whhT, ws_dc,
-                         gx, sync_ws, stream);
+    rc = ssasr_bilstm_bwd(dy, ys_s, ys_n, x, xs_s, xs_n, S, N, I, H, lens, w_ih_f, w_hh_f, w_ih_r, w_hh_r, gates, cs, hs,
+                          dx, dxs_s, dxs_n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ws_whhT, ws_dc, gx, sync_ws,
+                          armed, tsave, stream);
     if (rc) return rc;
     hipEvent_t ev = evs->ev[0];
     SSASR_HIP(hipEventRecord(ev, st));
@@ -819,10 +747,7 @@ extern "C" int ssasr_bilstm_bwd_overlapped(const float* dy, int64_t ys_s, int64_
     return ssasr_bilstm_wgrad(gates, x, xs_s, xs_n, hs, S, N, I, H, dw_ih_f, dw_hh_f, db_f, db2_f, dw_ih_r, dw_hh_r,
                               db_r, db2_r, 1, side_stream);
   }
-  if (S <= 0 || N <= 0 || I <= 0 || H <= 0 || !dy || !x || !gates || (!cs && !tsave) || !hs || !ws_whhT || !ws_dc)
-    return SSASR_EARG;
-  const float* wih[2] = {w_ih_f, w_ih_r};
-  if (!w_hh_f || !w_hh_r) return SSASR_EARG;
+  if (!bwd_args_ok(S, N, I, H, dy, x, gates, cs, tsave, hs, ws_whhT, ws_dc) || !w_hh_f || !w_hh_r) return SSASR_EARG;
   // Everything of `stream` is enqueued first -- the ranges' launches, an event behind each, the input
   // gradient -- and only then the second stream's work: a range is ~150 us of GPU time on the short
   // layers, less than the host needs to enqueue its seven weight-gradient launches, and a recurrence
@@ -855,7 +780,7 @@ extern "C" int ssasr_bilstm_bwd_overlapped(const float* dy, int64_t ys_s, int64_
     const int base = evs->next_word;
     evs->next_word = (evs->next_word + 8) % SsasrEvents::PROGRESS_WORDS;
     prog.words = evs->progress + base;
-    const unsigned signals = (unsigned)((H / 16) * 2 * ((N + 15) / 16));      // row-writing workgroups (half 0)
+    const unsigned signals = (unsigned)bptt_workgroups(N, H, 2);      // row-writing workgroups (half 0)
     for (int k = 0; k + 1 < nseg; ++k) {
       prog.bound[k] = (int)bound[k + 1];
       evs->expected[base + k] += signals;
@@ -864,7 +789,7 @@ extern "C" int ssasr_bilstm_bwd_overlapped(const float* dy, int64_t ys_s, int64_
     }
     done[nseg - 1] = evs->ev[nseg - 1];
     rc = ssasr_launch_bptt_persistent(nullptr, gates, cs, dy, ys_s, ys_n, lens, gx, sync_ws, S, N, H, 2, st, 0, S,
-                                      ws_dc, w_hh_f, w_hh_r, armed, tsave, done[nseg - 1], &prog);
+                                      ws_dc, w_hh_f, w_hh_r, armed != 0, tsave, done[nseg - 1], &prog);
     if (rc) {                   // nothing was launched: nothing will count into the words
       for (int k = 0; k + 1 < nseg; ++k) evs->expected[base + k] -= signals;
       return rc;
@@ -875,31 +800,18 @@ extern "C" int ssasr_bilstm_bwd_overlapped(const float* dy, int64_t ys_s, int64_
       // the K-split kernel takes its weight slices straight from W_hh: no transposed copy
       done[k] = evs->ev[k];
       rc = ssasr_launch_bptt_persistent(nullptr, gates, cs, dy, ys_s, ys_n, lens, gx, sync_ws, S, N, H, 2, st, i0, i1,
-                                        ws_dc, w_hh_f, w_hh_r, armed, tsave, done[k]);
+                                        ws_dc, w_hh_f, w_hh_r, armed != 0, tsave, done[k]);
       if (rc) return rc;      // (ksplit_ok was checked: EARG here means misaligned arguments)
     }
   }
-  const int64_t rows = S * N;
-  // input gradient (critical path: the layer below needs it): dX = dG_f W_ih_f + dG_r W_ih_r.  On the
-  // split-bf16 kernel both directions are the two K segments of ONE launch (GemmDesc::kcat): dX is written
-  // once instead of written, read back and written again, and the second launch's tail is gone
-  const bool kcat = dx && ssasr_options().gemm_x6 != 0 && ssasr_options().gemm_kcat != 0 && (4 * H) % 32 == 0;
-  for (int d = 0; d < (kcat ? 1 : 2) && dx; ++d) {
-    GemmDesc g{};
-    g.A = gates + d * rows * 4 * H; g.ma = rm_dense(4 * H);
-    g.B = wih[d]; g.mb = rm_dense(I);
-    g.C = dx; g.mc = RowMap{0, N, dxs_s, dxs_n};
-    g.M = (int)rows; g.N = (int)I; g.K = (int)(4 * H);
-    g.ta = 0; g.tb = 1; g.alpha = 1.f; g.beta = d ? 1.f : 0.f; g.splitk = 1; g.batch = 1;
-    if (kcat) { g.kcat = 2; g.ska = rows * 4 * H; g.skb = wih[1] - wih[0]; }
-    if ((rc = ssasr_launch_gemm(g, st))) return rc;
-  }
+  if ((rc = launch_input_grad(gates, w_ih_f, w_ih_r, dx, dxs_s, dxs_n, S, N, I, H, st))) return rc;
   // A layer without an input gradient is the first one: its last range ends the backward pass, nothing is left
   // to run beside that range's weight-gradient products, and the two event hand-offs around them (first
   // stream -> second -> first, ~10 + 20 us on the timeline) are exposed in front of the optimiser.  They go on
   // `stream` itself, right behind the recurrence and on the whole chip, once the second stream's earlier
   // ranges (which add into the same outputs) are done -- long before, so that wait costs nothing.
   const bool tail_inline = !dx && ssasr_options().tail_inline != 0;
+  const int both[2] = {0, 1};
   for (int k = 0; k < nseg; ++k) {
     const int64_t i0 = bound[k], i1 = bound[k + 1];
     const bool inl = tail_inline && k == nseg - 1;
@@ -911,9 +823,10 @@ extern "C" int ssasr_bilstm_bwd_overlapped(const float* dy, int64_t ys_s, int64_
     } else {
       SSASR_HIP(hipStreamWaitEvent(side, done[k], 0));
     }
-    // iterations [i0, i1) cover steps S - i1 .. S - i0 - 1 of the forward direction and i0 .. i1 - 1 of the reverse
-    if ((rc = wgrad_pair_range(S - i1, S - i0, i0, i1, gates, x, xs_s, xs_n, hs, S, N, I, H, dwih, dwhh, db, db2,
-                               inl ? st : side)))
+    // iterations [i0, i1) cover steps S - i1 .. S - i0 - 1 of the forward direction and i0 .. i1 - 1 of the reverse:
+    // equal lengths, the step without a predecessor included, so both directions go as the batches of one launch
+    const int64_t lo[2] = {S - i1, i0}, hi[2] = {S - i0, i1};
+    if ((rc = wgrad_range(2, both, lo, hi, gates, x, xs_s, xs_n, hs, S, N, I, H, dwih, dwhh, db, db2, inl ? st : side)))
       return rc;
   }
   return SSASR_OK;

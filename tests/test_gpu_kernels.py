@@ -278,6 +278,24 @@ def test_bilstm_segmented_bptt_with_overlapped_weight_gradients(N, S, I, H, segm
         _lib.set_option('SSASR_WGRAD_FUSED', old_fused)
 
 
+@pytest.mark.parametrize('one_launch,kcat,fused', [(0, 1, 1), (0, 1, 0), (1, 0, 1), (0, 0, 0)])
+def test_bilstm_segmented_bptt_launch_forms(one_launch, kcat, fused, monkeypatch):
+    """The forms the default switches do not reach on this device: one BPTT launch per step range
+    (SSASR_BPTT_ONE_LAUNCH=0, otherwise taken only without stream-wait-value or with several column windows)
+    and the input gradient as two launches (SSASR_GEMM_KCAT=0), with fused and separate weight gradients.
+    The smallest shape that still segments: two 16-column chunks, the second with one live column, and
+    S = 32 x segments."""
+    from ss_asr_amd import _lib, ops
+    monkeypatch.setattr(ops, 'bptt_segments', 2)
+    names = ('SSASR_BPTT_ONE_LAUNCH', 'SSASR_GEMM_KCAT', 'SSASR_WGRAD_FUSED')
+    old = [_lib.set_option(n, v) for n, v in zip(names, (one_launch, kcat, fused))]
+    try:
+        _segmented_bptt_case(17, 64, 24, 64)
+    finally:
+        for n, v in zip(names, old):
+            _lib.set_option(n, v)
+
+
 def _segmented_bptt_case(N, S, I, H):
     from ss_asr_amd import ops
     from ss_asr_amd.optim import FlatParameters

@@ -25,7 +25,8 @@
  *
  * ABI history.  Added under 16 without changing anything older (the version number stays): beam search --
  * ssasr_beam, ssasr_decode_beam_ws_bytes, ssasr_decode_beam; joint CTC / attention decoding -- ssasr_ctc_prefix,
- * ssasr_decode_beam_ctc_ws_bytes, ssasr_decode_beam_ctc.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
+ * ssasr_decode_beam_ctc_ws_bytes, ssasr_decode_beam_ctc; length bonus, coverage term and end detection in the beam
+ * search -- ssasr_beam_terms, ssasr_decode_beam_ex_ws_bytes, ssasr_decode_beam_ex.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
  * (nothing older changed).  15: inference -- ssasr_charlm, ssasr_charlm_step, ssasr_infer, ssasr_decode_greedy (nothing
  * older changed).  14 and before: the training entry points below.
  *
@@ -644,7 +645,9 @@ int ssasr_charlm_train_bwd(const ssasr_charlm* lm, const int32_t* y, int64_t B, 
  *          advanced by its own character;
  *   stop:  no live hypothesis left, or after max_steps steps: what is live then is emitted as it stands;
  *   output: hypotheses by score descending, ties to the earlier step, then to candidate order; unused slots zero.
- * No length normalisation, no coverage term, no end-detection heuristic.  K == 1 follows greedy decoding (the
+ * This entry has no length term, no coverage term and no end detection; ssasr_decode_beam_ex (below) adds an
+ * additive length bonus, a coverage term and a stop rule.  Still not built: normalising a score by its length, and
+ * ESPnet's M-window end detector.  K == 1 follows greedy decoding (the
  * Python surface calls ssasr_decode_greedy for it).  An utterance's results depend on its own frames, enc_len,
  * K and max_steps alone: the same bits in any batch, at any padded T.
  * Accepted: the dimensions ssasr_decode_greedy accepts (its LDS bound does not apply: all per-hypothesis state is
@@ -722,6 +725,53 @@ typedef struct ssasr_ctc_prefix {
 int64_t ssasr_decode_beam_ctc_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D, int64_t V,
                                        int64_t Hl, int64_t S);
 int ssasr_decode_beam_ctc(const ssasr_beam* d, const ssasr_ctc_prefix* c, void* stream);
+
+/* ---- length bonus, coverage term, end detection (added under ABI 16) -------------------------------------------
+ * BUILD-DEFINED: the reference has no beam search.  ssasr_decode_beam (c NULL or ctc_weight 0) / ssasr_decode_beam_ctc
+ * with three terms inside the same one-launch kernel.  Per utterance, on top of those entries' semantics; everything
+ * else -- ties, the <EOS> rule, the cap, the output order, the unused slots, an utterance's independence of N and
+ * the padded T -- is unchanged.
+ *   Length bonus: candidate score = that entry's candidate score + length_bonus (beta) when v != eos, so a
+ *     hypothesis of n characters carries n * beta.  beta is any finite float.  This is the ADDITIVE reward, not a
+ *     division by the length: a normalised score is not a sum over steps, it could only re-order the final list and
+ *     could not change which prefixes survive.  Score normalisation by length is not built.
+ *   Coverage (Chorowski & Jaitly 2016): every live hypothesis g keeps cum_g[t], the sum of its attention weights
+ *     over its executed steps (float, zero at the start), and cov_g, the number of frames with cum_g[t] >
+ *     coverage_threshold (tau).  At a step, after the softmax over the frames, for every live b:
+ *     cum'_b[t] = cum_b[t] + att_b[t] for t < enc_len, cov'_b = the number of t < enc_len with cum'_b[t] > tau; every
+ *     candidate (b, v), <EOS> included, gets + coverage_weight (eta) * (cov'_b - cov_b); a chosen non-eos candidate's
+ *     new slot takes cum', cov' of its parent.  The counts are integers, so the term telescopes to
+ *     eta * cov(final prefix).  eta == 0: no coverage state exists and tau is not read.
+ *   End detection, after the selection of step s (the finished list and the new live set are known): the loop ends
+ *     when at least one hypothesis is finished, at least one is live, and
+ *     max(live scores) < max(finished scores) - end_margin (delta).  The live hypotheses are then DISCARDED, not
+ *     emitted (they are abandoned prefixes, unlike the cap's): n_hyps = finished.  With beta == 0, eta == 0 and
+ *     lm_weight >= 0 every step's increment is <= 0 (with the CTC term as well: a prefix probability never grows), so
+ *     with delta == 0 the best hypothesis and its score are exactly those of the search without the rule; only the
+ *     tail of the N-best list is lost.  Otherwise the rule is a heuristic.  ESPnet's M-window end detector is not
+ *     built.
+ *   n_steps[n]: the loop iterations the utterance executed, for any combination of terms.
+ * Accepted: what the underlying entry accepts (c non-NULL: ssasr_decode_beam_ctc's checks), with beta and eta
+ * finite, tau finite and > 0 when eta != 0, delta not NaN (delta < 0: no end detection), and
+ * ws_bytes >= ssasr_decode_beam_ex_ws_bytes(..., ctc = (c != NULL), coverage = (eta != 0)).  That figure is
+ * ssasr_decode_beam_ws_bytes / ssasr_decode_beam_ctc_ws_bytes for coverage == 0 and larger by the coverage block
+ * otherwise: cum, 2 buffers x K x up4(T) floats per utterance, behind everything else in the slice (a new slot's row
+ * is a copy of its parent's into the other buffer, beside the Speller state).  Everything else, t == NULL included,
+ * is an argument error before any launch, and the size query returns 0.
+ * All terms off (beta == 0, eta == 0, delta < 0): the call launches exactly the kernel ssasr_decode_beam /
+ * ssasr_decode_beam_ctc launch and gives the same bits. */
+typedef struct ssasr_beam_terms {
+  float length_bonus;        /* beta: added to every candidate (b, v) with v != eos                      */
+  float coverage_weight;     /* eta; 0: coverage off, no coverage state, threshold ignored               */
+  float coverage_threshold;  /* tau > 0                                                                  */
+  float end_margin;          /* delta >= 0: end detection on; < 0: off                                   */
+  int32_t* n_steps;          /* [N] optional: steps the utterance's loop executed                        */
+} ssasr_beam_terms;
+
+int64_t ssasr_decode_beam_ex_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
+                                      int64_t V, int64_t Hl, int64_t S, int32_t ctc, int32_t coverage);
+int ssasr_decode_beam_ex(const ssasr_beam* d, const ssasr_ctc_prefix* c /* NULL or weight 0: no CTC */,
+                         const ssasr_beam_terms* t, void* stream);
 
 #ifdef __cplusplus
 }

@@ -74,6 +74,12 @@ class CtcPrefix(C.Structure):
     _fields_ = [('w_ctc', P), ('b_ctc', P), ('ctc_weight', F32), ('blank', C.c_int32)]
 
 
+class BeamTerms(C.Structure):
+    """struct ssasr_beam_terms (include/ssasr.h)."""
+    _fields_ = [('length_bonus', F32), ('coverage_weight', F32), ('coverage_threshold', F32), ('end_margin', F32),
+                ('n_steps', P)]
+
+
 SIGNATURES = {
     'ssasr_abi_version': (I32, []),
     'ssasr_set_option': (I32, [C.c_char_p, I32]),
@@ -109,6 +115,8 @@ SIGNATURES = {
     'ssasr_decode_beam': (I32, [C.POINTER(Beam), P]),
     'ssasr_decode_beam_ctc_ws_bytes': (I64, [I64] * 9),
     'ssasr_decode_beam_ctc': (I32, [C.POINTER(Beam), C.POINTER(CtcPrefix), P]),
+    'ssasr_decode_beam_ex_ws_bytes': (I64, [I64] * 9 + [I32, I32]),
+    'ssasr_decode_beam_ex': (I32, [C.POINTER(Beam), C.POINTER(CtcPrefix), C.POINTER(BeamTerms), P]),
     'ssasr_charlm_train_ws_floats': (I64, [I64, I64, I64, I64]),
     'ssasr_charlm_train_fwd': (I32, [C.POINTER(CharLM), P, P, P, P, I64, I64, P, P, P, P, P]),
     'ssasr_charlm_train_bwd': (I32, [C.POINTER(CharLM), P, I64, I64, F32, P, P]),

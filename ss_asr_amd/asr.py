@@ -258,6 +258,8 @@ class ASR(nn.Module):
         # decode_nbest's device results for beam_size > 1: (chars [N, K, steps] int32, n_chars [N, K] int32,
         # hyp_scores [N, K], n_hyps [N] int32)
         self.last_beam = None
+        # n_steps [N] int32 of the last decode_nbest call that had a length bonus, a coverage term or end detection on
+        self.last_beam_steps = None
         self.init_parameters()
 
     def init_parameters(self):
@@ -345,15 +347,40 @@ class ASR(nn.Module):
                              % type(self).__name__)
         return head.weight, head.bias, ctc_weight
 
-    def decode(self, x, x_len, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1, ctc_weight=0.0):
+    @staticmethod
+    def _beam_terms(length_bonus, coverage_weight, coverage_threshold, end_margin):
+        """None with every term at its default (today's path), else ops.decode_beam_ex's keywords."""
+        length_bonus, coverage_weight = float(length_bonus), float(coverage_weight)
+        if not math.isfinite(length_bonus):
+            raise ValueError('length_bonus must be finite, got %r' % (length_bonus,))
+        if not math.isfinite(coverage_weight):
+            raise ValueError('coverage_weight must be finite, got %r' % (coverage_weight,))
+        if coverage_weight != 0.0:
+            coverage_threshold = float(coverage_threshold)
+            if not (math.isfinite(coverage_threshold) and coverage_threshold > 0.0):
+                raise ValueError('coverage_threshold must be finite and > 0, got %r' % (coverage_threshold,))
+        if end_margin is not None:
+            end_margin = float(end_margin)
+            if not (math.isfinite(end_margin) and end_margin >= 0.0):
+                raise ValueError('end_margin must be None or finite and >= 0, got %r' % (end_margin,))
+        if length_bonus == 0.0 and coverage_weight == 0.0 and end_margin is None:
+            return None
+        return dict(length_bonus=length_bonus, coverage_weight=coverage_weight,
+                    coverage_threshold=coverage_threshold if coverage_weight != 0.0 else 0.5, end_margin=end_margin)
+
+    def decode(self, x, x_len, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1, ctc_weight=0.0,
+               length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None):
         """src/asr.py:112-173: greedy decoding of ONE utterance (x [1, seq, features], x_len from prepare_x)
         until <EOS> or max_decoding_steps (200 in the reference, :128), every step's character scores being
         log_softmax(speller) + lm_weight * log_softmax(rnn_lm).  Returns the decoded string.  rnn_lm None: no LM
         term.  The whole loop is one launch (ssasr_decode_greedy).  beam_size > 1: the best hypothesis of a beam
-        search of that width (decode_many).  ctc_weight > 0: joint CTC / attention decoding (decode_nbest)."""
+        search of that width (decode_many).  ctc_weight > 0: joint CTC / attention decoding (decode_nbest).
+        length_bonus, coverage_weight / coverage_threshold, end_margin: the beam search's terms (decode_nbest)."""
         assert len(x.shape) == 3 and x.shape[0] == 1
         return self.decode_many([x], [x_len], rnn_lm, mapper, lm_weight, max_decoding_steps=max_decoding_steps,
-                                beam_size=beam_size, ctc_weight=ctc_weight)[0]
+                                beam_size=beam_size, ctc_weight=ctc_weight, length_bonus=length_bonus,
+                                coverage_weight=coverage_weight, coverage_threshold=coverage_threshold,
+                                end_margin=end_margin)[0]
 
     def _encode_packed(self, xs, x_lens):
         """Each utterance encoded alone, packed to ([N, T'max, E], int32 [N] frame counts on the device)."""
@@ -374,7 +401,7 @@ class ASR(nn.Module):
         return packed, _dev_i32(enc_lens, dev)
 
     def decode_many(self, xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1,
-                    ctc_weight=0.0):
+                    ctc_weight=0.0, length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None):
         """decode() for a list of single utterances in ONE decode launch.  Each utterance is encoded alone
         (blstm_4 recurs over the utterance axis, src/asr.py:237-238, :262: a batched encoder would change every
         transcript); the encoder outputs are packed to [N, T'max, E] and every utterance gets a workgroup of its
@@ -382,11 +409,16 @@ class ASR(nn.Module):
         beam_size > 1 (at most 32): beam search of that width in one launch (ssasr_decode_beam; no length
         normalisation); returns each utterance's best hypothesis and keeps (chars [N, K, steps], n_chars [N, K],
         hyp_scores [N, K], n_hyps [N]) on the device in last_beam; last_decode is left as it was.
-        ctc_weight > 0: as beam_size > 1, for any beam_size in 1..32 (decode_nbest)."""
-        if beam_size != 1 or self._ctc_head(ctc_weight) is not None:
+        ctc_weight > 0, or a length bonus, a coverage term or end detection on: as beam_size > 1, for any beam_size
+        in 1..32 (decode_nbest)."""
+        terms = self._beam_terms(length_bonus, coverage_weight, coverage_threshold, end_margin)
+        if beam_size != 1 or self._ctc_head(ctc_weight) is not None or terms is not None:
             return [nbest[0][0] for nbest in self.decode_nbest(xs, x_lens, rnn_lm, mapper, lm_weight, beam_size,
                                                                max_decoding_steps=max_decoding_steps,
-                                                               ctc_weight=ctc_weight)]
+                                                               ctc_weight=ctc_weight, length_bonus=length_bonus,
+                                                               coverage_weight=coverage_weight,
+                                                               coverage_threshold=coverage_threshold,
+                                                               end_margin=end_margin)]
         with torch.no_grad():
             packed, enc_lens = self._encode_packed(xs, x_lens)
             self.last_decode = ops.decode_greedy(
@@ -397,7 +429,7 @@ class ASR(nn.Module):
         return [''.join(mapper.ind_to_char(c) for c in row[:n]) for row, n in zip(chars, n_chars)]
 
     def decode_nbest(self, xs, x_lens, rnn_lm, mapper, lm_weight, beam_size, max_decoding_steps=200, *,
-                     ctc_weight=0.0):
+                     ctc_weight=0.0, length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None):
         """Beam search over a list of single utterances in ONE launch: per utterance the list of (text, score),
         best first, score = the sum of the chosen characters' log_softmax(speller) + lm_weight *
         log_softmax(rnn_lm) entries (<EOS>'s included when it ended the hypothesis; no length normalisation).
@@ -406,12 +438,20 @@ class ASR(nn.Module):
         any beam_size in 1..32 (width 1 is the beam kernel at K = 1); a character's score entry is then
         (1 - ctc_weight) * log_softmax(speller) + ctc_weight * (the CTC prefix score's increase) + lm_weight *
         log_softmax(rnn_lm), and characters that the utterance's frames cannot hold are never chosen.  Sets
-        last_beam.  ctc_weight 0 is the path above exactly."""
+        last_beam.  ctc_weight 0 is the path above exactly.
+        length_bonus (beta, added per character), coverage_weight / coverage_threshold (eta times the number of
+        frames whose summed attention exceeds the threshold) and end_margin (None: off; delta >= 0: the loop ends once
+        the best live score is below the best finished one by more than delta, the live prefixes being dropped) are
+        the terms of ssasr_decode_beam_ex (include/ssasr.h).  With any of them on, any beam_size in 1..32 runs the
+        beam kernel (width 1 is the beam kernel at K = 1), last_beam is set and last_beam_steps keeps n_steps [N],
+        the loop iterations each utterance executed.  With all at their defaults every call takes the path above
+        exactly."""
         beam_size = int(beam_size)
         if not 1 <= beam_size <= ops.MAX_BEAM:
             raise ValueError('beam_size must be in 1..%d, got %d' % (ops.MAX_BEAM, beam_size))
         ctc = self._ctc_head(ctc_weight)
-        if beam_size == 1 and ctc is None:
+        terms = self._beam_terms(length_bonus, coverage_weight, coverage_threshold, end_margin)
+        if beam_size == 1 and ctc is None and terms is None:
             texts = self.decode_many(xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=max_decoding_steps)
             chars, n_chars, scores, _ = self.last_decode
             steps = torch.clamp(n_chars + 1, max=max_decoding_steps)            # executed steps: <EOS>'s too
@@ -423,7 +463,11 @@ class ASR(nn.Module):
             packed, enc_lens = self._encode_packed(xs, x_lens)
             args = (packed, enc_lens, self._decoder_params(), (self.attention.psi.weight, self.attention.psi.bias),
                     rnn_lm, lm_weight, mapper.char_to_ind(EOS_TKN), max_decoding_steps, beam_size)
-            self.last_beam = ops.decode_beam(*args) if ctc is None else ops.decode_beam_ctc(*args, ctc)
+            if terms is not None:
+                out = ops.decode_beam_ex(*args, ctc, **terms)
+                self.last_beam, self.last_beam_steps = out[:4], out[4]
+            else:
+                self.last_beam = ops.decode_beam(*args) if ctc is None else ops.decode_beam_ctc(*args, ctc)
         chars, n_chars, hyp_scores, n_hyps = [t.cpu().tolist() for t in self.last_beam]
         return [[(''.join(mapper.ind_to_char(c) for c in chars[i][k][:n_chars[i][k]]), hyp_scores[i][k])
                  for k in range(n_hyps[i])] for i in range(len(xs))]

@@ -505,6 +505,21 @@ __host__ __device__ inline CtcWs ctc_ws_map(const BeamWs& m, int K, int T) {
   return c;
 }
 
+// ---- length bonus, coverage term, end detection (semantics in include/ssasr.h, ssasr_beam_terms) ------------------
+// TERMS true: the same loop with beta added to every non-<EOS> candidate, eta * (cov' - cov) to every candidate of a
+// parent, and the stop rule after the selection.  Coverage state, per live hypothesis g: cum_g [T] floats in the
+// workspace slice behind everything else (T goes to 16,384), double-buffered like the Speller state -- phase 3 adds
+// the step's attention row to the parent's row in place and counts, phase 11 copies the parent's row into the new
+// slot's row of the other buffer -- and cov_g, the step's cov' and the step's increments in LDS (K ints / floats).
+// eta == 0: no coverage state, the slice is the plain / CTC one.  n_steps is written by every instantiation.
+struct TermsDev {
+  float beta, eta, tau, delta;            // delta < 0: no end detection
+  int32_t* n_steps;
+};
+
+// floats of one utterance's coverage block: cum, 2 buffers x K rows of up4(T)
+__host__ __device__ inline int64_t cov_ws_floats(const BeamWs& m, int K) { return 2 * (int64_t)K * m.Tp; }
+
 constexpr int kCtcAhead = 4;              // frames whose loads a lattice loop issues before it needs the first
 
 // log(exp(a) + exp(b))
@@ -594,9 +609,9 @@ __device__ void ctc_extend(const float* lp, const double* pn0, const double* pb0
 
 // CTC false: ssasr_decode_beam's kernel (cd unread).  CTC true: the same loop with the candidates scored
 // score_b + (1 - lambda) * log_softmax(asr) + lambda * (psi(h) - psi(g)) + lm_weight * log_softmax(lm), candidates
-// at -inf never chosen; only the prologue and phases 8 to 11 differ.
-template <bool CTC>
-__global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDev cd) {
+// at -inf never chosen; only the prologue and phases 8 to 11 differ.  TERMS false: td.n_steps alone is read.
+template <bool CTC, bool TERMS>
+__global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDev cd, TermsDev td) {
   __shared__ float cand[kMaxBeam * 64];            // score_b + row_b[v]; NaN: struck out
   __shared__ float score[2][kMaxBeam];             // live hypotheses' scores, by step parity
   __shared__ float redv[kWaves];
@@ -606,16 +621,22 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
   __shared__ int par[kMaxBeam], chr[kMaxBeam];     // new live slots: parent slot, character
   __shared__ float fin_score[kMaxBeam];            // finished / capped hypotheses in (step, candidate order)
   __shared__ int fin_len[kMaxBeam], fin_par[kMaxBeam];
-  __shared__ int counts[2];                        // new live slots, finished hypotheses
+  __shared__ int counts[TERMS ? 3 : 2];            // new live slots, finished hypotheses; TERMS: the stop rule fired
   __shared__ double cpsi[CTC ? kMaxBeam * 64 : 1]; // CTC: psi of the step's candidates
   __shared__ int lastc[2][CTC ? kMaxBeam : 1];     // CTC: the live hypotheses' last characters, by step parity
+  __shared__ int cov[2][TERMS ? kMaxBeam : 1];     // coverage: the live hypotheses' counts, by step parity
+  __shared__ int cov_new[TERMS ? kMaxBeam : 1];    // coverage: cov' of the step's parents
+  __shared__ float cov_inc[TERMS ? kMaxBeam : 1];  // coverage: eta * (cov' - cov) of the step's parents
 
   const InferDev& p = bd.in;
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int T = p.T, E = p.E, A = p.A, D = p.D, V = p.V, Hl = p.lm.H, K = bd.K, S = p.max_steps;
   const BeamWs m = beam_ws_map(K, T, E, A, D, Hl, S);
   const CtcWs cm = ctc_ws_map(m, K, T);
-  float* ws = bd.ws + (int64_t)n * (CTC ? cm.total : m.total);
+  const bool cover = TERMS && td.eta != 0.f;
+  int64_t slice = CTC ? cm.total : m.total;
+  if constexpr (TERMS) slice += cover ? cov_ws_floats(m, K) : 0;
+  float* ws = bd.ws + (int64_t)n * slice;
   float *xin = ws + m.xin, *lmx = ws + m.lmx, *q = ws + m.q, *gates = ws + m.gates, *en = ws + m.en,
         *part = ws + m.part, *gi = ws + m.gi, *gh = ws + m.gh, *lg = ws + m.lg, *lmlg = ws + m.lmlg;
   int32_t* bp = reinterpret_cast<int32_t*>(ws + m.bp);
@@ -667,6 +688,15 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
       psi_cur[0] = 0.0;
     }
   }
+  // coverage: the empty prefix has attended to nothing
+  float* ccur = ws + (CTC ? cm.total : m.total);
+  float* cnxt = ccur + (int64_t)K * Tp;
+  if constexpr (TERMS) {
+    if (cover) {
+      for (int t = tid; t < len; t += kThreads) ccur[t] = 0.f;
+      if (tid == 0) cov[0][0] = 0;
+    }
+  }
   phase_sync();
 
   int live = 1, nfin = 0, step = 0;
@@ -699,6 +729,25 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
         sum += ex;
       }
       sum = wave_sum(sum);
+      if constexpr (TERMS) {
+        if (cover) {                                 // cum' = cum + att in place, cov' = frames with cum' > tau
+          float* cum = ccur + (int64_t)b * Tp;
+          float cnt = 0.f;                           // an integer <= 16,384: exact, whatever the order
+          for (int t = lane; t < len; t += 64) {
+            const float a = row[t] / sum;
+            row[t] = a;
+            const float c = cum[t] + a;
+            cum[t] = c;
+            cnt += c > td.tau ? 1.f : 0.f;
+          }
+          const int cn = (int)wave_sum(cnt);
+          if (lane == 0) {
+            cov_new[b] = cn;
+            cov_inc[b] = td.eta * (float)(cn - cov[step & 1][b]);
+          }
+          continue;
+        }
+      }
       for (int t = lane; t < len; t += 64) row[t] = row[t] / sum;
     }
     if (Hl) {
@@ -743,11 +792,19 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
         float fin = (1.f - cd.lambda) * a + cd.lambda * (float)(ps - psi_cur[b]);
         if (Hl) fin += p.lm_weight * l;
         fin += sc[b];
+        if constexpr (TERMS) {
+          if (lane != p.eos) fin += td.beta;
+          if (cover) fin += cov_inc[b];
+        }
         cand[b * 64 + lane] = (lane < V && fin == fin) ? fin : -INFINITY;
       }
     } else {
       for (int b = wave; b < live; b += kWaves) {
-        const float fin = score_row(lg + b * 64, Hl ? lmlg + b * 64 : nullptr, V, p.lm_weight) + sc[b];
+        float fin = score_row(lg + b * 64, Hl ? lmlg + b * 64 : nullptr, V, p.lm_weight) + sc[b];
+        if constexpr (TERMS) {
+          if (lane != p.eos) fin += td.beta;
+          if (cover) fin += cov_inc[b];
+        }
         cand[b * 64 + lane] = (lane < V && fin == fin) ? fin : -INFINITY;      // a NaN is never chosen before a number
       }
     }
@@ -814,15 +871,35 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
             psi_nxt[nl] = cpsi[pick[i]];
             lastc[(step + 1) & 1][nl] = v;
           }
+          if constexpr (TERMS) {
+            if (cover) cov[(step + 1) & 1][nl] = cov_new[b];
+          }
           ++nl;
         }
       }
       counts[0] = nl;
       counts[1] = nf;
+      if constexpr (TERMS) {                         // the stop rule: the best live score is below the best finished - delta
+        int stop = 0;
+        if (td.delta >= 0.f && nf > 0 && nl > 0) {
+          float ml = sc_new[0], mf = fin_score[0];
+          for (int j = 1; j < nl; ++j) ml = fmaxf(ml, sc_new[j]);
+          for (int j = 1; j < nf; ++j) mf = fmaxf(mf, fin_score[j]);
+          stop = ml < mf - td.delta;
+        }
+        counts[2] = stop;
+      }
     }
     __syncthreads();
     const int nl = counts[0];
     nfin = counts[1];
+    if constexpr (TERMS) {
+      if (counts[2]) {                               // the live hypotheses are abandoned prefixes: discarded, not emitted
+        live = 0;
+        ++step;
+        break;
+      }
+    }
     // 11: a new slot's state is its parent's row, copied into the other buffer; its inputs are its character's
     for (int i = tid; i < nl * (Sz / 4); i += kThreads) {
       const int j = i / (Sz / 4), o = i % (Sz / 4);
@@ -835,6 +912,19 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
     for (int i = tid; i < nl * Hl; i += kThreads) {
       const int j = i / Hl, u = i % Hl;
       lmx[(int64_t)j * Hl + u] = p.lm.emb[(int64_t)chr[j] * Hl + u];
+    }
+    if constexpr (TERMS) {                           // and its coverage row is its parent's cum'
+      if (cover) {
+        const int n4 = up4(len) / 4;
+        for (int i = tid; i < nl * n4; i += kThreads) {
+          const int j = i / n4, o = i % n4;
+          reinterpret_cast<float4*>(cnxt + (int64_t)j * Tp)[o] =
+              reinterpret_cast<const float4*>(ccur + (int64_t)par[j] * Tp)[o];
+        }
+        float* c = ccur;
+        ccur = cnxt;
+        cnxt = c;
+      }
     }
     if constexpr (CTC) {                             // and its lattice rows are its parent's, advanced by its character
       if (tid < nl) {
@@ -872,6 +962,7 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
     hyp_scores[tid] = 0.f;
   }
   if (tid == 0) bd.n_hyps[n] = total;
+  if (tid == 0 && td.n_steps) td.n_steps[n] = step;  // loop iterations executed
   phase_sync();
   // output order: score descending, ties to the earlier entry of the (step, candidate order) list
   if (tid < total) {
@@ -1000,15 +1091,33 @@ extern "C" int64_t ssasr_decode_beam_ctc_ws_bytes(int64_t N, int64_t K, int64_t 
   return N * ctc_ws_map(m, (int)K, (int)T).total * (int64_t)sizeof(float);
 }
 
+extern "C" int64_t ssasr_decode_beam_ex_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
+                                                 int64_t V, int64_t Hl, int64_t S, int32_t ctc, int32_t coverage) {
+  if (!decode_dims_ok(N, K, T, E, A, D, V, Hl, S)) return 0;
+  const BeamWs m = beam_ws_map((int)K, (int)T, (int)E, (int)A, (int)D, (int)Hl, (int)S);
+  const int64_t slice = (ctc ? ctc_ws_map(m, (int)K, (int)T).total : m.total) + (coverage ? cov_ws_floats(m, (int)K) : 0);
+  return N * slice * (int64_t)sizeof(float);
+}
+
 namespace {
 
-// ssasr_decode_beam (cp == nullptr) and ssasr_decode_beam_ctc
-int launch_beam(const ssasr_beam* dp, const ssasr_ctc_prefix* cp, void* stream) {
+// ssasr_decode_beam (cp == nullptr), ssasr_decode_beam_ctc and ssasr_decode_beam_ex (tp != nullptr)
+int launch_beam(const ssasr_beam* dp, const ssasr_ctc_prefix* cp, const ssasr_beam_terms* tp, void* stream) {
   BeamDev b{};
   if (!dp || !infer_dev(*dp, dp->K, b.in)) return SSASR_EARG;
   const ssasr_beam& d = *dp;
-  const int64_t need = (cp ? ssasr_decode_beam_ctc_ws_bytes : ssasr_decode_beam_ws_bytes)(
-      d.N, d.K, d.T, d.E, d.A, d.D, d.V, b.in.lm.H, d.max_steps);
+  TermsDev t{0.f, 0.f, 0.f, -1.f, nullptr};
+  if (tp) {
+    if (!std::isfinite(tp->length_bonus) || !std::isfinite(tp->coverage_weight) || tp->end_margin != tp->end_margin)
+      return SSASR_EARG;
+    if (tp->coverage_weight != 0.f && !(std::isfinite(tp->coverage_threshold) && tp->coverage_threshold > 0.f))
+      return SSASR_EARG;
+    t = TermsDev{tp->length_bonus, tp->coverage_weight, tp->coverage_weight != 0.f ? tp->coverage_threshold : 0.f,
+                 tp->end_margin >= 0.f ? tp->end_margin : -1.f, tp->n_steps};
+  }
+  const bool terms = t.beta != 0.f || t.eta != 0.f || t.delta >= 0.f;
+  const int64_t need = ssasr_decode_beam_ex_ws_bytes(d.N, d.K, d.T, d.E, d.A, d.D, d.V, b.in.lm.H, d.max_steps,
+                                                     cp ? 1 : 0, t.eta != 0.f ? 1 : 0);
   if (!d.ws || !aligned16(d.ws) || !d.hyp_scores || !d.n_hyps || d.ws_bytes < need) return SSASR_EARG;
   b.K = (int)d.K; b.ws = d.ws; b.hyp_scores = d.hyp_scores; b.n_hyps = d.n_hyps;
   CtcDev c{};
@@ -1020,21 +1129,35 @@ int launch_beam(const ssasr_beam* dp, const ssasr_ctc_prefix* cp, void* stream) 
       c = CtcDev{cp->w_ctc, cp->b_ctc, cp->ctc_weight, cp->blank};
     }
   }
-  if (c.w)
-    hipLaunchKernelGGL(decode_beam_kernel<true>, dim3((unsigned)d.N), dim3(kThreads), 0, (hipStream_t)stream, b, c);
+  // all terms off: the instantiations ssasr_decode_beam / ssasr_decode_beam_ctc launch
+  const dim3 grid((unsigned)d.N), block(kThreads);
+  if (c.w && terms)
+    hipLaunchKernelGGL((decode_beam_kernel<true, true>), grid, block, 0, (hipStream_t)stream, b, c, t);
+  else if (c.w)
+    hipLaunchKernelGGL((decode_beam_kernel<true, false>), grid, block, 0, (hipStream_t)stream, b, c, t);
+  else if (terms)
+    hipLaunchKernelGGL((decode_beam_kernel<false, true>), grid, block, 0, (hipStream_t)stream, b, c, t);
   else
-    hipLaunchKernelGGL(decode_beam_kernel<false>, dim3((unsigned)d.N), dim3(kThreads), 0, (hipStream_t)stream, b, c);
+    hipLaunchKernelGGL((decode_beam_kernel<false, false>), grid, block, 0, (hipStream_t)stream, b, c, t);
   SSASR_LAUNCH_CHECK();
   return SSASR_OK;
 }
 
 }  // namespace
 
-extern "C" int ssasr_decode_beam(const ssasr_beam* dp, void* stream) { return launch_beam(dp, nullptr, stream); }
+extern "C" int ssasr_decode_beam(const ssasr_beam* dp, void* stream) {
+  return launch_beam(dp, nullptr, nullptr, stream);
+}
 
 extern "C" int ssasr_decode_beam_ctc(const ssasr_beam* dp, const ssasr_ctc_prefix* cp, void* stream) {
   if (!cp) return SSASR_EARG;
-  return launch_beam(dp, cp, stream);
+  return launch_beam(dp, cp, nullptr, stream);
+}
+
+extern "C" int ssasr_decode_beam_ex(const ssasr_beam* dp, const ssasr_ctc_prefix* cp, const ssasr_beam_terms* tp,
+                                    void* stream) {
+  if (!tp) return SSASR_EARG;
+  return launch_beam(dp, cp, tp, stream);
 }
 
 extern "C" int ssasr_charlm_step(const ssasr_charlm* lm, const int32_t* x, const float* h1, const float* h2,

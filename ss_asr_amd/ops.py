@@ -1091,17 +1091,23 @@ def decode_greedy(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, wan
 MAX_BEAM = 32
 
 
-def beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws=None, ctc=False):
+def beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws=None, ctc=False,
+                coverage=None):
     """(struct ssasr_beam, its outputs (chars, n_chars, hyp_scores, n_hyps), the tensors it points into) for
     decode_beam's arguments; the outputs are allocated, not yet written.  ctc: the workspace is sized for
-    ssasr_decode_beam_ctc."""
+    ssasr_decode_beam_ctc.  coverage True / False: it is sized by ssasr_decode_beam_ex_ws_bytes, with / without the
+    coverage block."""
     lib = _lib.load()
     d, keep = _decode_struct(_lib.Beam, feat, enc_len, params, psi, lm, lm_weight, eos, max_steps)
     N, K, S = d.N, int(beam_size), d.max_steps
     dev = keep[0].device
     hl = lm.hidden_size if lm is not None else 0
-    query = lib.ssasr_decode_beam_ctc_ws_bytes if ctc else lib.ssasr_decode_beam_ws_bytes
-    need = int(query(N, K, d.T, d.E, d.A, d.D, d.V, hl, S))
+    if coverage is None:
+        query = lib.ssasr_decode_beam_ctc_ws_bytes if ctc else lib.ssasr_decode_beam_ws_bytes
+        need = int(query(N, K, d.T, d.E, d.A, d.D, d.V, hl, S))
+    else:
+        need = int(lib.ssasr_decode_beam_ex_ws_bytes(N, K, d.T, d.E, d.A, d.D, d.V, hl, S, int(bool(ctc)),
+                                                     int(bool(coverage))))
     if need <= 0:
         raise RuntimeError('ssasr_decode_beam: invalid argument (beam size %d, sizes N %d T %d E %d A %d D %d V %d '
                            'H %d steps %d)' % (K, N, d.T, d.E, d.A, d.D, d.V, hl, S))
@@ -1148,6 +1154,25 @@ def decode_beam_ctc(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, b
     c, c_keep = ctc_prefix_struct(ctc, blank)
     check(_lib.load().ssasr_decode_beam_ctc(C.byref(d), C.byref(c), _stream()), 'ssasr_decode_beam_ctc')
     return outs
+
+
+def decode_beam_ex(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ctc=None, *, length_bonus=0.0,
+                   coverage_weight=0.0, coverage_threshold=0.5, end_margin=None, ws=None, blank=CTC_BLANK):
+    """ssasr_decode_beam_ex: decode_beam (ctc None) / decode_beam_ctc (ctc = (ctc_head weight, bias, ctc_weight)) with
+    the length bonus added to every non-<EOS> candidate, coverage_weight * (the increase of the parent's count of
+    frames whose summed attention exceeds coverage_threshold) added to every candidate, and, for end_margin >= 0
+    (None: off), the loop ended once the best live score is below the best finished one by more than end_margin
+    (include/ssasr.h).  -> decode_beam's four results and n_steps [N] int32, the loop iterations each utterance
+    executed.  ws: at least ssasr_decode_beam_ex_ws_bytes bytes, or None to allocate one."""
+    d, outs, keep = beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws,
+                                ctc=ctc is not None, coverage=float(coverage_weight) != 0.0)
+    n_steps = torch.empty(d.N, device=outs[0].device, dtype=torch.int32)
+    t = _lib.BeamTerms(float(length_bonus), float(coverage_weight), float(coverage_threshold),
+                       -1.0 if end_margin is None else float(end_margin), n_steps.data_ptr())
+    c, c_keep = ctc_prefix_struct(ctc, blank) if ctc is not None else (None, None)
+    check(_lib.load().ssasr_decode_beam_ex(C.byref(d), C.byref(c) if c is not None else None, C.byref(t), _stream()),
+          'ssasr_decode_beam_ex')
+    return outs + (n_steps,)
 
 
 # ---------------------------------------------------------------------------

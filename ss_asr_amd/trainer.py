@@ -465,8 +465,42 @@ class ASRTester(Solver):
     it (:567-569); here <ckpdir>/char_lm.cpt is loaded when it exists.
     BUILD-DEFINED: with 'ctc_weight' in asr.mdl the model is ctc.JointCTCASR, as ASRTrainer builds it, and
     asr.decode_ctc_weight (absent: 0) in (0, 1] decodes with the CTC prefix score at that weight (joint CTC /
-    attention decoding, ssasr_decode_beam_ctc, any beam size); `decode_file` then ends in `_ctc<weight>`."""
+    attention decoding, ssasr_decode_beam_ctc, any beam size); `decode_file` then ends in `_ctc<weight>`.
+    asr.decode_length_bonus, asr.decode_coverage_weight (with asr.decode_coverage_threshold, absent: 0.5) and
+    asr.decode_end_margin (absent: off) are the beam search's length bonus, coverage term and end detection
+    (ssasr_decode_beam_ex, any beam size); `decode_file` gains `_lb<bonus>`, `_cov<weight>`, `_end<margin>` for the
+    terms that are on."""
     decode_group = 32
+    TERM_KEYS = ('decode_length_bonus', 'decode_coverage_weight', 'decode_coverage_threshold', 'decode_end_margin')
+
+    @classmethod
+    def decode_terms(cls, asr_config):
+        """(ASR.decode_many's keywords for the terms asr_config turns on, their `decode_file` suffix), validated."""
+        import math
+        vals = {}
+        for key in cls.TERM_KEYS:
+            v = asr_config.get(key)
+            if v is None:
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError('asr.{} must be a finite number, got {!r}'.format(key, v))
+            vals[key] = v
+        kw, suffix = {}, ''
+        if vals.get('decode_length_bonus', 0) != 0:
+            kw['length_bonus'] = vals['decode_length_bonus']
+            suffix += '_lb{:}'.format(vals['decode_length_bonus'])
+        if vals.get('decode_coverage_weight', 0) != 0:
+            tau = vals.get('decode_coverage_threshold', 0.5)
+            if not tau > 0:
+                raise ValueError('asr.decode_coverage_threshold must be > 0, got {!r}'.format(tau))
+            kw['coverage_weight'], kw['coverage_threshold'] = vals['decode_coverage_weight'], tau
+            suffix += '_cov{:}'.format(vals['decode_coverage_weight'])
+        if 'decode_end_margin' in vals:
+            if vals['decode_end_margin'] < 0:
+                raise ValueError('asr.decode_end_margin must be >= 0, got {!r}'.format(vals['decode_end_margin']))
+            kw['end_margin'] = vals['decode_end_margin']
+            suffix += '_end{:}'.format(vals['decode_end_margin'])
+        return kw, suffix
 
     def __init__(self, config, paras):
         super().__init__(config, paras, 'asr')
@@ -505,6 +539,8 @@ class ASRTester(Solver):
         self.decode_ctc_weight = self.config['asr'].get('decode_ctc_weight', 0)
         if self.decode_ctc_weight > 0:
             self.decode_file += '_ctc{:}'.format(self.decode_ctc_weight)
+        self.decode_term_args, suffix = self.decode_terms(self.config['asr'])
+        self.decode_file += suffix
 
     def exec(self, lm_weight=None):
         """-> the decoded strings, one per utterance of the test index, in index order."""
@@ -516,16 +552,18 @@ class ASRTester(Solver):
         ctc_weight = self.decode_ctc_weight
         if isinstance(ctc_weight, bool) or not isinstance(ctc_weight, (int, float)) or not 0 <= ctc_weight <= 1:
             raise ValueError('asr.decode_ctc_weight must be a number in [0, 1], got {!r}'.format(ctc_weight))
-        self.verbose('Start decoding ({}{})'.format(
+        terms = self.decode_term_args
+        self.verbose('Start decoding ({}{}{})'.format(
             'beam search, beam size {}'.format(beam) if beam > 1 else 'greedy, beam size 1',
-            ', joint CTC / attention scores, CTC weight {}'.format(ctc_weight) if ctc_weight > 0 else ''))
+            ', joint CTC / attention scores, CTC weight {}'.format(ctc_weight) if ctc_weight > 0 else '',
+            ''.join(', {} {}'.format(k.replace('_', ' '), v) for k, v in terms.items())))
         self.verbose('Number of utts to decode : {}, {} per launch.'.format(len(self.test_set), self.decode_group))
         results, xs, x_lens = [], [], []
 
         def flush():
             if xs:
                 results.extend(self.asr_model.decode_many(xs, x_lens, self.lm, self.mapper, lm_weight,
-                                                          beam_size=beam, ctc_weight=ctc_weight))
+                                                          beam_size=beam, ctc_weight=ctc_weight, **terms))
                 del xs[:], x_lens[:]
 
         for b_ind, (x, y) in enumerate(self.test_set):

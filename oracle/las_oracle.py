@@ -118,7 +118,7 @@ class OracleSpeller(nn.Module):
         self.state_list, self.cell_list = [], []
 
     def init_rnn(self, batch, device=None):
-        z = torch.zeros(batch, self.state_size)
+        z = torch.zeros(batch, self.state_size, dtype=self.layer_1.weight_ih.dtype)   # (a .double() model runs too)
         self.state_list = [z, z]
         self.cell_list = [z, z]
 
@@ -255,6 +255,55 @@ def inverse_cdf_bounds(logits_row):
     p = np.exp(l - l.max()).astype(np.float32)
     run = np.cumsum(p, dtype=np.float32)
     return run, float(run[-1])
+
+
+def decoder_replay(model, feat, enc_len, teacher, modes, uniforms=None):
+    """The decode loop of OracleASR.forward (src/asr.py:67-110) from the encoder output `feat`
+    [B, T', E] instead of audio, with every step's rule given by the caller: modes[t] = 0 feeds the
+    label teacher[:, t + 1], 1 draws by the inverse-CDF rule of inverse_cdf_bounds from
+    uniforms[t, b], 2 takes the argmax.  `model` is an OracleASR (float64 capable: the model and
+    `feat` share a dtype); enc_len holds B ints; teacher is an integer [B, >= U + 1] tensor (or None
+    when no step is teacher forced).  Differentiable in `feat` and the model's parameters.
+
+    Returns (logits [B, U, V], attention [B, U, T'] detached, fed [U + 1, B] int64 -- fed[t] went
+    into step t, fed[0] = <sos> --, margin [U, B] float64).  margin[t, b] says how far the decision
+    of a step that is not teacher forced was from going the other way: the gap between the two
+    largest logits (mode 2), or the distance of u * total from the nearest edge of the cumulative
+    sums relative to total (mode 1); +inf on teacher-forced steps."""
+    batch = feat.shape[0]
+    steps = len(modes)
+    enc_len = [int(v) for v in enc_len]
+    model.decoder.init_rnn(batch)
+    model.attention.reset_enc_mem()
+    fed = torch.zeros(steps + 1, batch, dtype=torch.long)
+    margin = np.full((steps, batch), np.inf)
+    last = model.embed(fed[0].clone())                                    # asr.py:73
+    logits, atts = [], []
+    for t, mode in enumerate(modes):
+        alpha, ctx = model.attention(model.decoder.state_list[0], feat, enc_len)
+        cur = model.char_trans(model.decoder(torch.cat([last, ctx], dim=-1)))
+        row = cur.detach()
+        if mode == 0:
+            fed[t + 1] = teacher[:, t + 1].long()
+        elif mode == 2:
+            fed[t + 1] = torch.argmax(row, dim=-1)                        # asr.py:100
+            if row.shape[1] > 1:
+                top = torch.topk(row, 2, dim=-1).values
+                margin[t] = (top[:, 0] - top[:, 1]).numpy()
+        elif mode == 1:
+            for b in range(batch):
+                run, tot = inverse_cdf_bounds(row[b].numpy())
+                target = float(uniforms[t, b]) * tot
+                over = np.nonzero(run.astype(np.float64) > target)[0]
+                fed[t + 1, b] = int(over[0]) if len(over) else len(run) - 1
+                margin[t, b] = float(np.abs(run.astype(np.float64) - target).min()) / tot
+        else:
+            raise ValueError('step mode %r' % (mode,))
+        last = model.embed(fed[t + 1].clone())
+        logits.append(cur)
+        atts.append(alpha.detach())
+    model.attention.reset_enc_mem()
+    return torch.stack(logits, dim=1), torch.stack(atts, dim=1), fed, margin
 
 
 def masked_ce_loss(logits, y, ans_len):

@@ -274,3 +274,56 @@ def test_sae_trainer_trajectory_oracle_matches_reference(golden, name):
                 np.testing.assert_allclose(sae(x, lis).reshape(-1)[:512].numpy(), fx['eval_pred_head'], atol=1e-5, rtol=0)
                 sae.train()
     _check_final_weights(fx, w0, state())
+
+
+def test_decoder_replay_is_the_loop_of_the_pinned_forward():
+    """lo.decoder_replay (the float64 decoder-only reference of tests/test_gpu_decoder_forms.py) against
+    OracleASR.forward, which the fixtures above pin: fed the oracle encoder's output and teacher steps it gives
+    forward's logits and attention to 1e-12; with sampled and greedy steps mixed in, forward replayed on the
+    characters it fed (forced_chars) gives its logits again, every greedy pick is the argmax and every draw
+    lies inside its own inverse-CDF bracket."""
+    dims = (11, 8, 8, 4, 6)
+    torch.manual_seed(0)
+    model = lo.seeded_weights(lo.OracleASR(*dims, 1.0), 3).double()
+    rng = np.random.default_rng(7)
+    lens, U = [40, 33, 16], 6
+    x = torch.from_numpy(rng.standard_normal((3, 40, 6)))
+    for b, l in enumerate(lens):
+        x[b, l:] = 0
+    y = torch.from_numpy(rng.integers(1, 11, (3, U + 2)))
+    y[:, 0] = 0
+    with torch.no_grad():
+        enc_len, logits, att = model(x, U, teacher=y, state_len=lens)
+        feat, enc_len2 = model.encoder(x, lens)
+        assert enc_len == enc_len2 == [5, 4, 2]
+        r_logits, r_att, fed, margin = lo.decoder_replay(model, feat, enc_len, y, [0] * U)
+        assert r_logits.dtype == torch.float64 and (margin == np.inf).all()
+        assert torch.equal(fed, torch.cat([torch.zeros(1, 3, dtype=torch.long), y[:, 1:U + 1].t()]))
+        assert float((r_logits - logits).abs().max()) <= 1e-12 and float((r_att - att).abs().max()) <= 1e-12
+        assert float(r_att[1, :, 4:].abs().sum()) == 0.0 and float(r_att[2, :, 2:].abs().sum()) == 0.0
+
+        modes = [1, 0, 2, 1, 2, 0]
+        uni = rng.random((U, 3)).astype(np.float32)
+        r_logits, r_att, fed, margin = lo.decoder_replay(model, feat, enc_len, y, modes, uni)
+        _, logits, att = model(x, U, teacher=y, state_len=lens, forced_chars=fed)
+        assert float((r_logits - logits).abs().max()) <= 1e-12 and float((r_att - att).abs().max()) <= 1e-12
+        for t, mode in enumerate(modes):
+            assert np.isfinite(margin[t]).all() == (mode != 0) and (margin[t] >= 0).all()
+            for b in range(3):
+                c = int(fed[t + 1, b])
+                if mode == 0:
+                    assert c == int(y[b, t + 1])
+                elif mode == 2:
+                    assert c == int(torch.argmax(logits[b, t]))
+                    top = torch.sort(logits[b, t], descending=True).values
+                    assert abs(float(top[0] - top[1]) - margin[t, b]) <= 1e-12
+                else:
+                    run, tot = lo.inverse_cdf_bounds(logits[b, t].numpy())
+                    target = float(uni[t, b]) * tot
+                    assert (float(run[c - 1]) if c else 0.0) <= target < float(run[c])
+                    assert abs(np.abs(run.astype(np.float64) - target).min() / tot - margin[t, b]) <= 1e-12
+    # differentiable in feat and the parameters
+    f = feat.clone().requires_grad_(True)
+    lo.decoder_replay(model, f, enc_len, y, modes, uni)[0].sum().backward()
+    assert float(f.grad[1, 4:].abs().sum()) == 0.0 and float(f.grad[1, :4].abs().min()) > 0.0
+    assert model.attention.psi.weight.grad is not None and model.encoder.blstm_1.layer.weight_hh_l0.grad is None

@@ -208,7 +208,10 @@ int ssasr_attn_precompute_wgrad(const float* dcomp, const float* feat, int64_t r
 
 /* One Attention.forward call after the cache exists (src/asr.py:383-390).
  * state [B][D], w_phi [A][D] (phi.weight), comp [B][T][A], feat [B][T][E],
- * enc_len int32[B].  Two launches: q [B][A] = tanh(phi(state)) (small MFMA
+ * enc_len int32[B] (NULL: every utterance has T frames; an entry above T acts as T).
+ * Accepted: A % 4 == 0, E % 4 == 0, D % 4 == 0, T <= 16384, A <= 2048, E <= 8192, forward and
+ * backward, every E among them included (the kernels' LDS limit is raised where a shape needs
+ * more than 64 KB).  Two launches: q [B][A] = tanh(phi(state)) (small MFMA
  * kernel), then energies + masked softmax + context: att [B][T], ctx [B][E].
  * state == NULL skips the first launch and takes q as an input.
  * ws: optional workspace of ssasr_attn_step_ws_floats(B, T, A, E) floats that selects the

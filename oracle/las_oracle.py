@@ -599,12 +599,14 @@ def pyramid_explicit(x_bt, lens, weights):
 
 def attention_step_explicit(state, feat, comp, lens, w_phi):
     """One Attention.forward call after the cached psi projection
-    (src/asr.py:383-390).  Returns (alpha [B,T'], ctx [B,E])."""
+    (src/asr.py:383-390).  Returns (alpha [B,T'], ctx [B,E]).  `lens` None means
+    every utterance is T' frames long, and so does an entry above T'."""
     q = torch.tanh(state @ w_phi.t())
     energy = torch.einsum('bta,ba->bt', comp, q)
-    idx = torch.arange(feat.shape[1]).unsqueeze(0)
-    energy = energy.masked_fill(idx >= torch.as_tensor(list(lens)).unsqueeze(1),
-                                float('-inf'))
+    if lens is not None:
+        idx = torch.arange(feat.shape[1]).unsqueeze(0)
+        energy = energy.masked_fill(idx >= torch.as_tensor(list(lens)).unsqueeze(1),
+                                    float('-inf'))
     alpha = torch.softmax(energy, dim=-1)
     return alpha, torch.einsum('bt,bte->be', alpha, feat)
 

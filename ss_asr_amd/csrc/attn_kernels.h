@@ -614,6 +614,25 @@ __global__ __launch_bounds__(256) void attn_step_fwd_kernel(AttnFwd p) {
   const int EC = E / p.nch;
   const int c0 = chunk * EC;
   const int ncol4 = EC >> 2;
+  if (ncol4 > 256) {
+    // a chunk wider than the block (attn_pick_nch finds no narrower quad-aligned divisor, e.g.
+    // E = 4 * prime): each thread owns whole columns and walks the chunk's quads with a stride
+    const float* fb = p.feat + (int64_t)b * T * E + c0;
+    for (int f4 = tid; f4 < ncol4; f4 += 256) {
+      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int t = 0; t < len; ++t) {
+        const float w = sE[t];
+        const float4 h = *reinterpret_cast<const float4*>(fb + (int64_t)t * E + 4 * f4);
+        acc.x = fmaf(w, h.x, acc.x);
+        acc.y = fmaf(w, h.y, acc.y);
+        acc.z = fmaf(w, h.z, acc.z);
+        acc.w = fmaf(w, h.w, acc.w);
+      }
+      float* cx = p.ctx + (int64_t)b * p.ctx_ld + c0 + 4 * f4;
+      cx[0] = acc.x; cx[1] = acc.y; cx[2] = acc.z; cx[3] = acc.w;
+    }
+    return;
+  }
   const int tgc = 256 / ncol4;
   const int f4 = tid % ncol4, tg = tid / ncol4;
   float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -143,6 +143,20 @@ bool attn_split_taken(int64_t B, int64_t T, int64_t A, int64_t E) {
 // exchange buffers this call uses, and the word a timed-out hand-off is reported in.  With a
 // workspace the split form is the ONLY form: a shape, alignment or device that cannot take it is an
 // argument error (the caller's phase bookkeeping would otherwise drift from what was launched).
+// Dynamic LDS of the three attention launches whose byte count grows with T, A or E (long, general,
+// backward).  Up to 64 KB a launch needs nothing; above, the kernel's limit is raised first, once
+// per size and only ever upwards (`raised` is that kernel's high-water mark).  The shape limits of
+// attn_dims_ok stay below the CU's 160 KB (106,560 bytes at most), anything else is an argument error.
+int attn_dyn_lds(const void* fn, size_t bytes, size_t& raised) {
+  if (bytes <= 64 * 1024 || bytes <= raised) return SSASR_OK;
+  hipFuncAttributes fa{};
+  SSASR_HIP(hipFuncGetAttributes(&fa, fn));
+  if (bytes + fa.sharedSizeBytes > 160 * 1024) return SSASR_EARG;
+  SSASR_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+  raised = bytes;
+  return SSASR_OK;
+}
+
 int launch_attn_fwd(const AttnFwd& p, hipStream_t st, float* ws = nullptr, int phase = 0, int* status = nullptr) {
   const dim3 grid((unsigned)p.B, (unsigned)p.nch), block(256);
   const bool fast = p.A == 128 && p.E == 128 * p.nch && aligned16(p.comp) && aligned16(p.feat) &&
@@ -168,8 +182,17 @@ int launch_attn_fwd(const AttnFwd& p, hipStream_t st, float* ws = nullptr, int p
   }
   if (fast && p.T <= 128) hipLaunchKernelGGL(attn_step_fwd_fast_kernel<1>, grid, block, 0, st, p);
   else if (fast && p.T <= 256) hipLaunchKernelGGL(attn_step_fwd_fast_kernel<2>, grid, block, 0, st, p);
-  else if (fast) hipLaunchKernelGGL(attn_step_fwd_long_kernel, grid, block, attn_fwd_long_lds(p.T), st, p);
-  else hipLaunchKernelGGL(attn_step_fwd_kernel, grid, block, attn_fwd_lds(p.A, p.T), st, p);
+  else if (fast) {
+    static size_t raised = 0;
+    const size_t lds = attn_fwd_long_lds(p.T);
+    if (const int rc = attn_dyn_lds(reinterpret_cast<const void*>(attn_step_fwd_long_kernel), lds, raised)) return rc;
+    hipLaunchKernelGGL(attn_step_fwd_long_kernel, grid, block, lds, st, p);
+  } else {
+    static size_t raised = 0;
+    const size_t lds = attn_fwd_lds(p.A, p.T);
+    if (const int rc = attn_dyn_lds(reinterpret_cast<const void*>(attn_step_fwd_kernel), lds, raised)) return rc;
+    hipLaunchKernelGGL(attn_step_fwd_kernel, grid, block, lds, st, p);
+  }
   return SSASR_OK;
 }
 
@@ -184,7 +207,10 @@ int launch_phi(const float* state, const float* w_phi, float* q, int64_t B, int6
 }
 
 int launch_attn_bwd(const AttnBwd& p, hipStream_t st) {
-  hipLaunchKernelGGL(attn_step_bwd_kernel, dim3((unsigned)p.B), dim3(512), attn_bwd_lds(p.E, p.T), st, p);
+  static size_t raised = 0;
+  const size_t lds = attn_bwd_lds(p.E, p.T);
+  if (const int rc = attn_dyn_lds(reinterpret_cast<const void*>(attn_step_bwd_kernel), lds, raised)) return rc;
+  hipLaunchKernelGGL(attn_step_bwd_kernel, dim3((unsigned)p.B), dim3(512), lds, st, p);
   return SSASR_OK;
 }
 
@@ -226,7 +252,7 @@ extern "C" int ssasr_attn_step_bwd(const float* dctx, const float* datt, const f
   p.dctx = dctx; p.dctx_ld = E; p.datt = datt; p.datt_sb = T; p.att = att; p.att_sb = T; p.q = q;
   p.comp = comp; p.feat = feat; p.lens = enc_len; p.de = de; p.de_sb = T; p.dqpre = dqpre;
   p.B = (int)B; p.T = (int)T; p.A = (int)A; p.E = (int)E;
-  launch_attn_bwd(p, (hipStream_t)stream);
+  if (const int rc = launch_attn_bwd(p, (hipStream_t)stream)) return rc;
   SSASR_LAUNCH_CHECK();
   return SSASR_OK;
 }
@@ -614,7 +640,7 @@ extern "C" int ssasr_decoder_bwd(const ssasr_decoder* dp, const ssasr_decoder_gr
       ab.de = g.ws_de + t * T; ab.de_sb = U * T;
       ab.dqpre = g.ws_dqpre + t * B * A;
       ab.B = (int)B; ab.T = (int)T; ab.A = (int)A; ab.E = (int)E;
-      launch_attn_bwd(ab, st);
+      if ((rc = launch_attn_bwd(ab, st))) return rc;
     }
   }
   SSASR_LAUNCH_CHECK();

@@ -327,3 +327,46 @@ def test_decoder_replay_is_the_loop_of_the_pinned_forward():
     lo.decoder_replay(model, f, enc_len, y, modes, uni)[0].sum().backward()
     assert float(f.grad[1, 4:].abs().sum()) == 0.0 and float(f.grad[1, :4].abs().min()) > 0.0
     assert model.attention.psi.weight.grad is not None and model.encoder.blstm_1.layer.weight_hh_l0.grad is None
+
+
+@pytest.mark.parametrize('lens', [[9, 8, 4, 1], [12, 9, 1, 30], None], ids=['inside', 'above_T', 'none'])
+def test_attention_step_explicit_is_masked_softmax_and_bmm(lens):
+    """lo.attention_step_explicit (the float64 reference of tests/test_gpu_attention_forms.py and of the
+    attention cases in tests/test_gpu_kernels.py) against an independent formulation: an additive -inf mask,
+    torch.softmax and torch.bmm, with autograd on both sides.  Lengths 1, T', above T' (which must act as T')
+    and None (every utterance full length); frames at or past an utterance's length get alpha exactly 0 and
+    carry no gradient."""
+    B, T, A, E, D = 4, 9, 8, 12, 6
+    g = torch.Generator().manual_seed(11)
+    draw = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)       # noqa: E731
+    vals = [draw(B, D), draw(B, T, E), torch.tanh(draw(B, T, A)), draw(A, D)]
+    ga, gc = draw(B, T), draw(B, E)
+    eff = [T] * B if lens is None else [min(int(l), T) for l in lens]
+
+    a = [v.clone().requires_grad_(True) for v in vals]
+    alpha, ctx = lo.attention_step_explicit(a[0], a[1], a[2], lens, a[3])
+    ((alpha * ga).sum() + (ctx * gc).sum()).backward()
+
+    b = [v.clone().requires_grad_(True) for v in vals]
+    state, feat, comp, w_phi = b
+    q = torch.tanh(torch.nn.functional.linear(state, w_phi))
+    mask = torch.zeros(B, T, dtype=torch.float64)
+    for i, l in enumerate(eff):
+        mask[i, l:] = float('-inf')
+    want_alpha = torch.softmax(torch.bmm(comp, q.unsqueeze(2)).squeeze(2) + mask, dim=1)
+    want_ctx = torch.bmm(want_alpha.unsqueeze(1), feat).squeeze(1)
+    ((want_alpha * ga).sum() + (want_ctx * gc).sum()).backward()
+
+    assert alpha.dtype == torch.float64 and alpha.shape == (B, T) and ctx.shape == (B, E)
+    alpha, ctx, want_alpha, want_ctx = (t.detach() for t in (alpha, ctx, want_alpha, want_ctx))
+    assert float((alpha - want_alpha).abs().max()) <= 1e-14 and float((ctx - want_ctx).abs().max()) <= 1e-13
+    assert float((alpha.sum(1) - 1).abs().max()) <= 1e-14
+    for x, y, name in zip(a, b, ['state', 'feat', 'comp', 'w_phi']):
+        assert float((x.grad - y.grad).abs().max()) <= 1e-12, name
+    for i, l in enumerate(eff):
+        assert float(alpha[i, l:].abs().sum()) == 0.0
+        assert float(a[1].grad[i, l:].abs().sum()) == 0.0 and float(a[2].grad[i, l:].abs().sum()) == 0.0
+        assert float(alpha[i, :l].min()) > 0.0
+    if lens is not None and max(lens) > T:       # an entry above T' is the full-length utterance
+        full, _ = lo.attention_step_explicit(vals[0], vals[1], vals[2], eff, vals[3])
+        assert torch.equal(full, alpha)

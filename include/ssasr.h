@@ -23,7 +23,7 @@
  *   - return 0 on success, a negative value for an argument error, a positive
  *     hipError_t for a HIP failure.
  *
- * ABI history.  Added under 16 without changing anything older (the version number stays): beam search --
+ * ABI history.  Added under 16 without changing anything older (the version number stays): ssasr_gemm_tile_choice; beam search --
  * ssasr_beam, ssasr_decode_beam_ws_bytes, ssasr_decode_beam; joint CTC / attention decoding -- ssasr_ctc_prefix,
  * ssasr_decode_beam_ctc_ws_bytes, ssasr_decode_beam_ctc; length bonus, coverage term and end detection in the beam
  * search -- ssasr_beam_terms, ssasr_decode_beam_ex_ws_bytes, ssasr_decode_beam_ex.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
@@ -55,6 +55,7 @@ int ssasr_abi_version(void);
  * SSASR_NO_PERSISTENT_DECODER, SSASR_NO_PERSISTENT_DECODER_BWD, SSASR_PERSIST_DELAY_FWD,
  * SSASR_PERSIST_DELAY_BWD, SSASR_GEMM_TILE (0 the launcher's cost model, 64 | 128 tile kernels, 256 the wide stream-K kernel,
  * 255 the wide kernel on whole tiles), SSASR_GEMM_WIDE (1; 0: the cost model never picks the wide kernel), SSASR_GEMM_X6, SSASR_GEMM_KCAT,
+ * SSASR_GEMM_EPI (0; 1: the wide kernel's stores without their LDS staging, 2 | 3: direct | staged stores into the stream-K slabs instead of C),
  * SSASR_GEMM_TRACE_LO / _HI (set_option only: device address of a phase-stamp buffer, tools/gemm_trace.py), SSASR_WGRAD_FUSED, SSASR_BPTT_ONE_LAUNCH (1: a layer's BPTT ranges as one launch, the second stream released by in-kernel progress words), SSASR_NO_WINDOWS,
  * SSASR_LAST_SEG_PCT, SSASR_TAIL_INLINE, SSASR_NO_RESIDENCY_CHECK, SSASR_NO_TSAVE, SSASR_ATTN_RPH,
  * SSASR_TEST_DROP_TILE / SSASR_TEST_DROP_ATTN_SLICE / SSASR_TEST_DROP_DEC_SLICE (fault injection for the
@@ -91,6 +92,15 @@ int ssasr_gemm_f32(int ta, int tb, int64_t M, int64_t N, int64_t K, float alpha,
                    int64_t lda, const float* B, int64_t ldb, float beta, float* C, int64_t ldc,
                    const float* bias, int act, int64_t batch, int64_t strideA, int64_t strideB,
                    int64_t strideC, int splitk, void* stream);
+
+/* Which kernel family the launcher takes for a product of densely stored operands (lda = K or M, ldb = K or N, batch
+ * strides M K and N K) under the current switches: 64 | 128 = the tile kernels with that block tile, 256 = the wide
+ * kernel as a stream-K grid, 255 = the wide kernel on whole tiles (forced by SSASR_GEMM_TILE only); 0 for an empty
+ * product, negative for an argument error.  kcat: K segments per product (0 | 1: none), aligned16: both operands start
+ * on 16-byte boundaries.  A pure host function (no device needed): it labels a timing with the kernel that ran and
+ * pins the decision table in a test.  A product chosen as 256 still takes the tile kernels on a fifth stream (above). */
+int ssasr_gemm_tile_choice(int ta, int tb, int64_t M, int64_t N, int64_t K, int64_t batch, int splitk, int kcat,
+                           int aligned16);
 
 /* Bidirectional LSTM layer with packed-sequence semantics.
  * Logical input [S steps][N columns][I]: element (s, n, i) at

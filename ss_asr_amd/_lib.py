@@ -88,6 +88,7 @@ SIGNATURES = {
     'ssasr_events_destroy': (I32, [P]),
     'ssasr_gemm_f32': (I32, [I32, I32, I64, I64, I64, F32, P, I64, P, I64, F32, P, I64, P, I32,
                              I64, I64, I64, I64, I32, P]),
+    'ssasr_gemm_tile_choice': (I32, [I32, I32, I64, I64, I64, I64, I32, I32, I32]),
     'ssasr_bilstm_fwd': (I32, [P, I64, I64, I64, I64, I64, I64, P] + [P] * 8 +
                          [P, I64, I64, P, P, P, P, P, I32, P, P]),
     'ssasr_bilstm_tsave_floats': (I64, [I64, I64, I64]),

@@ -17,8 +17,9 @@
 // both operands, which lets a K-contiguous operand be fetched with a single
 // ds_read_b128 per 16x16 fragment.
 #include <atomic>
+#include <climits>
 #include <mutex>
-#include <cstdlib>
+#include <type_traits>
 #include "../../include/ssasr.h"
 #include "common.h"
 
@@ -223,15 +224,82 @@ __device__ __forceinline__ float gemm_act(int act, float v) {
   }
 }
 
+// What an epilogue needs of its tile's descriptor, batch offsets applied (the wide kernel's values may leave after the
+// loaders of the NEXT part have been set up, so the few fields are copied out)
+struct EpiDesc {
+  float* C;
+  RowMap mc;
+  const float* b1;
+  const float* b2;
+  float alpha, beta;
+  int act, M, N;
+};
+__device__ __forceinline__ EpiDesc epi_desc(const GemmDesc& g, int bz) {
+  return EpiDesc{g.C + (int64_t)bz * g.sc, g.mc, g.bias1 ? g.bias1 + (int64_t)bz * g.sbias : nullptr,
+                 g.bias2 ? g.bias2 + (int64_t)bz * g.sbias : nullptr, g.alpha, g.beta, g.act, g.M, g.N};
+}
+
+// One output value, scaled and biased, to *dst.  add: ADDED atomically (split-K slices, stream-K parts).
+__device__ __forceinline__ void epi_store_one(const EpiDesc& g, float* dst, float v, bool add) {
+  if (add) {
+    atomicAdd(dst, v);
+  } else {
+    v = gemm_act(g.act, v);
+    if (g.beta != 0.f) v += g.beta * *dst;
+    *dst = v;
+  }
+}
+
+// A lane's four consecutive columns nb .. nb + 3 of the output row at C + rowoff, scaled and biased.  vecC: 16-byte
+// accesses to C are legal.  (C and rowoff stay apart and every address is formed as C + rowoff + ..: with the row
+// pointer passed ready-made the wide kernel's store-mode instantiations, at 256 VGPRs, spill 16 registers more.)
+__device__ __forceinline__ void epi_store_quad(const EpiDesc& g, float* C, int64_t rowoff, int nb, float (&v)[4], bool add,
+                                               bool vecC) {
+  if (add) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (nb + e < g.N) atomicAdd(C + rowoff + nb + e, v[e]);
+    return;
+  }
+  if (g.act == 3) {
+    // columns come in (re, im) pairs (a DFT against a basis whose cos / sin rows are interleaved): the
+    // lane's four columns are two bins, C[m][n / 2] = re^2 + im^2 -- the power spectrum leaves the
+    // product's epilogue, the complex spectrum never exists in memory (frontend.hip)
+    float* dst = C + rowoff + (nb >> 1);
+    if (nb + 1 < g.N) dst[0] = v[0] * v[0] + v[1] * v[1];
+    if (nb + 3 < g.N) dst[1] = v[2] * v[2] + v[3] * v[3];
+    return;
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = gemm_act(g.act, v[e]);
+  if (vecC && nb + 3 < g.N) {
+    float4* dst = reinterpret_cast<float4*>(C + rowoff + nb);
+    float4 o = make_float4(v[0], v[1], v[2], v[3]);
+    if (g.beta != 0.f) {
+      const float4 c0 = *dst;
+      o.x += g.beta * c0.x; o.y += g.beta * c0.y; o.z += g.beta * c0.z; o.w += g.beta * c0.w;
+    }
+    *dst = o;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (nb + e >= g.N) continue;
+      float o = v[e];
+      if (g.beta != 0.f) o += g.beta * C[rowoff + nb + e];
+      C[rowoff + nb + e] = o;
+    }
+  }
+}
+
+// lead: this K slice brings the biases; add: see epi_store_one
 template <int TM, int TN, int WM, int WN, bool TR>
-__device__ __forceinline__ void gemm_epilogue(const GemmDesc& g, const f32x4 (&acc)[TM][TN], int m0, int n0,
-                                              int wm, int wn, int r, int q, int bz, int kz) {
+__device__ __forceinline__ void gemm_epilogue(const EpiDesc& g, const f32x4 (&acc)[TM][TN], int m0, int n0,
+                                              int wm, int wn, int r, int q, bool lead, bool add) {
+  float* C = g.C;
+  const float* b1 = g.b1;
+  const float* b2 = g.b2;
   if (!TR) {
     // Epilogue.  D fragment: column = lane & 15, row = 4 * (lane >> 4) + reg.
-    float* C = g.C + (int64_t)bz * g.sc;
-    const float* b1 = g.bias1 ? g.bias1 + (int64_t)bz * g.sbias : nullptr;
-    const float* b2 = g.bias2 ? g.bias2 + (int64_t)bz * g.sbias : nullptr;
-    const bool lead = (kz == 0);
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -248,13 +316,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmDesc& g, const f32x4 (&a
             if (b1) v += b1[n];
             if (b2) v += b2[n];
           }
-          if (g.splitk > 1) {
-            atomicAdd(C + rowoff + n, v);
-          } else {
-            v = gemm_act(g.act, v);
-            if (g.beta != 0.f) v += g.beta * C[rowoff + n];
-            C[rowoff + n] = v;
-          }
+          epi_store_one(g, C + rowoff + n, v, add);
         }
       }
     }
@@ -265,10 +327,6 @@ __device__ __forceinline__ void gemm_epilogue(const GemmDesc& g, const f32x4 (&a
   // consecutive output COLUMNS n, so a lane owns 16 contiguous bytes of C and a store instruction
   // writes 64-byte runs of 16 rows (four times fewer store instructions than one float per lane;
   // the K = 80 input projection of the first layer is bound by its 0.4 GB of output).
-  float* C = g.C + (int64_t)bz * g.sc;
-  const float* b1 = g.bias1 ? g.bias1 + (int64_t)bz * g.sbias : nullptr;
-  const float* b2 = g.bias2 ? g.bias2 + (int64_t)bz * g.sbias : nullptr;
-  const bool lead = (kz == 0);
   const bool vecC = map_vec_ok_dev(g.mc) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0);
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
@@ -288,42 +346,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmDesc& g, const f32x4 (&a
           if (b2) v[e] += b2[nb + e];
         }
       }
-      if (g.splitk > 1) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (nb + e < g.N) atomicAdd(C + rowoff + nb + e, v[e]);
-        continue;
-      }
-      if (g.act == 3) {
-        // columns come in (re, im) pairs (a DFT against a basis whose cos / sin rows are interleaved): the
-        // lane's four columns are two bins, C[m][n / 2] = re^2 + im^2 -- the power spectrum leaves the
-        // product's epilogue, the complex spectrum never exists in memory (frontend.hip)
-        float* dst = C + rowoff + (nb >> 1);
-        if (nb + 1 < g.N) dst[0] = v[0] * v[0] + v[1] * v[1];
-        if (nb + 3 < g.N) dst[1] = v[2] * v[2] + v[3] * v[3];
-        continue;
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[e] = gemm_act(g.act, v[e]);
-      }
-      if (vecC && nb + 3 < g.N) {
-        float4* dst = reinterpret_cast<float4*>(C + rowoff + nb);
-        float4 o = make_float4(v[0], v[1], v[2], v[3]);
-        if (g.beta != 0.f) {
-          const float4 c0 = *dst;
-          o.x += g.beta * c0.x; o.y += g.beta * c0.y; o.z += g.beta * c0.z; o.w += g.beta * c0.w;
-        }
-        *dst = o;
-      } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (nb + e >= g.N) continue;
-          float o = v[e];
-          if (g.beta != 0.f) o += g.beta * C[rowoff + nb + e];
-          C[rowoff + nb + e] = o;
-        }
-      }
+      epi_store_quad(g, C, rowoff, nb, v, add, vecC);
     }
   }
 }
@@ -423,7 +446,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmDesc g, bool vecA, bo
     buf ^= 1;
   }
 
-  gemm_epilogue<TM, TN, WM, WN, TR>(g, acc, m0, n0, wm, wn, r, q, bz, kz);
+  gemm_epilogue<TM, TN, WM, WN, TR>(epi_desc(g, bz), acc, m0, n0, wm, wn, r, q, kz == 0, g.splitk > 1);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -455,20 +478,25 @@ template <int BMN, int NP = 3> struct XGeom {
   static constexpr int BYTES = NP * PLANE;
 };
 
-// four consecutive k of one row -> 8 bytes in each plane
-template <int BMN, int NP = 3>
-__device__ __forceinline__ void x_store4(char* img, int row, int slot, float k0, float k1, float k2, float k3) {
-  char* dst = img + row * XROW + ((slot ^ ((row >> 1) & 6)) * 8);    // chunk (slot >> 1) ^ ((row >> 2) & 3)
+// four floats -> 8 bytes at `dst` in each of the NP planes
+template <int BMN, int NP>
+__device__ __forceinline__ void x_put4(char* dst, const float4& v) {
   if constexpr (NP == 1) {
-    *reinterpret_cast<uint2*>(dst) = make_uint2(x6_pack(k0, k1), x6_pack(k2, k3));
+    *reinterpret_cast<uint2*>(dst) = make_uint2(x6_pack(v.x, v.y), x6_pack(v.z, v.w));
     return;
   }
   uint32_t a1, a2, a3, b1, b2, b3;
-  x_split2(k0, k1, a1, a2, a3);
-  x_split2(k2, k3, b1, b2, b3);
+  x_split2(v.x, v.y, a1, a2, a3);
+  x_split2(v.z, v.w, b1, b2, b3);
   *reinterpret_cast<uint2*>(dst) = make_uint2(a1, b1);
   *reinterpret_cast<uint2*>(dst + XGeom<BMN>::PLANE) = make_uint2(a2, b2);
   *reinterpret_cast<uint2*>(dst + 2 * XGeom<BMN>::PLANE) = make_uint2(a3, b3);
+}
+
+// four consecutive k of one row of a K-contiguous image
+template <int BMN, int NP = 3>
+__device__ __forceinline__ void x_store4(char* img, int row, int slot, const float4& v) {
+  x_put4<BMN, NP>(img + row * XROW + ((slot ^ ((row >> 1) & 6)) * 8), v);    // chunk (slot >> 1) ^ ((row >> 2) & 3)
 }
 
 // MN-contiguous operand: the image keeps the source orientation -- three planes [32 k][BMN mn] of bf16,
@@ -491,54 +519,25 @@ __device__ __forceinline__ int xt_off(int k, int mn) {       // byte offset of (
   return k * (BMN * 2) + ((((mn >> 4) ^ xt_swz<BMN, W32>(k)) << 5) | ((mn & 15) * 2));
 }
 
-template <int BMN, int NT = 256, bool W32 = false, int NP = 3>
-struct XTLoader : TileLoader<BMN, true, NT> {
-  static constexpr int NV = TileGeom<BMN, true, NT>::NV;
+// The fp32 kernel's loader, stored through the split: T as above, otherwise the K-contiguous image of x_store4
+template <int BMN, bool T, int NT = 256, bool W32 = false, int NP = 3>
+struct XLoader : TileLoader<BMN, T, NT> {
+  static constexpr int NV = TileGeom<BMN, T, NT>::NV;
   static constexpr int PER_ROW = BMN / 4;
   int tid_;
-  __device__ __forceinline__ void init(const Operand& op, int mn0, int k0, int tid, int) {
-    TileLoader<BMN, true, NT>::init(op, mn0, k0, tid);
+  __device__ __forceinline__ void init(const Operand& op, int mn0, int k0, int tid) {
+    TileLoader<BMN, T, NT>::init(op, mn0, k0, tid);
     tid_ = tid;
   }
   __device__ __forceinline__ void store(char* img, const float4 (&v)[NV]) const {
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int f = tid_ + i * NT;
-      char* dst = img + xt_off<BMN, W32>(f / PER_ROW, (f % PER_ROW) * 4);
-      if constexpr (NP == 1) {
-        *reinterpret_cast<uint2*>(dst) = make_uint2(x6_pack(v[i].x, v[i].y), x6_pack(v[i].z, v[i].w));
-        continue;
-      }
-      uint32_t a1, a2, a3, b1, b2, b3;
-      x_split2(v[i].x, v[i].y, a1, a2, a3);
-      x_split2(v[i].z, v[i].w, b1, b2, b3);
-      *reinterpret_cast<uint2*>(dst) = make_uint2(a1, b1);
-      *reinterpret_cast<uint2*>(dst + XGeom<BMN>::PLANE) = make_uint2(a2, b2);
-      *reinterpret_cast<uint2*>(dst + 2 * XGeom<BMN>::PLANE) = make_uint2(a3, b3);
+      if constexpr (T) x_put4<BMN, NP>(img + xt_off<BMN, W32>(f / PER_ROW, (f % PER_ROW) * 4), v[i]);
+      else x_store4<BMN, NP>(img, f / (BK / 4), f % (BK / 4), v[i]);
     }
   }
 };
-
-// K-contiguous operand: the fp32 kernel's loader, stored through the split
-template <int BMN, int NT = 256, int NP = 3>
-struct XNLoader : TileLoader<BMN, false, NT> {
-  static constexpr int NV = TileGeom<BMN, false, NT>::NV;
-  __device__ __forceinline__ void init(const Operand& op, int mn0, int k0, int tid, int) {
-    TileLoader<BMN, false, NT>::init(op, mn0, k0, tid);
-    this->tid_ = tid;
-  }
-  int tid_;
-  __device__ __forceinline__ void store(char* img, const float4 (&v)[NV]) const {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int f = tid_ + i * NT;
-      x_store4<BMN, NP>(img, f / (BK / 4), f % (BK / 4), v[i].x, v[i].y, v[i].z, v[i].w);
-    }
-  }
-};
-
-template <int BMN, bool T, int NT = 256, bool W32 = false, int NP = 3> struct XLoaderOf { using type = XNLoader<BMN, NT, NP>; static constexpr int NV = TileGeom<BMN, false, NT>::NV; };
-template <int BMN, int NT, bool W32, int NP> struct XLoaderOf<BMN, true, NT, W32, NP> { using type = XTLoader<BMN, NT, W32, NP>; static constexpr int NV = TileGeom<BMN, true, NT>::NV; };
 
 template <int BMN>
 __device__ __forceinline__ bf16x8 x_frag(const char* img, int plane, int row, int q) {
@@ -568,6 +567,49 @@ __device__ __forceinline__ bf16x8 x_operand(const char* img, int plane, int base
 // SEG (GemmDesc::nseg > 0, TA = TB = true): the column tiles of the launch belong to up to two segments, each
 // with its own B / C / K window over shared A rows; the workgroups of the first column tile also sum the
 // columns of the A rows they stream (GemmDesc::colsum).  One launch = one pass over A.
+// Which segment column tile bx (of width BN) of batch bz belongs to: g becomes that segment's product and bx its column
+// tile inside the segment.  Returns whether this tile also sums the columns of its A rows.
+template <int BN>
+__device__ __forceinline__ bool seg_select(const GemmDesc& gin, GemmDesc& g, int& bx, int bz) {
+  const int nt0 = (gin.seg[0].N + BN - 1) / BN;
+  const int sidx = bx >= nt0 ? 1 : 0;
+  const bool do_colsum = bx == 0 && gin.colsum[bz] != nullptr;
+  if (sidx) bx -= nt0;
+  g.A = gin.seg[sidx].A[bz]; g.sa = 0;
+  g.B = gin.seg[sidx].B[bz]; g.sb = 0; g.mb = gin.seg[sidx].mb;
+  g.C = gin.seg[sidx].C[bz]; g.sc = 0; g.mc = RowMap{gin.seg[sidx].ldc, 0, 0, 0};
+  g.N = gin.seg[sidx].N; g.K = gin.seg[sidx].K;
+  return do_colsum;
+}
+
+// Column sums of a workgroup's BM columns (workgroup-uniform call): thread tid brings the sums of columns
+// m0 + 4 * (tid % (BM / 4)) .. + 3 over the K steps it loaded; the NT / (BM / 4) threads of a column quad meet in
+// LDS (`red`: NT float4 that are no longer read as an operand image) and the totals are added to cs (and cs2).
+template <int NT, int BM>
+__device__ __forceinline__ void colsum_reduce(float4* red, int tid, const float4& csum, int m0, int M, float alpha,
+                                              float* cs, float* cs2) {
+  constexpr int PER_ROW = BM / 4;
+  red[tid] = csum;
+  __syncthreads();
+  if (tid < PER_ROW) {
+    float4 v = red[tid];
+#pragma unroll
+    for (int k = 1; k < NT / PER_ROW; ++k) {
+      const float4 a = red[tid + k * PER_ROW];
+      v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
+    }
+    const int m = m0 + 4 * tid;
+    const float vv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (m + e < M) {
+        atomicAdd(cs + m + e, alpha * vv[e]);
+        if (cs2) atomicAdd(cs2 + m + e, alpha * vv[e]);
+      }
+    }
+  }
+}
+
 template <int BM, int BN, bool TA, bool TB, bool TR, bool SEG = false, int NP = 3>
 __global__ __launch_bounds__(256) void gemm_x6_kernel(GemmDesc gin, bool vecA, bool vecB) {
   constexpr int WM = BM / 2, WN = BN / 2;      // per-wave tile
@@ -585,17 +627,7 @@ __global__ __launch_bounds__(256) void gemm_x6_kernel(GemmDesc gin, bool vecA, b
   const int bz = bzz / g.splitk;
   const int kz = bzz - bz * g.splitk;
   bool do_colsum = false;
-  if constexpr (SEG) {
-    // which segment this column tile belongs to; from here on the descriptor is that segment's product
-    const int nt0 = (gin.seg[0].N + BN - 1) / BN;
-    const int sidx = bx >= nt0 ? 1 : 0;
-    do_colsum = bx == 0 && gin.colsum[bz] != nullptr;
-    if (sidx) bx -= nt0;
-    g.A = gin.seg[sidx].A[bz]; g.sa = 0;
-    g.B = gin.seg[sidx].B[bz]; g.sb = 0; g.mb = gin.seg[sidx].mb;
-    g.C = gin.seg[sidx].C[bz]; g.sc = 0; g.mc = RowMap{gin.seg[sidx].ldc, 0, 0, 0};
-    g.N = gin.seg[sidx].N; g.K = gin.seg[sidx].K;
-  }
+  if constexpr (SEG) do_colsum = seg_select<BN>(gin, g, bx, bz);      // from here on the descriptor is that segment's product
   const int m0 = by * BM, n0 = bx * BN;
 
   // kcat > 1 (splitk == 1, K % BK == 0, dense K layouts: checked by the launcher): the K loop runs over kcat
@@ -610,18 +642,18 @@ __global__ __launch_bounds__(256) void gemm_x6_kernel(GemmDesc gin, bool vecA, b
 
   Operand opA{g.A + (int64_t)bz * g.sa, g.ma, g.M, vecA};
   Operand opB{g.B + (int64_t)bz * g.sb, g.mb, g.N, vecB};
-  typename XLoaderOf<BM, TA, 256, false, NP>::type la;
-  typename XLoaderOf<BN, TB, 256, false, NP>::type lb;
-  la.init(opA, m0, kbeg, tid, 0);
-  lb.init(opB, n0, kbeg, tid, 128);
+  XLoader<BM, TA, 256, false, NP> la;
+  XLoader<BN, TB, 256, false, NP> lb;
+  la.init(opA, m0, kbeg, tid);
+  lb.init(opB, n0, kbeg, tid);
   const bool interior = vecA && vecB && (!TA || g.M % 4 == 0) && (!TB || g.N % 4 == 0);
   // column sums of the A rows this workgroup streams: thread tid always holds the same four columns
-  // m0 + 4 * (tid % (BM / 4)) .. + 3 of every K step (XTLoader's layout), so it sums them in registers
+  // m0 + 4 * (tid % (BM / 4)) .. + 3 of every K step (the MN-contiguous loader's layout), so it sums them in registers
   float4 csum = make_float4(0.f, 0.f, 0.f, 0.f);
-  auto colsum_add = [&](const float4 (&v)[XLoaderOf<BM, TA>::NV]) {
+  auto colsum_add = [&](const float4 (&v)[decltype(la)::NV]) {
     if (la.idx[0] < g.M) {        // (columns past M alias valid ones on the predicate-free path)
 #pragma unroll
-      for (int i = 0; i < XLoaderOf<BM, TA>::NV; ++i) { csum.x += v[i].x; csum.y += v[i].y; csum.z += v[i].z; csum.w += v[i].w; }
+      for (int i = 0; i < decltype(la)::NV; ++i) { csum.x += v[i].x; csum.y += v[i].y; csum.z += v[i].z; csum.w += v[i].w; }
     }
   };
 
@@ -631,7 +663,7 @@ __global__ __launch_bounds__(256) void gemm_x6_kernel(GemmDesc gin, bool vecA, b
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  float4 ra[XLoaderOf<BM, TA>::NV], rb[XLoaderOf<BN, TB>::NV];
+  float4 ra[decltype(la)::NV], rb[decltype(lb)::NV];
   if (kbeg < kend) {
     if (interior && kbeg + BK <= kend) { la.load_fast(ra); lb.load_fast(rb); }
     else { la.load_guarded(ra, kbeg, kend, vecA); lb.load_guarded(rb, kbeg, kend, vecB); }
@@ -690,31 +722,10 @@ __global__ __launch_bounds__(256) void gemm_x6_kernel(GemmDesc gin, bool vecA, b
 #undef SSASR_X6_STEP
     __syncthreads();          // the next tile is in place
   }
-  gemm_epilogue<TM, TN, WM, WN, TR>(g, acc, m0, n0, wm, wn, r, q, bz, kz);
+  gemm_epilogue<TM, TN, WM, WN, TR>(epi_desc(g, bz), acc, m0, n0, wm, wn, r, q, kz == 0, g.splitk > 1);
   if constexpr (SEG) {
-    if (do_colsum) {          // (workgroup-uniform) the 256 / (BM / 4) threads of a column quad meet in LDS
-      constexpr int PER_ROW = BM / 4;
-      float4* red = reinterpret_cast<float4*>(xlds);          // the operand image is no longer read
-      red[tid] = csum;
-      __syncthreads();
-      if (tid < PER_ROW) {
-        float4 v = red[tid];
-#pragma unroll
-        for (int k = 1; k < 256 / PER_ROW; ++k) {
-          const float4 a = red[tid + k * PER_ROW];
-          v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-        }
-        const int m = m0 + 4 * tid;
-        const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if (m + e < g.M) {
-            atomicAdd(gin.colsum[bz] + m + e, g.alpha * vv[e]);
-            if (gin.colsum2[bz]) atomicAdd(gin.colsum2[bz] + m + e, g.alpha * vv[e]);
-          }
-        }
-      }
-    }
+    if (do_colsum)            // (workgroup-uniform; the operand image is no longer read)
+      colsum_reduce<256, BM>(reinterpret_cast<float4*>(xlds), tid, csum, m0, g.M, g.alpha, gin.colsum[bz], gin.colsum2[bz]);
   }
 }
 
@@ -760,17 +771,6 @@ __device__ __forceinline__ bf16x8 x32_operand(const char* img, int plane, int ba
   else return x32_frag<BMN>(img, plane, base, h, lane);
 }
 
-// What an epilogue of the wide kernel needs of its tile's descriptor (a part's values may leave after the loaders of
-// the NEXT part have been set up, so the few fields are copied out)
-struct EpiDesc {
-  float* C;
-  RowMap mc;
-  const float* b1;
-  const float* b2;
-  float alpha, beta;
-  int act, M, N;
-};
-
 // Epilogue of the wide kernel: acc[i][j] = the wave's 32 x 32 blocks (D layout of v_mfma_f32_32x32x16_bf16: column =
 // lane & 31, row = 8 (reg >> 2) + 4 (lane >> 5) + (reg & 3)).  TR: the products were accumulated transposed, so the
 // lane's column is the output ROW m and four consecutive registers are four consecutive output COLUMNS (16-byte stores).
@@ -799,13 +799,7 @@ __device__ __forceinline__ void gemm_epilogue32(const EpiDesc& g, const f32x16 (
             if (b1) v += b1[n];
             if (b2) v += b2[n];
           }
-          if (add) {
-            atomicAdd(C + rowoff + n, v);
-          } else {
-            v = gemm_act(g.act, v);
-            if (g.beta != 0.f) v += g.beta * C[rowoff + n];
-            C[rowoff + n] = v;
-          }
+          epi_store_one(g, C + rowoff + n, v, add);
         }
       }
     return;
@@ -850,37 +844,7 @@ __device__ __forceinline__ void gemm_epilogue32(const EpiDesc& g, const f32x16 (
             if (b2) v[e] += b2[nb + e];
           }
         }
-        if (add) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            if (nb + e < g.N) atomicAdd(C + rowoff + nb + e, v[e]);
-          continue;
-        }
-        if (g.act == 3) {        // (re, im) column pairs -> power (see gemm_epilogue)
-          float* dst = C + rowoff + (nb >> 1);
-          if (nb + 1 < g.N) dst[0] = v[0] * v[0] + v[1] * v[1];
-          if (nb + 3 < g.N) dst[1] = v[2] * v[2] + v[3] * v[3];
-          continue;
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = gemm_act(g.act, v[e]);
-        if (vecC && nb + 3 < g.N) {
-          float4* dst = reinterpret_cast<float4*>(C + rowoff + nb);
-          float4 o = make_float4(v[0], v[1], v[2], v[3]);
-          if (g.beta != 0.f) {
-            const float4 c0 = *dst;
-            o.x += g.beta * c0.x; o.y += g.beta * c0.y; o.z += g.beta * c0.z; o.w += g.beta * c0.w;
-          }
-          *dst = o;
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            if (nb + e >= g.N) continue;
-            float o = v[e];
-            if (g.beta != 0.f) o += g.beta * C[rowoff + nb + e];
-            C[rowoff + nb + e] = o;
-          }
-        }
+        epi_store_quad(g, C, rowoff, nb, v, add, vecC);
       }
   }
 }
@@ -967,8 +931,10 @@ __device__ __forceinline__ void gemm_epilogue32_rows(const EpiDesc& e, const f32
     const int m = m0 + row;
     if (m >= e.M || nb >= e.N) continue;
     float v[4] = {e.alpha * a.x + bias[0], e.alpha * a.y + bias[1], e.alpha * a.z + bias[2], e.alpha * a.w + bias[3]};
+    // From here on this is epi_store_quad's store half, written out: behind the helper two of the store-mode
+    // instantiations spill one register more (tools/kernel_resources.sh).  A change to either belongs in both.
     float* dst = e.C + rm_off(e.mc, m);
-    if (e.act == 3) {        // (re, im) column pairs -> power (see gemm_epilogue)
+    if (e.act == 3) {        // (re, im) column pairs -> power (see epi_store_quad)
       if (nb + 1 < e.N) dst[nb >> 1] = v[0] * v[0] + v[1] * v[1];
       if (nb + 3 < e.N) dst[(nb >> 1) + 1] = v[2] * v[2] + v[3] * v[3];
       continue;
@@ -1018,9 +984,9 @@ __global__ __launch_bounds__(WIDE_NT, 2) void gemm_x6w_kernel(GemmDesc gin, bool
 
   // ---- state of the part being computed (the loaders are opened one part AHEAD of the epilogue: see the loop's end)
   GemmDesc g = gin;
-  typename XLoaderOf<BM, TA, NT, true>::type la;
-  typename XLoaderOf<BN, TB, NT, true>::type lb;
-  float4 ra[XLoaderOf<BM, TA, NT>::NV], rb[XLoaderOf<BN, TB, NT>::NV];     // values of the tile AFTER the one in LDS
+  XLoader<BM, TA, NT, true> la;
+  XLoader<BN, TB, NT, true> lb;
+  float4 ra[decltype(la)::NV], rb[decltype(lb)::NV];     // values of the tile AFTER the one in LDS
   int t = 0, ks0 = 0, ks1 = 0, bz = 0, m0 = 0, n0 = 0, kbeg = 0, kend = 0;
   int64_t jumpA = 0, jumpB = 0;
   bool do_colsum = false;
@@ -1047,17 +1013,7 @@ __global__ __launch_bounds__(WIDE_NT, 2) void gemm_x6w_kernel(GemmDesc gin, bool
     bz = tq / plan.tiles_y;
     g = gin;
     do_colsum = false;
-    if constexpr (SEG) {
-      // which segment this column tile belongs to; from here on the descriptor is that segment's product
-      const int nt0 = (gin.seg[0].N + BN - 1) / BN;
-      const int sidx = bx >= nt0 ? 1 : 0;
-      do_colsum = bx == 0 && gin.colsum[bz] != nullptr;
-      if (sidx) bx -= nt0;
-      g.A = gin.seg[sidx].A[bz]; g.sa = 0;
-      g.B = gin.seg[sidx].B[bz]; g.sb = 0; g.mb = gin.seg[sidx].mb;
-      g.C = gin.seg[sidx].C[bz]; g.sc = 0; g.mc = RowMap{gin.seg[sidx].ldc, 0, 0, 0};
-      g.N = gin.seg[sidx].N; g.K = gin.seg[sidx].K;
-    }
+    if constexpr (SEG) do_colsum = seg_select<BN>(gin, g, bx, bz);      // from here on the descriptor is that segment's product
     m0 = by * BM; n0 = bx * BN;
     const int ktot = g.kcat > 1 ? g.kcat * g.K : g.K;
     kbeg = ks0 * BK;
@@ -1069,11 +1025,11 @@ __global__ __launch_bounds__(WIDE_NT, 2) void gemm_x6w_kernel(GemmDesc gin, bool
     if (g.kcat > 1 && kbeg >= g.K) {          // a run that starts inside a later K segment
       const int sgm = kbeg / g.K;
       opA.p += (int64_t)sgm * g.ska; opB.p += (int64_t)sgm * g.skb;
-      la.init(opA, m0, kbeg - sgm * g.K, tid, 0);
-      lb.init(opB, n0, kbeg - sgm * g.K, tid, 128);
+      la.init(opA, m0, kbeg - sgm * g.K, tid);
+      lb.init(opB, n0, kbeg - sgm * g.K, tid);
     } else {
-      la.init(opA, m0, kbeg, tid, 0);
-      lb.init(opB, n0, kbeg, tid, 128);
+      la.init(opA, m0, kbeg, tid);
+      lb.init(opB, n0, kbeg, tid);
     }
     if (kbeg < kend) fetch();
   };
@@ -1085,10 +1041,10 @@ __global__ __launch_bounds__(WIDE_NT, 2) void gemm_x6w_kernel(GemmDesc gin, bool
 
   while (true) {
     float4 csum = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto colsum_add = [&](const float4 (&v)[XLoaderOf<BM, TA, NT>::NV]) {
+    auto colsum_add = [&](const float4 (&v)[decltype(la)::NV]) {
       if (la.idx[0] < g.M) {
 #pragma unroll
-        for (int i = 0; i < XLoaderOf<BM, TA, NT>::NV; ++i) { csum.x += v[i].x; csum.y += v[i].y; csum.z += v[i].z; csum.w += v[i].w; }
+        for (int i = 0; i < decltype(la)::NV; ++i) { csum.x += v[i].x; csum.y += v[i].y; csum.z += v[i].z; csum.w += v[i].w; }
       }
     };
 
@@ -1184,8 +1140,7 @@ __global__ __launch_bounds__(WIDE_NT, 2) void gemm_x6w_kernel(GemmDesc gin, bool
     // ---- this part's values leave for C.  First the NEXT part is opened: its first global loads are in flight while
     // the stores below drain (a part is 32 K steps at K = 1,024: the two dependent load latencies of a prologue
     // and the 128 KB of an epilogue were a fifth of it)
-    EpiDesc ed{g.C + (int64_t)bz * g.sc, g.mc, g.bias1 ? g.bias1 + (int64_t)bz * g.sbias : nullptr,
-               g.bias2 ? g.bias2 + (int64_t)bz * g.sbias : nullptr, g.alpha, g.beta, g.act, g.M, g.N};
+    const EpiDesc ed = epi_desc(g, bz);
     const bool lead = ks0 == 0;                         // the part with the tile's first K step brings the biases
     const bool whole = ks0 == 0 && ks1 == plan.ksteps;
     const int em0 = m0 + wm * WM, en0 = n0 + wn * WN;
@@ -1269,28 +1224,9 @@ __global__ __launch_bounds__(WIDE_NT, 2) void gemm_x6w_kernel(GemmDesc gin, bool
     ++part_no;
     if (has_next) SSASR_XW_STAMP(0);
     if constexpr (SEG) {
-      if (cur_colsum) {         // (workgroup-uniform) the NT / (BM / 4) threads of a column quad meet in LDS
-        constexpr int PER_ROW = BM / 4;
-        float4* red = reinterpret_cast<float4*>(xlds);          // the operand images are no longer read
-        red[tid] = csum;
-        __syncthreads();
-        if (tid < PER_ROW) {
-          float4 v = red[tid];
-#pragma unroll
-          for (int k = 1; k < NT / PER_ROW; ++k) {
-            const float4 a = red[tid + k * PER_ROW];
-            v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-          }
-          const int m = cur_m0 + 4 * tid;
-          const float vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            if (m + e < ed.M) {
-              atomicAdd(gin.colsum[cur_bz] + m + e, ed.alpha * vv[e]);
-              if (gin.colsum2[cur_bz]) atomicAdd(gin.colsum2[cur_bz] + m + e, ed.alpha * vv[e]);
-            }
-          }
-        }
+      if (cur_colsum) {         // (workgroup-uniform; the operand images are no longer read)
+        colsum_reduce<NT, BM>(reinterpret_cast<float4*>(xlds), tid, csum, cur_m0, ed.M, ed.alpha, gin.colsum[cur_bz],
+                              gin.colsum2[cur_bz]);
         __syncthreads();        // the next part's prologue rewrites the image
       }
     }
@@ -1304,71 +1240,72 @@ bool map_vec_ok(const RowMap& m) {
   return m.inner ? (m.so % 4 == 0 && m.si % 4 == 0) : (m.ld % 4 == 0);
 }
 
-// the split-bf16 tile kernel with NP planes per operand (3: fp32 products; 1: SSASR_GEMM_BF16)
-template <int BM, int BN, int NP>
-int launch_x6_tiles(const GemmDesc& g, bool vecA, bool vecB, hipStream_t st, dim3 grid) {
-  dim3 block(256);
-  constexpr size_t lds = XGeom<BM, NP>::BYTES + XGeom<BN, NP>::BYTES;
-#define SSASR_X6_LAUNCH(A_, B_, R_, S_)                                                                     \
-  do {                                                                                                      \
-    auto fn = gemm_x6_kernel<BM, BN, A_, B_, R_, S_, NP>;                                                   \
-    static bool once = false;                                                                               \
-    if (!once) {                                                                                            \
-      SSASR_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-      once = true;                                                                                          \
-    }                                                                                                       \
-    hipLaunchKernelGGL(fn, grid, block, lds, st, g, vecA, vecB);                                            \
-  } while (0)
-  // split-K launches add their partial products atomically: one float per lane in rows of 16
-  // consecutive columns (TR = false); everything else stores 16 bytes per lane (TR = true)
-#define SSASR_X6_PICK(A_, B_)                                                                               \
-  do {                                                                                                      \
-    if (g.splitk > 1) SSASR_X6_LAUNCH(A_, B_, false, false);                                                \
-    else SSASR_X6_LAUNCH(A_, B_, true, false);                                                              \
-  } while (0)
-  if (g.nseg > 0) {                 // column segments (validated by ssasr_launch_gemm): partial products are
-    int nt = 0;                     // always ADDED (atomics): several K slices and earlier ranges meet in C
-    for (int k = 0; k < g.nseg; ++k) nt += (g.seg[k].N + BN - 1) / BN;
-    grid.x = (unsigned)nt;
-    SSASR_X6_LAUNCH(true, true, false, true);
-  } else if (!g.ta && !g.tb) SSASR_X6_PICK(false, false);
-  else if (!g.ta && g.tb) SSASR_X6_PICK(false, true);
-  else if (g.ta && !g.tb) SSASR_X6_PICK(true, false);
-  else SSASR_X6_PICK(true, true);
-#undef SSASR_X6_PICK
-#undef SSASR_X6_LAUNCH
+// One launch of the kernel instantiation `Kernel`; its first launch raises the kernel's dynamic LDS limit to `lds`.
+template <auto Kernel, class... Args>
+int launch_kernel(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+  if (lds > 0) {
+    static bool once = false;
+    if (!once) {
+      SSASR_HIP(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      once = true;
+    }
+  }
+  hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
   SSASR_LAUNCH_CHECK();
   return SSASR_OK;
 }
 
+// The kernel form that serves a descriptor, as types: f(TA, TB, TR, SEG), each a std::bool_constant.  tr: the values
+// are STORED, 16 bytes per lane; otherwise they are added atomically, one float per lane in rows of 16 consecutive
+// columns (split-K launches, stream-K parts; column segments always: several K slices and earlier ranges meet in C).
+template <class F>
+int with_kernel_form(const GemmDesc& g, bool tr, F&& f) {
+  constexpr std::true_type T{};
+  constexpr std::false_type N{};
+  if (g.nseg > 0) return f(T, T, N, T);
+  switch ((g.ta ? 4 : 0) | (g.tb ? 2 : 0) | (tr ? 1 : 0)) {
+    case 0: return f(N, N, N, N);
+    case 1: return f(N, N, T, N);
+    case 2: return f(N, T, N, N);
+    case 3: return f(N, T, T, N);
+    case 4: return f(T, N, N, N);
+    case 5: return f(T, N, T, N);
+    case 6: return f(T, T, N, N);
+    default: return f(T, T, T, N);
+  }
+}
+
+// the split-bf16 tile kernel with NP planes per operand (3: fp32 products; 1: SSASR_GEMM_BF16)
+template <int BM, int BN, int NP>
+int launch_x6_tiles(const GemmDesc& g, bool vecA, bool vecB, hipStream_t st, dim3 grid) {
+  constexpr size_t lds = XGeom<BM, NP>::BYTES + XGeom<BN, NP>::BYTES;
+  if (g.nseg > 0) {                 // column segments (validated by ssasr_launch_gemm)
+    int nt = 0;
+    for (int k = 0; k < g.nseg; ++k) nt += (g.seg[k].N + BN - 1) / BN;
+    grid.x = (unsigned)nt;
+  }
+  return with_kernel_form(g, g.splitk <= 1, [&](auto ta, auto tb, auto tr, auto seg) {
+    return launch_kernel<gemm_x6_kernel<BM, BN, ta, tb, tr, seg, NP>>(grid, dim3(256), lds, st, g, vecA, vecB);
+  });
+}
+
 template <int BM, int BN>
-int launch_tiles(const GemmDesc& gin, bool vecA, bool vecB, hipStream_t st) {
-  GemmDesc g = gin;
+int launch_tiles(const GemmDesc& g, bool vecA, bool vecB, hipStream_t st) {
   dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, g.batch * g.splitk);
-  dim3 block(256);
   if (ssasr_options().gemm_x6) {
     if (ssasr_options().gemm_bf16) return launch_x6_tiles<BM, BN, 1>(g, vecA, vecB, st, grid);
     return launch_x6_tiles<BM, BN, 3>(g, vecA, vecB, st, grid);
   }
-#define SSASR_GEMM_LAUNCH(A_, B_)                                                                           \
-  do {                                                                                                      \
-    if (g.splitk > 1) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, A_, B_, false>), grid, block, 0, st, g, vecA, vecB); \
-    else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, A_, B_, true>), grid, block, 0, st, g, vecA, vecB);    \
-  } while (0)
-  if (!g.ta && !g.tb) SSASR_GEMM_LAUNCH(false, false);
-  else if (!g.ta && g.tb) SSASR_GEMM_LAUNCH(false, true);
-  else if (g.ta && !g.tb) SSASR_GEMM_LAUNCH(true, false);
-  else SSASR_GEMM_LAUNCH(true, true);
-#undef SSASR_GEMM_LAUNCH
-  SSASR_LAUNCH_CHECK();
-  return SSASR_OK;
+  return with_kernel_form(g, g.splitk <= 1, [&](auto ta, auto tb, auto tr, auto) {      // (static LDS; no segment form)
+    return launch_kernel<gemm_f32_kernel<BM, BN, ta, tb, tr>>(grid, dim3(256), 0, st, g, vecA, vecB);
+  });
 }
 
 // What the wide kernel takes (it has no guarded loads): 16-byte loads legal everywhere, whole K steps, K-side row maps
 // that advance without a loop.
 static bool flat_map(const RowMap& m) { return m.inner == 0 || m.inner >= BK; }
-static bool wide_eligible(const GemmDesc& g, bool vecA, bool vecB) {
-  if (ssasr_options().gemm_bf16) return false;       // the one-plane variant exists as tile kernels only
+static bool wide_eligible(const GemmDesc& g, bool vecA, bool vecB, const SsasrOptions& o) {
+  if (!o.gemm_x6 || o.gemm_bf16) return false;       // split-bf16 only; its one-plane variant exists as tile kernels only
   if (!vecA || !vecB || (g.ta && g.M % 4) || (g.ta && !flat_map(g.ma))) return false;
   if (g.nseg > 0) {
     for (int k = 0; k < g.nseg; ++k)
@@ -1386,8 +1323,7 @@ static int parts_bound(long long units, long long G, int ksteps) {
 
 // Launch of the wide kernel as a stream-K grid.  streamk = false: one run per tile and K slice (the classic
 // grid: whole tiles, split-K slices added atomically), for A/B.
-int launch_wide(const GemmDesc& gin, bool vecA, bool vecB, hipStream_t st, bool streamk) {
-  GemmDesc g = gin;
+int launch_wide(const GemmDesc& g, bool vecA, bool vecB, hipStream_t st, bool streamk) {
   WidePlan p{};
   p.tiles_x = (g.N + WIDE_BN - 1) / WIDE_BN;
   if (g.nseg > 0) {
@@ -1456,39 +1392,13 @@ int launch_wide(const GemmDesc& gin, bool vecA, bool vecB, hipStream_t st, bool 
     p.ws = ws_base + (size_t)r * SK_MAX_G * 2;
     p.slabs = slab_base + (size_t)r * SK_MAX_G * SK_SLABS * SK_SLAB_FLOATS;
   }
-  {
-    const SsasrOptions& o = ssasr_options();
-    p.epi = getenv("SSASR_GEMM_EPI") ? atoi(getenv("SSASR_GEMM_EPI")) : 0;
-    p.trace = reinterpret_cast<unsigned long long*>(((unsigned long long)(unsigned)o.gemm_trace_hi << 32) | (unsigned)o.gemm_trace_lo);
-  }
-  dim3 grid((unsigned)G), block(WIDE_NT);
-  constexpr size_t lds = 2 * WIDE_STAGE;
-#define SSASR_XW_LAUNCH(...)                                                                                \
-  do {                                                                                                      \
-    auto fn = gemm_x6w_kernel<__VA_ARGS__>;                                                                 \
-    static bool once = false;                                                                               \
-    if (!once) {                                                                                            \
-      SSASR_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-      once = true;                                                                                          \
-    }                                                                                                       \
-    hipLaunchKernelGGL(fn, grid, block, lds, st, g, vecA, vecB, p);                                         \
-  } while (0)
-  if (g.nseg > 0) {
-    SSASR_XW_LAUNCH(true, true, false, true);
-  } else if (p.acc) {
-    if (!g.ta && !g.tb) SSASR_XW_LAUNCH(false, false, false);
-    else if (!g.ta && g.tb) SSASR_XW_LAUNCH(false, true, false);
-    else if (g.ta && !g.tb) SSASR_XW_LAUNCH(true, false, false);
-    else SSASR_XW_LAUNCH(true, true, false);
-  } else {
-    if (!g.ta && !g.tb) SSASR_XW_LAUNCH(false, false, true);
-    else if (!g.ta && g.tb) SSASR_XW_LAUNCH(false, true, true);
-    else if (g.ta && !g.tb) SSASR_XW_LAUNCH(true, false, true);
-    else SSASR_XW_LAUNCH(true, true, true);
-  }
-#undef SSASR_XW_LAUNCH
-  SSASR_LAUNCH_CHECK();
-  return SSASR_OK;
+  const SsasrOptions& o = ssasr_options();
+  p.epi = o.gemm_epi;
+  if ((p.epi == 2 || p.epi == 3) && !p.slabs) p.epi = 0;      // those two write to the region's slabs: none was taken
+  p.trace = reinterpret_cast<unsigned long long*>(((unsigned long long)(unsigned)o.gemm_trace_hi << 32) | (unsigned)o.gemm_trace_lo);
+  return with_kernel_form(g, !p.acc, [&](auto ta, auto tb, auto tr, auto seg) {
+    return launch_kernel<gemm_x6w_kernel<ta, tb, tr, seg>>(dim3((unsigned)G), dim3(WIDE_NT), 2 * WIDE_STAGE, st, g, vecA, vecB, p);
+  });
 }
 
 }  // namespace
@@ -1530,40 +1440,38 @@ static int launch_segments(GemmDesc g, hipStream_t st) {
   return launch_tiles<64, 64>(g, vecA, vecB, st);
 }
 
-int ssasr_launch_gemm(const GemmDesc& gin, hipStream_t st) {
-  GemmDesc g = gin;
-  if (g.nseg > 0) return launch_segments(g, st);
-  if (g.M <= 0 || g.N <= 0 || g.batch <= 0) return SSASR_OK;
-  if (g.K < 0 || !g.A || !g.B || !g.C) return SSASR_EARG;
-  if (g.splitk < 1) g.splitk = 1;
+// Argument checks of a plain product (no column segments) beyond its pointers
+static int check_product(const GemmDesc& g, const SsasrOptions& o) {
+  if (g.K < 0) return SSASR_EARG;
   if (g.splitk > 1 && g.act != 0) return SSASR_EARG;
   if (g.act == 3 && (g.bias1 || g.bias2 || g.beta != 0.f || (g.N & 1))) return SSASR_EARG;
   // K segments: split-bf16 kernel only, whole K steps per segment, dense (row-major) K-side layouts
-  if (g.kcat > 1 && (g.splitk != 1 || !ssasr_options().gemm_x6 || g.K % 32 != 0 || (g.ta && g.ma.inner) ||
-                     (g.tb && g.mb.inner)))
+  if (g.kcat > 1 && (g.splitk != 1 || !o.gemm_x6 || g.K % 32 != 0 || (g.ta && g.ma.inner) || (g.tb && g.mb.inner)))
     return SSASR_EARG;
   if (g.batch * g.splitk > 65535) return SSASR_EARG;
-  const bool vecA = aligned16(g.A) && map_vec_ok(g.ma) && (g.sa % 4 == 0) && (g.kcat <= 1 || g.ska % 4 == 0);
-  const bool vecB = aligned16(g.B) && map_vec_ok(g.mb) && (g.sb % 4 == 0) && (g.kcat <= 1 || g.skb % 4 == 0);
+  return SSASR_OK;
+}
+// 16-byte loads of the operands are legal, given 16-byte aligned bases
+static bool operand_vec_ok(const RowMap& m, int64_t batch_stride, int kcat, int64_t kseg_stride) {
+  return map_vec_ok(m) && (batch_stride % 4 == 0) && (kcat <= 1 || kseg_stride % 4 == 0);
+}
+
+// The kernel family of a checked plain product: 64 | 128 = the tile kernels' shape, 256 = the wide kernel as a stream-K
+// grid, 255 = the wide kernel on whole tiles.  A pure function of its arguments.  streamk_ok = false: what to take
+// when the stream-K grid has no workspace region left.
+static int gemm_tile_choice(const GemmDesc& g, bool vecA, bool vecB, const SsasrOptions& o, bool streamk_ok) {
+  if (g.tile == 64 || g.tile == 128) return g.tile;
+  const bool wide_ok = wide_eligible(g, vecA, vecB, o);
+  if (g.tile == 256 && wide_ok && streamk_ok) return 256;
+  if (const int forced = o.gemm_tile) {       // diagnostic: force a tile shape
+    if (forced == 256 && wide_ok && streamk_ok) return 256;
+    if (forced == 255 && wide_ok) return 255;
+    if (forced == 128 || forced == 64) return forced;
+  }
   // 128x128 tiles only when they still give every CU work.
   const int64_t big = (int64_t)((g.M + 127) / 128) * ((g.N + 127) / 128) * g.batch * g.splitk;
-  if (g.tile == 64) return launch_tiles<64, 64>(g, vecA, vecB, st);
-  if (g.tile == 128) return launch_tiles<128, 128>(g, vecA, vecB, st);
-  if (g.tile == 256 && ssasr_options().gemm_x6 && wide_eligible(g, vecA, vecB)) {
-    const int rc = launch_wide(g, vecA, vecB, st, true);
-    if (rc != WIDE_NO_REGION) return rc;
-  }
-  if (const int forced = ssasr_options().gemm_tile) {       // diagnostic: force a tile shape
-    if (forced == 256 && ssasr_options().gemm_x6 && wide_eligible(g, vecA, vecB)) {                                                // wide, stream-K
-      const int rc = launch_wide(g, vecA, vecB, st, true);
-      if (rc != WIDE_NO_REGION) return rc;
-    }
-    if (forced == 255 && ssasr_options().gemm_x6 && wide_eligible(g, vecA, vecB)) return launch_wide(g, vecA, vecB, st, false);    // wide, classic grid
-    if (forced == 128) return launch_tiles<128, 128>(g, vecA, vecB, st);
-    if (forced == 64) return launch_tiles<64, 64>(g, vecA, vecB, st);
-  }
   const int64_t cus = 256;
-  if (big < cus) return launch_tiles<64, 64>(g, vecA, vecB, st);
+  if (big < cus) return 64;
   // Both tile shapes run at 85-110 TF once the chip is full; what differs is how the LAST round of
   // workgroups fills it.  Measured at K = 1024 (tools/gemm_tiles.py), in units of 150 us: 128 x 128
   // tiles, two per CU -- a CU's pair of tiles costs 1.0, a single one 0.9 (0.63 when every CU has at
@@ -1572,7 +1480,7 @@ int ssasr_launch_gemm(const GemmDesc& gin, hipStream_t st) {
     const int64_t n = (big + cus - 1) / cus;
     const int64_t small = (int64_t)((g.M + 63) / 64) * ((g.N + 63) / 64) * g.batch;
     double t128, t64;
-    if (ssasr_options().gemm_x6) {
+    if (o.gemm_x6) {
       // the split-bf16 kernel, same sweep (us at K = 1024): 128-tiles 78 up to one per CU, 101 up to
       // two, a trailing odd round ~70; 64-tiles 12 + 0.056 per tile with a floor of 45
       t128 = n == 1 ? 78.0 : 101.0 * (double)(n / 2) + 70.0 * (double)(n % 2);
@@ -1582,7 +1490,7 @@ int ssasr_launch_gemm(const GemmDesc& gin, hipStream_t st) {
       t128 = n == 1 ? 0.63 : 1.0 * (double)(n / 2) + 0.9 * (double)(n % 2);
       t64 = 0.133 + 0.00052 * (double)small * (256.0 / (double)cus);
     }
-    if (ssasr_options().gemm_x6 && ssasr_options().gemm_wide) {
+    if (o.gemm_x6 && o.gemm_wide && streamk_ok) {
       // The wide kernel as a stream-K grid (gemm_x6w_kernel): every CU runs units / 256 K steps at 2.4 us each plus
       // ~16 us per part (prologue, epilogue, hand-off of a cut tile) -- tools/gemm_wide.py on the products of the
       // 32 x 800-frame step: 100 K steps per run in 307 us, 50 in 163, 25 in 89, 256 of 4096^3 in 624.  The tile
@@ -1593,19 +1501,55 @@ int ssasr_launch_gemm(const GemmDesc& gin, hipStream_t st) {
       // (With 128..255 tiles -- whole tiles, one per workgroup -- the kernel is faster than the tile kernels back to back
       // with itself, but alternating on the 470-frame train step the step was 0.4 % SLOWER: 5.681 against 5.659 ms,
       // tools/ab_option.py.  Only products that fill the chip take it, and only on a clear margin.)
-      if (wide >= cus && ktot >= 4 * BK && wide_eligible(g, vecA, vecB)) {
+      if (wide >= cus && ktot >= 4 * BK && wide_ok) {
         const double per = (double)wide * ksteps / (double)cus;
         const double twide = 2.4 * per + 16.0 * (per / ksteps + 1.0);
         const double scale = (double)ktot / 1024.0;
-        if (twide < 0.92 * scale * (t64 < t128 ? t64 : t128)) {
-          const int rc = launch_wide(g, vecA, vecB, st, true);
-          if (rc != WIDE_NO_REGION) return rc;
-        }
+        if (twide < 0.92 * scale * (t64 < t128 ? t64 : t128)) return 256;
       }
     }
-    if (t64 < t128) return launch_tiles<64, 64>(g, vecA, vecB, st);
+    if (t64 < t128) return 64;
   }
-  return launch_tiles<128, 128>(g, vecA, vecB, st);
+  return 128;
+}
+
+int ssasr_launch_gemm(const GemmDesc& gin, hipStream_t st) {
+  GemmDesc g = gin;
+  if (g.nseg > 0) return launch_segments(g, st);
+  if (g.M <= 0 || g.N <= 0 || g.batch <= 0) return SSASR_OK;
+  if (!g.A || !g.B || !g.C) return SSASR_EARG;
+  if (g.splitk < 1) g.splitk = 1;
+  const SsasrOptions& o = ssasr_options();
+  if (const int rc = check_product(g, o)) return rc;
+  const bool vecA = aligned16(g.A) && operand_vec_ok(g.ma, g.sa, g.kcat, g.ska);
+  const bool vecB = aligned16(g.B) && operand_vec_ok(g.mb, g.sb, g.kcat, g.skb);
+  int tile = gemm_tile_choice(g, vecA, vecB, o, true);
+  if (tile == 256) {
+    const int rc = launch_wide(g, vecA, vecB, st, true);
+    if (rc != WIDE_NO_REGION) return rc;
+    tile = gemm_tile_choice(g, vecA, vecB, o, false);       // a fifth stream: no workspace region left
+  }
+  if (tile == 255) return launch_wide(g, vecA, vecB, st, false);
+  return tile == 64 ? launch_tiles<64, 64>(g, vecA, vecB, st) : launch_tiles<128, 128>(g, vecA, vecB, st);
+}
+
+// C-ABI query (include/ssasr.h): gemm_tile_choice of a product with densely stored operands
+extern "C" int ssasr_gemm_tile_choice(int ta, int tb, int64_t M, int64_t N, int64_t K, int64_t batch, int splitk,
+                                      int kcat, int aligned16) {
+  if (M <= 0 || N <= 0 || batch <= 0) return 0;
+  if (M > INT_MAX || N > INT_MAX || K > INT_MAX || K < INT_MIN || batch > INT_MAX) return SSASR_EARG;
+  GemmDesc g{};
+  g.M = (int)M; g.N = (int)N; g.K = (int)K;
+  g.ta = ta; g.tb = tb;
+  g.ma = rm_dense(ta ? M : K); g.mb = rm_dense(tb ? N : K); g.mc = rm_dense(N);
+  g.alpha = 1.f; g.splitk = splitk < 1 ? 1 : splitk;
+  g.batch = (int)batch; g.sa = M * K; g.sb = N * K; g.sc = M * N;
+  g.kcat = kcat; g.ska = g.sa * batch; g.skb = g.sb * batch;
+  const SsasrOptions& o = ssasr_options();
+  if (const int rc = check_product(g, o)) return rc;
+  const bool vecA = aligned16 && operand_vec_ok(g.ma, g.sa, g.kcat, g.ska);
+  const bool vecB = aligned16 && operand_vec_ok(g.mb, g.sb, g.kcat, g.skb);
+  return gemm_tile_choice(g, vecA, vecB, o, true);
 }
 
 // C-ABI entry (include/ssasr.h).

@@ -32,6 +32,7 @@ void init_options() {
   g_opt.gemm_x6 = env_int("SSASR_GEMM_X6", 1);
   g_opt.gemm_wide = env_int("SSASR_GEMM_WIDE", 1);
   g_opt.gemm_bf16 = env_int("SSASR_GEMM_BF16", 0);
+  g_opt.gemm_epi = env_int("SSASR_GEMM_EPI", 0);
   g_opt.gemm_trace_lo = g_opt.gemm_trace_hi = 0;
   g_opt.gemm_kcat = env_int("SSASR_GEMM_KCAT", 1);
   g_opt.wgrad_fused = env_int("SSASR_WGRAD_FUSED", 1);
@@ -64,6 +65,7 @@ const Named kNames[] = {
     {"SSASR_GEMM_X6", &SsasrOptions::gemm_x6},
     {"SSASR_GEMM_WIDE", &SsasrOptions::gemm_wide},
     {"SSASR_GEMM_BF16", &SsasrOptions::gemm_bf16},
+    {"SSASR_GEMM_EPI", &SsasrOptions::gemm_epi},
     {"SSASR_GEMM_KCAT", &SsasrOptions::gemm_kcat},
     {"SSASR_WGRAD_FUSED", &SsasrOptions::wgrad_fused},
     {"SSASR_BPTT_ONE_LAUNCH", &SsasrOptions::bptt_one_launch},

@@ -138,6 +138,60 @@ def test_argument_errors_are_negative_and_need_no_gpu():
     # matrix products default to the split-bf16 form; 0 selects the fp32 MFMA instruction
     assert _lib.set_option('SSASR_GEMM_X6', 0) == 1 and _lib.set_option('SSASR_GEMM_X6', 1) == 0
     assert lib.ssasr_set_option(b'SSASR_NO_SUCH_SWITCH', 1) < 0
+    # the wide kernel's epilogue diagnostic round-trips like the other switches
+    assert _lib.set_option('SSASR_GEMM_EPI', 2) == 0 and _lib.set_option('SSASR_GEMM_EPI', 0) == 2
+
+
+# (M, N, K), splitk, {switches}, choice: the launcher's decision table for NN products under the defaults (split-bf16
+# on, wide on, nothing forced), 16-byte aligned operands.  64 | 128: tile kernels, 256: the wide kernel as a stream-K grid.
+TILE_CHOICES = [
+    ((4096, 4096, 4096), 1, {}, 256),        # wide model 662 < 0.92 * 4 * 202
+    ((25600, 2048, 1024), 1, {}, 256),       # 596 < 0.92 * 676
+    ((9000, 512, 1024), 1, {}, 64),          # 144 wide tiles < 256; 75.2 < 101
+    ((2048, 2048, 1024), 1, {}, 64),         # 69.3 < 78
+    ((4096, 2048, 1024), 1, {}, 128),        # wide 108.8 not below 0.92 * 101
+    ((4096, 4096, 1000), 1, {}, 128),        # K % 32: not wide-eligible
+    ((33, 1024, 1024), 1, {}, 64),           # fewer than 256 tiles of 128 x 128
+    ((4096, 4096, 4096), 4, {}, 128),        # split-K: no cost model
+    ((2048, 2048, 1024), 1, {'SSASR_GEMM_X6': 0}, 128),       # the fp32 kernels' model: 0.63 < 0.665
+    ((4096, 4096, 4096), 1, {'SSASR_GEMM_WIDE': 0}, 128),
+]
+
+
+@pytest.mark.parametrize('shape,splitk,switches,want', TILE_CHOICES)
+def test_gemm_tile_choice_decision_table(shape, splitk, switches, want):
+    """ssasr_gemm_tile_choice is the launcher's own (pure, host-only) choice of kernel family; the table pins it."""
+    from ss_asr_amd import _lib
+    lib = _lib.load()
+    old = {k: _lib.set_option(k, v) for k, v in
+           dict({'SSASR_GEMM_X6': 1, 'SSASR_GEMM_WIDE': 1, 'SSASR_GEMM_TILE': 0, 'SSASR_GEMM_BF16': 0}, **switches).items()}
+    try:
+        M, N, K = shape
+        assert lib.ssasr_gemm_tile_choice(0, 0, M, N, K, 1, splitk, 1, 1) == want
+    finally:
+        for k, v in old.items():
+            _lib.set_option(k, v)
+
+
+def test_gemm_tile_choice_forced_shapes_and_argument_errors():
+    from ss_asr_amd import _lib
+    lib = _lib.load()
+    assert lib.ssasr_gemm_tile_choice(0, 0, 0, 128, 128, 1, 1, 1, 1) == 0            # empty product: nothing is launched
+    assert lib.ssasr_gemm_tile_choice(0, 0, 128, 128, -1, 1, 1, 1, 1) < 0
+    assert lib.ssasr_gemm_tile_choice(0, 0, 2 ** 32 + 4096, 4096, 4096, 1, 1, 1, 1) < 0     # sizes beyond int are refused, not narrowed
+    assert lib.ssasr_gemm_tile_choice(0, 0, 128, 128, 100, 1, 1, 2, 1) < 0           # K segments: whole K steps only
+    old = _lib.set_option('SSASR_GEMM_TILE', 256)
+    try:
+        assert lib.ssasr_gemm_tile_choice(0, 0, 300, 138, 96, 1, 1, 1, 1) == 256
+        assert lib.ssasr_gemm_tile_choice(1, 1, 300, 140, 96, 1, 1, 1, 1) == 256
+        assert lib.ssasr_gemm_tile_choice(1, 1, 300, 138, 96, 1, 1, 1, 1) == 64       # N % 4 with tb: tile kernels, by the model
+        assert lib.ssasr_gemm_tile_choice(0, 0, 300, 138, 96, 1, 1, 1, 0) == 64       # unaligned operands
+        _lib.set_option('SSASR_GEMM_TILE', 255)
+        assert lib.ssasr_gemm_tile_choice(0, 0, 300, 138, 96, 1, 2, 1, 1) == 255
+        _lib.set_option('SSASR_GEMM_TILE', 128)
+        assert lib.ssasr_gemm_tile_choice(0, 0, 33, 64, 96, 1, 1, 1, 1) == 128
+    finally:
+        _lib.set_option('SSASR_GEMM_TILE', old)
 
 
 def test_ops_refuse_cpu_tensors():

@@ -26,7 +26,8 @@
  * ABI history.  Added under 16 without changing anything older (the version number stays): ssasr_gemm_tile_choice; beam search --
  * ssasr_beam, ssasr_decode_beam_ws_bytes, ssasr_decode_beam; joint CTC / attention decoding -- ssasr_ctc_prefix,
  * ssasr_decode_beam_ctc_ws_bytes, ssasr_decode_beam_ctc; length bonus, coverage term and end detection in the beam
- * search -- ssasr_beam_terms, ssasr_decode_beam_ex_ws_bytes, ssasr_decode_beam_ex.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
+ * search -- ssasr_beam_terms, ssasr_decode_beam_ex_ws_bytes, ssasr_decode_beam_ex; SpecAugment in batch assembly and label smoothing in the
+ * masked CE -- ssasr_specaug, ssasr_gather_batch_aug, ssasr_specaug_plan, ssasr_ce_loss_ls_fwd, ssasr_ce_loss_ls_bwd.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
  * (nothing older changed).  15: inference -- ssasr_charlm, ssasr_charlm_step, ssasr_infer, ssasr_decode_greedy (nothing
  * older changed).  14 and before: the training entry points below.
  *
@@ -372,6 +373,22 @@ int ssasr_ce_loss_fwd(const float* logits, const int32_t* y, int64_t y_ld, int64
 int ssasr_ce_loss_bwd(const float* logits, const int32_t* y, int64_t y_ld, const float* lse,
                       const float* dloss, int64_t B, int64_t U, int64_t V, float* dlogits, void* stream);
 
+/* The same loss with label smoothing.  BUILD-DEFINED -- the reference's ASR loss has none (the BCE smoothing of
+ * its ADVTrainer is the discriminator's and unrelated); the semantics are
+ * torch.nn.functional.cross_entropy(..., label_smoothing=eps): the target is (1 - eps) on the label plus eps / V
+ * on every one of the V classes, class 0 included, so a labelled step costs
+ *   (1 - eps) (lse - z[lab]) + eps (lse - mean_v z[v]).
+ * Labels, masking, denominators, the block-order mean and the layout of lse are ssasr_ce_loss_fwd's.  _bwd:
+ * dlogits = (p - (1 - eps) [v == lab] - eps / V) dloss / (B denom[b]) on labelled steps, 0 elsewhere.
+ * For eps > 0 the log-sum-exp and the gradient are formed in double and rounded once (lse holds the correctly
+ * rounded value), so that a labelled step's dlogits sum to zero over V as closely as float storage allows.
+ * 0 <= eps < 1, else an argument error; eps == 0 launches the kernels of the entries above (the same bits). */
+int ssasr_ce_loss_ls_fwd(const float* logits, const int32_t* y, int64_t y_ld, int64_t y_cols, int64_t B,
+                         int64_t U, int64_t V, float eps, float* lse, float* loss, void* stream);
+int ssasr_ce_loss_ls_bwd(const float* logits, const int32_t* y, int64_t y_ld, const float* lse,
+                         const float* dloss, int64_t B, int64_t U, int64_t V, float eps,
+                         float* dlogits, void* stream);
+
 /* CTC negative log likelihood over the Listener's frames: the auxiliary branch of
  * BASELINE.json configs[3] ("Joint CTC+attention loss").  BUILD-DEFINED -- the reference
  * has no CTC (its only loss is src/trainer.py:426-434), so this replaces no reference
@@ -521,6 +538,40 @@ int ssasr_frame_lengths(const float* x, int64_t B, int64_t T, int64_t F, int32_t
  * rows after (out is [B][T][F], T >= max lens). */
 int ssasr_gather_batch(const float* frames, const int64_t* offsets, const int32_t* lens, int64_t B,
                        int64_t T, int64_t F, float* out, void* stream);
+
+/* SpecAugment (Park et al. 2019: frequency and time masks on the log-mel input; no time warping) applied in the
+ * pass that assembles the batch.  BUILD-DEFINED -- the reference trains on unaugmented filterbanks.
+ * out[b][t][f] = frames[offsets[b] + t][f] for t < lens[b], EXCEPT that a cell whose t lies in one of the
+ * utterance's time masks or whose f lies in one of its frequency masks holds `fill`; rows t >= lens[b] are zero,
+ * not `fill`.  A mask (start, width) covers start <= i < start + width; masks may overlap, width 0 covers nothing.
+ * utt_ids int32 [B]: every row's index in the CORPUS.  An utterance's masks depend on (seed, epoch, utt_id, len, F)
+ * alone -- not on its batch, its slot, B or the rank -- and are drawn statelessly, in unsigned integer arithmetic
+ * only (no floating point anywhere), all of it modulo 2^32 unless it says 64-bit:
+ *   mix(x):  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *   h = mix((seed mod 2^32) ^ 0x9e3779b9); h = mix(h ^ (seed >> 32)); h = mix(h ^ (epoch mod 2^32));
+ *   h = mix(h ^ (epoch >> 32)); hu = mix(h ^ utt_id)          (utt_id as its 32-bit two's complement pattern)
+ *   draw(k, n) = (mix(hu ^ k) * n) >> 32                      (the product in 64 bits: uniform on 0 .. n - 1)
+ * Masks are numbered j = 0 .. n_freq - 1 (frequency), then j = n_freq .. n_freq + n_time - 1 (time):
+ *   frequency mask j:  width = draw(2 j, max_freq + 1),  start = draw(2 j + 1, F - width + 1)
+ *   time mask j:       width = draw(2 j, cap + 1),       start = draw(2 j + 1, len - width + 1),
+ *                      cap = min(max_time, len * time_permille / 1000)   (64-bit product, integer division).
+ * Limits (argument error otherwise): n_freq, n_time in 0 .. 8, 0 <= max_freq <= F, max_time >= 0,
+ * 0 <= time_permille <= 1000, and those of ssasr_gather_batch.  With n_freq = n_time = 0 the entry launches
+ * ssasr_gather_batch's kernel.  epoch: the caller's draw counter (one value per pass over the corpus).
+ * ssasr_specaug_plan is a HOST function (host pointers, no GPU work): the masks the kernel applies to one
+ * utterance, from the same code, as masks[n_freq + n_time][2] = (start, width); len >= 0, F > 0. */
+typedef struct ssasr_specaug {
+  int32_t n_freq, max_freq;
+  int32_t n_time, max_time;
+  int32_t time_permille;
+  float fill;
+  uint64_t seed;
+  uint64_t epoch;
+} ssasr_specaug;
+int ssasr_gather_batch_aug(const float* frames, const int64_t* offsets, const int32_t* lens,
+                           const int32_t* utt_ids, int64_t B, int64_t T, int64_t F,
+                           const ssasr_specaug* p, float* out, void* stream);
+int ssasr_specaug_plan(const ssasr_specaug* p, int32_t utt_id, int32_t len, int32_t F, int32_t* masks);
 
 /* Log-mel filterbank of one waveform: log_fbank, src/preprocess.py:187-208
  * (librosa 0.6.3 melspectrogram defaults: centred reflect-padded STFT with a

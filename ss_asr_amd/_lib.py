@@ -80,6 +80,12 @@ class BeamTerms(C.Structure):
                 ('n_steps', P)]
 
 
+class SpecAug(C.Structure):
+    """struct ssasr_specaug (include/ssasr.h)."""
+    _fields_ = [('n_freq', C.c_int32), ('max_freq', C.c_int32), ('n_time', C.c_int32), ('max_time', C.c_int32),
+                ('time_permille', C.c_int32), ('fill', F32), ('seed', C.c_uint64), ('epoch', C.c_uint64)]
+
+
 SIGNATURES = {
     'ssasr_abi_version': (I32, []),
     'ssasr_set_option': (I32, [C.c_char_p, I32]),
@@ -123,6 +129,8 @@ SIGNATURES = {
     'ssasr_charlm_train_bwd': (I32, [C.POINTER(CharLM), P, I64, I64, F32, P, P]),
     'ssasr_ce_loss_fwd': (I32, [P, P, I64, I64, I64, I64, I64, P, P, P]),
     'ssasr_ce_loss_bwd': (I32, [P, P, I64, P, P, I64, I64, I64, P, P]),
+    'ssasr_ce_loss_ls_fwd': (I32, [P, P, I64, I64, I64, I64, I64, F32, P, P, P]),
+    'ssasr_ce_loss_ls_bwd': (I32, [P, P, I64, P, P, I64, I64, I64, F32, P, P]),
     'ssasr_ctc_ws_floats': (I64, [I64, I64, I64, I64]),
     'ssasr_ctc_loss_fwd': (I32, [P, P, P, I64, P, I64, I64, I64, I64, I32, P, P, P]),
     'ssasr_ctc_loss_bwd': (I32, [P, P, P, I64, P, I64, I64, I64, I64, I32, P, P, P, P, P]),
@@ -154,6 +162,8 @@ SIGNATURES = {
     'ssasr_decoder_bwd_chain_floats': (I64, [I64] * 6),
     'ssasr_frame_lengths': (I32, [P, I64, I64, I64, P, P]),
     'ssasr_gather_batch': (I32, [P, P, P, I64, I64, I64, P, P]),
+    'ssasr_gather_batch_aug': (I32, [P, P, P, P, I64, I64, I64, C.POINTER(SpecAug), P, P]),
+    'ssasr_specaug_plan': (I32, [C.POINTER(SpecAug), I32, I32, I32, C.POINTER(C.c_int32)]),
     'ssasr_logmel_frames': (I64, [I64, I64, I64]),
     'ssasr_logmel_batch_rows': (I64, [I64, I64, I64]),
     'ssasr_logmel_batch': (I32, [P, P, I64, I64, I64, I64, I64, I64, P, P, P, P, P, P]),

@@ -12,9 +12,11 @@ namespace {
 // share of the row's summed token loss (tail[b][g]) and, from block 0, the row's denominator
 // count(y != 0).  Labels are read in place: step t's label is y[b][t + 1].
 constexpr int CE_G = 8;
-__global__ __launch_bounds__(256) void ce_fwd_kernel(const float* logits, const int32_t* y, int64_t y_ld,
-                                                     int y_cols, int U, int V, float* lse, float* tail,
-                                                     float* denom) {
+// LS: label smoothing, tok(b,t) = (1 - eps) (lse - z[lab]) + eps (lse - mean_v z[v]); the row sum of z rides in the
+// max pass, and the log-sum-exp is formed in double.  Without it the body is the plain kernel's own arithmetic.
+template <bool LS>
+__device__ __forceinline__ void ce_fwd_body(const float* logits, const int32_t* y, int64_t y_ld, int y_cols, int U,
+                                            int V, float eps, float* lse, float* tail, float* denom) {
   __shared__ float sm[4];
   __shared__ int sn[4];
   const int b = blockIdx.x, g = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -22,17 +24,39 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* logits, const 
   float tok = 0.f;
   for (int t = g + CE_G * wave; t < U; t += 4 * CE_G) {
     const float* row = logits + ((int64_t)b * U + t) * V;
-    float m = -INFINITY;
-    for (int v = lane; v < V; v += 64) m = fmaxf(m, row[v]);
+    float m = -INFINITY, zs = 0.f;
+    for (int v = lane; v < V; v += 64) {
+      m = fmaxf(m, row[v]);
+      if constexpr (LS) zs += row[v];
+    }
     m = wave_max(m);
-    float s = 0.f;
-    for (int v = lane; v < V; v += 64) s += expf(row[v] - m);
-    s = wave_sum(s);
-    const float l = m + logf(s);
+    if constexpr (LS) zs = wave_sum(zs);
+    float l;
+    double ld = 0.0;
+    if constexpr (LS) {
+      // the saved float is the correctly rounded log-sum-exp: its error is a common factor of the step's
+      // probabilities in the backward pass, and the gradient is held to summing to zero over V within 1e-7
+      double s = 0.0;
+      for (int v = lane; v < V; v += 64) s += exp((double)row[v] - (double)m);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+      ld = (double)m + log(s);
+      l = (float)ld;
+    } else {
+      float s = 0.f;
+      for (int v = lane; v < V; v += 64) s += expf(row[v] - m);
+      s = wave_sum(s);
+      l = m + logf(s);
+    }
     const int lab = t + 1 < y_cols ? yr[t + 1] : 0;
     if (lane == 0) {
       lse[(int64_t)b * U + t] = l;
-      if (lab != 0) tok += l - row[lab];
+      if constexpr (LS) {
+        if (lab != 0)
+          tok += (float)((1.0 - (double)eps) * (ld - (double)row[lab]) + (double)eps * (ld - (double)zs / (double)V));
+      } else {
+        if (lab != 0) tok += l - row[lab];
+      }
     }
   }
   int cnt = 0;
@@ -48,6 +72,18 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* logits, const 
   }
 }
 
+__global__ __launch_bounds__(256) void ce_fwd_kernel(const float* logits, const int32_t* y, int64_t y_ld,
+                                                     int y_cols, int U, int V, float* lse, float* tail,
+                                                     float* denom) {
+  ce_fwd_body<false>(logits, y, y_ld, y_cols, U, V, 0.f, lse, tail, denom);
+}
+
+__global__ __launch_bounds__(256) void ce_ls_fwd_kernel(const float* logits, const int32_t* y, int64_t y_ld,
+                                                        int y_cols, int U, int V, float eps, float* lse,
+                                                        float* tail, float* denom) {
+  ce_fwd_body<true>(logits, y, y_ld, y_cols, U, V, eps, lse, tail, denom);
+}
+
 // loss = mean_b( (sum of the row's token losses, in block order) / denom[b] )   -- deterministic
 __global__ void ce_mean_kernel(const float* tail, const float* denom, int B, float* loss) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -61,9 +97,11 @@ __global__ void ce_mean_kernel(const float* tail, const float* denom, int B, flo
   }
 }
 
-__global__ void ce_bwd_kernel(const float* logits, const int32_t* y, int64_t y_ld, const float* denom,
-                              const float* lse, const float* dloss, int B, int U, int V,
-                              float* dlogits) {
+// LS: d tok / d z[v] = p[v] - (1 - eps) [v == lab] - eps / V.
+template <bool LS>
+__device__ __forceinline__ void ce_bwd_body(const float* logits, const int32_t* y, int64_t y_ld, const float* denom,
+                                            const float* lse, const float* dloss, int B, int U, int V, float eps,
+                                            float* dlogits) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t n = (int64_t)B * U * V;
   if (i >= n) return;
@@ -74,10 +112,29 @@ __global__ void ce_bwd_kernel(const float* logits, const int32_t* y, int64_t y_l
   const int lab = y[(int64_t)b * y_ld + t + 1];
   float g = 0.f;
   if (lab != 0) {
-    const float p = expf(logits[i] - lse[row]);
-    g = (p - (v == lab ? 1.f : 0.f)) * (*dloss) / ((float)B * denom[b]);
+    if constexpr (LS) {
+      // in double, rounded once: the V values of a step then sum to zero as closely as float storage allows
+      const double p = exp((double)logits[i] - (double)lse[row]);
+      g = (float)((p - (v == lab ? 1.0 - (double)eps : 0.0) - (double)eps / (double)V) * (double)(*dloss) /
+                  ((double)B * (double)denom[b]));
+    } else {
+      const float p = expf(logits[i] - lse[row]);
+      g = (p - (v == lab ? 1.f : 0.f)) * (*dloss) / ((float)B * denom[b]);
+    }
   }
   dlogits[i] = g;
+}
+
+__global__ void ce_bwd_kernel(const float* logits, const int32_t* y, int64_t y_ld, const float* denom,
+                              const float* lse, const float* dloss, int B, int U, int V,
+                              float* dlogits) {
+  ce_bwd_body<false>(logits, y, y_ld, denom, lse, dloss, B, U, V, 0.f, dlogits);
+}
+
+__global__ void ce_ls_bwd_kernel(const float* logits, const int32_t* y, int64_t y_ld, const float* denom,
+                                 const float* lse, const float* dloss, int B, int U, int V, float eps,
+                                 float* dlogits) {
+  ce_bwd_body<true>(logits, y, y_ld, denom, lse, dloss, B, U, V, eps, dlogits);
 }
 
 constexpr int NORM_BLOCK = 256;
@@ -247,7 +304,135 @@ __global__ __launch_bounds__(64) void gather_batch_kernel(const float* frames, c
   }
 }
 
+// SpecAugment plan (include/ssasr.h, ssasr_specaug): unsigned integer arithmetic only, the same code on the host
+// (ssasr_specaug_plan) and in gather_batch_aug_kernel.
+__host__ __device__ inline uint32_t specaug_mix(uint32_t x) {
+  x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
+  return x;
+}
+
+// the chain over seed and epoch, the same for every utterance of a launch
+__host__ __device__ inline uint32_t specaug_base(uint64_t seed, uint64_t epoch) {
+  uint32_t h = specaug_mix((uint32_t)seed ^ 0x9e3779b9U);
+  h = specaug_mix(h ^ (uint32_t)(seed >> 32));
+  h = specaug_mix(h ^ (uint32_t)epoch);
+  return specaug_mix(h ^ (uint32_t)(epoch >> 32));
+}
+
+__host__ __device__ inline uint32_t specaug_utt(uint32_t base, int32_t utt_id) {
+  return specaug_mix(base ^ (uint32_t)utt_id);
+}
+
+// draw k of an utterance, mapped to 0 .. n - 1
+__host__ __device__ inline int32_t specaug_draw(uint32_t hu, int32_t k, uint32_t n) {
+  return (int32_t)(((uint64_t)specaug_mix(hu ^ (uint32_t)k) * n) >> 32);
+}
+
+__host__ __device__ inline int32_t specaug_time_cap(int32_t max_time, int32_t time_permille, int32_t len) {
+  const int32_t r = (int32_t)(((uint64_t)(uint32_t)len * (uint32_t)time_permille) / 1000u);
+  return max_time < r ? max_time : r;
+}
+
+// mask j (frequency masks first, then time masks): width on 0 .. cap, start on 0 .. extent - width
+__host__ __device__ inline void specaug_mask(uint32_t hu, int32_t j, int32_t cap, int32_t extent, int32_t* start,
+                                             int32_t* width) {
+  const int32_t w = specaug_draw(hu, 2 * j, (uint32_t)cap + 1u);
+  *width = w;
+  *start = specaug_draw(hu, 2 * j + 1, (uint32_t)(extent - w) + 1u);
+}
+
+// gather_batch_kernel with the utterance's SpecAugment masks applied in the same pass.  grid (T, B), 64 threads.
+// Everything the plan reads is the same in every lane (kernel arguments, blockIdx, lens[b], utt_ids[b]), so the
+// draws are scalar work; a row past the utterance or inside a time mask is stored without a load.
+__global__ __launch_bounds__(64) void gather_batch_aug_kernel(const float* frames, const int64_t* offsets,
+                                                              const int32_t* lens, const int32_t* utt_ids, int T,
+                                                              int F, int n_freq, int max_freq, int n_time,
+                                                              int max_time, int time_permille, float fill,
+                                                              uint32_t base, float* out) {
+  const int t = blockIdx.x, b = blockIdx.y;
+  float* dst = out + ((int64_t)b * T + t) * F;
+  const int len = lens[b];
+  const bool vec = (F & 3) == 0 && ((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  bool whole = t >= len;                 // the row holds one value: zero padding, or `fill` inside a time mask
+  float value = 0.f;
+  uint32_t hu = 0;
+  if (!whole) {
+    hu = specaug_utt(base, utt_ids[b]);
+    const int cap = specaug_time_cap(max_time, time_permille, len);
+    for (int j = 0; j < n_time; ++j) {
+      int32_t s, w;
+      specaug_mask(hu, n_freq + j, cap, len, &s, &w);
+      if ((uint32_t)(t - s) < (uint32_t)w) { whole = true; value = fill; }
+    }
+  }
+  if (whole) {
+    if (vec) {
+      for (int f = threadIdx.x; f < (F >> 2); f += 64) reinterpret_cast<float4*>(dst)[f] = make_float4(value, value, value, value);
+    } else {
+      for (int f = threadIdx.x; f < F; f += 64) dst[f] = value;
+    }
+    return;
+  }
+  const float* src = frames + (offsets[b] + t) * F;
+  if (vec) {
+    for (int f = threadIdx.x; f < (F >> 2); f += 64) {
+      float4 v = reinterpret_cast<const float4*>(src)[f];
+      for (int j = 0; j < n_freq; ++j) {
+        int32_t s, w;
+        specaug_mask(hu, j, max_freq, F, &s, &w);
+        const uint32_t d = (uint32_t)(4 * f - s), uw = (uint32_t)w;
+        if (d < uw) v.x = fill;
+        if (d + 1 < uw) v.y = fill;
+        if (d + 2 < uw) v.z = fill;
+        if (d + 3 < uw) v.w = fill;
+      }
+      reinterpret_cast<float4*>(dst)[f] = v;
+    }
+  } else {
+    for (int f = threadIdx.x; f < F; f += 64) {
+      float v = src[f];
+      for (int j = 0; j < n_freq; ++j) {
+        int32_t s, w;
+        specaug_mask(hu, j, max_freq, F, &s, &w);
+        if ((uint32_t)(f - s) < (uint32_t)w) v = fill;
+      }
+      dst[f] = v;
+    }
+  }
+}
+
+bool specaug_args_ok(const ssasr_specaug* p, int64_t F) {
+  return p && p->n_freq >= 0 && p->n_freq <= 8 && p->n_time >= 0 && p->n_time <= 8 && p->max_freq >= 0 &&
+         p->max_freq <= F && p->max_time >= 0 && p->time_permille >= 0 && p->time_permille <= 1000;
+}
+
 }  // namespace
+
+extern "C" int ssasr_specaug_plan(const ssasr_specaug* p, int32_t utt_id, int32_t len, int32_t F, int32_t* masks) {
+  if (F <= 0 || len < 0 || !specaug_args_ok(p, F) || (!masks && p->n_freq + p->n_time > 0)) return SSASR_EARG;
+  const uint32_t hu = specaug_utt(specaug_base(p->seed, p->epoch), utt_id);
+  const int32_t cap = specaug_time_cap(p->max_time, p->time_permille, len);
+  for (int j = 0; j < p->n_freq + p->n_time; ++j) {
+    if (j < p->n_freq)
+      specaug_mask(hu, j, p->max_freq, F, masks + 2 * j, masks + 2 * j + 1);
+    else
+      specaug_mask(hu, j, cap, len, masks + 2 * j, masks + 2 * j + 1);
+  }
+  return SSASR_OK;
+}
+
+extern "C" int ssasr_gather_batch_aug(const float* frames, const int64_t* offsets, const int32_t* lens,
+                                      const int32_t* utt_ids, int64_t B, int64_t T, int64_t F, const ssasr_specaug* p,
+                                      float* out, void* stream) {
+  if (!specaug_args_ok(p, F)) return SSASR_EARG;
+  if (p->n_freq == 0 && p->n_time == 0) return ssasr_gather_batch(frames, offsets, lens, B, T, F, out, stream);
+  if (!frames || !offsets || !lens || !utt_ids || !out || B <= 0 || T <= 0 || F <= 0 || B > 65535) return SSASR_EARG;
+  hipLaunchKernelGGL(gather_batch_aug_kernel, dim3((unsigned)T, (unsigned)B), dim3(64), 0, (hipStream_t)stream,
+                     frames, offsets, lens, utt_ids, (int)T, (int)F, (int)p->n_freq, (int)p->max_freq, (int)p->n_time,
+                     (int)p->max_time, (int)p->time_permille, p->fill, specaug_base(p->seed, p->epoch), out);
+  SSASR_LAUNCH_CHECK();
+  return SSASR_OK;
+}
 
 extern "C" int ssasr_gather_batch(const float* frames, const int64_t* offsets, const int32_t* lens, int64_t B,
                                   int64_t T, int64_t F, float* out, void* stream) {
@@ -277,6 +462,33 @@ extern "C" int ssasr_ce_loss_bwd(const float* logits, const int32_t* y, int64_t 
   const int64_t n = B * U * V;
   hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits,
                      y, y_ld, lse + B * U + B * CE_G, lse, dloss, (int)B, (int)U, (int)V, dlogits);
+  SSASR_LAUNCH_CHECK();
+  return SSASR_OK;
+}
+
+extern "C" int ssasr_ce_loss_ls_fwd(const float* logits, const int32_t* y, int64_t y_ld, int64_t y_cols, int64_t B,
+                                    int64_t U, int64_t V, float eps, float* lse, float* loss, void* stream) {
+  if (!(eps >= 0.f && eps < 1.f)) return SSASR_EARG;
+  if (eps == 0.f) return ssasr_ce_loss_fwd(logits, y, y_ld, y_cols, B, U, V, lse, loss, stream);
+  if (!logits || !y || !lse || !loss || B <= 0 || U <= 0 || V <= 0 || y_cols < U + 1 || y_ld < y_cols)
+    return SSASR_EARG;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(ce_ls_fwd_kernel, dim3((unsigned)B, CE_G), dim3(256), 0, st, logits, y, y_ld, (int)y_cols,
+                     (int)U, (int)V, eps, lse, lse + B * U, lse + B * U + B * CE_G);
+  hipLaunchKernelGGL(ce_mean_kernel, dim3(1), dim3(64), 0, st, lse + B * U, lse + B * U + B * CE_G, (int)B, loss);
+  SSASR_LAUNCH_CHECK();
+  return SSASR_OK;
+}
+
+extern "C" int ssasr_ce_loss_ls_bwd(const float* logits, const int32_t* y, int64_t y_ld, const float* lse,
+                                    const float* dloss, int64_t B, int64_t U, int64_t V, float eps, float* dlogits,
+                                    void* stream) {
+  if (!(eps >= 0.f && eps < 1.f)) return SSASR_EARG;
+  if (eps == 0.f) return ssasr_ce_loss_bwd(logits, y, y_ld, lse, dloss, B, U, V, dlogits, stream);
+  if (!logits || !y || !lse || !dloss || !dlogits || B <= 0 || U <= 0 || V <= 0 || y_ld < U + 1) return SSASR_EARG;
+  const int64_t n = B * U * V;
+  hipLaunchKernelGGL(ce_ls_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits,
+                     y, y_ld, lse + B * U + B * CE_G, lse, dloss, (int)B, (int)U, (int)V, eps, dlogits);
   SSASR_LAUNCH_CHECK();
   return SSASR_OK;
 }

@@ -60,7 +60,7 @@ class JointCTCASR(ASR):
 
 class JointCTCTrainStep(ASRTrainStep):
     """ASRTrainStep whose loss is the joint one; everything else (all-reduce, clip, Adadelta,
-    status polling) is inherited."""
+    status polling) is inherited.  `label_smoothing` smooths the attention branch only."""
 
     def forward_loss(self, x, y, x_lens, ans_len):
         att_loss, logits, att = super().forward_loss(x, y, x_lens, ans_len)

@@ -34,7 +34,11 @@ def settle_collector(again=False):
 
 
 class ASRTrainStep:
-    def __init__(self, model, lr=1.0, eps=1e-8, rho=0.9, grad_clip=5.0):
+    def __init__(self, model, lr=1.0, eps=1e-8, rho=0.9, grad_clip=5.0, label_smoothing=0.0):
+        """label_smoothing in [0, 1) (build-defined): the smoothed CE of ops.masked_ce_loss; 0 is the reference's loss."""
+        if not 0.0 <= float(label_smoothing) < 1.0:
+            raise ValueError('label_smoothing must lie in [0, 1), got %r' % (label_smoothing,))
+        self.label_smoothing = float(label_smoothing)
         if not next(model.parameters()).is_cuda:
             raise RuntimeError('ASRTrainStep needs the model on the GPU (no CPU path)')
         self.model = model
@@ -52,7 +56,7 @@ class ASRTrainStep:
 
     def forward_loss(self, x, y, x_lens, ans_len):
         _, logits, att = self.model(x, ans_len, teacher=y, state_len=x_lens)
-        return ops.masked_ce_loss(logits, y, ans_len), logits, att
+        return ops.masked_ce_loss(logits, y, ans_len, self.label_smoothing), logits, att
 
     def __call__(self, x, y, x_lens, ans_len):
         """x [B,T,F] float32, y [B,L] int64 (both on the GPU), x_lens host list

@@ -14,6 +14,10 @@ index, whole batches only (:63); the index is expected to be sorted so that
 every batch is in decreasing frame-length order (conf/README.md:16).
 ``bucket=True`` instead sorts the whole corpus by length first.
 
+``spec_augment`` (build-defined, off by default): SpecAugment frequency / time masks applied by
+the assembling kernel itself (``ssasr_gather_batch_aug``), drawn per utterance and epoch; every
+``__iter__`` is one epoch, ``set_epoch`` resumes.  With ``None`` nothing changes.
+
 Yields ``(x [B, T, F] float32, x_lens list, y [B, L] int64, y_lens list)`` with
 T = max(x_lens) rounded up to a multiple of 8 (the pyramid's time reduction),
 the values ``prepare_x`` / ``prepare_y`` return for the same batch.
@@ -40,7 +44,7 @@ def rank_batches(n_batches, rank, world):
 
 class GpuResidentLoader:
     def __init__(self, tsv_file, batch_size, device, chars=TOKENS + ALL_CHARS, rank=0, world=1,
-                 bucket=False, time_multiple=8):
+                 bucket=False, time_multiple=8, spec_augment=None):
         rows = load_index(tsv_file)
         if bucket:
             rows.sort(key=lambda r: r['unpadded_num_frames'], reverse=True)
@@ -54,10 +58,12 @@ class GpuResidentLoader:
             n = int((a.sum(-1) != 0).sum())              # prepare_x's definition of a frame
             kept.append(a[:n])
         labels = [[char2idx[c] for c in r['normalized_text']] for r in used]
-        self._setup(kept, labels, batch_size, device, rank, world, time_multiple, char2idx[SOS_TKN])
+        self._setup(kept, labels, batch_size, device, rank, world, time_multiple, char2idx[SOS_TKN],
+                    spec_augment=spec_augment)
 
     @classmethod
-    def from_arrays(cls, utterances, labels, batch_size, device, rank=0, world=1, time_multiple=8, pad=0):
+    def from_arrays(cls, utterances, labels, batch_size, device, rank=0, world=1, time_multiple=8, pad=0,
+                    spec_augment=None):
         """The same loader over in-memory data: `utterances` = unpadded float32 [n_i, F] arrays in
         index order, `labels` = their character-id rows ('<' ... '>').  Used by bench.py, whose
         corpus is synthetic: the timed step then assembles its batch exactly as ASRTrainer's does."""
@@ -65,12 +71,12 @@ class GpuResidentLoader:
         self.rows = None
         n = len(plan_batches(len(utterances), batch_size)) * batch_size
         self._setup([np.asarray(u, dtype=np.float32) for u in utterances[:n]], [list(l) for l in labels[:n]],
-                    batch_size, device, rank, world, time_multiple, pad)
+                    batch_size, device, rank, world, time_multiple, pad, spec_augment=spec_augment)
         return self
 
     @classmethod
     def from_waveforms(cls, waves, sample_rate, texts, batch_size, device, n_mels=None, chars=TOKENS + ALL_CHARS,
-                       rank=0, world=1, time_multiple=8):
+                       rank=0, world=1, time_multiple=8, spec_augment=None):
         """The corpus built from WAVEFORMS on the GPU: all utterances go through the log-mel frontend in ONE
         batched call (frontend.log_fbank_batch -> ssasr_logmel_batch; src/preprocess.py:187-208 is what it
         replaces) and the frames stay on the device -- no .npy round trip, no host copy of the features.  `waves`: 1-D float arrays
@@ -97,10 +103,11 @@ class GpuResidentLoader:
         self.rows = None
         labels = [[char2idx[SOS_TKN]] + [char2idx[c] for c in texts[i]] + [char2idx[EOS_TKN]] for i in order]
         self._setup(None, labels, batch_size, device, rank, world, time_multiple, char2idx[SOS_TKN],
-                    resident=(feats, first, frames))
+                    resident=(feats, first, frames), spec_augment=spec_augment)
         return self
 
-    def _setup(self, kept, labels, batch_size, device, rank, world, time_multiple, pad, resident=None):
+    def _setup(self, kept, labels, batch_size, device, rank, world, time_multiple, pad, resident=None,
+               spec_augment=None):
         """kept: the utterances' unpadded [n_i, F] arrays (uploaded back to back), or None with
         resident = (frames tensor on the device, first row of every utterance, its frame count)."""
         self.device = torch.device(device)
@@ -136,6 +143,7 @@ class GpuResidentLoader:
                 y[i, :len(e)] = e
             self.y.append(torch.from_numpy(y).to(self.device))
             self.y_lens.append([int(v) + 1 for v in (y != 0).sum(-1)])      # prepare_y
+        self._set_spec_augment(spec_augment)
 
     def __len__(self):
         return len(self.starts)
@@ -143,16 +151,47 @@ class GpuResidentLoader:
     def bytes_resident(self):
         return 0 if self.frames is None else self.frames.numel() * 4
 
+    def _set_spec_augment(self, spec_augment):
+        """spec_augment: None, or a dict of struct ssasr_specaug's fields (include/ssasr.h) with the time cap
+        given as `time_ratio` (-> time_permille = round(1000 * ratio)): SpecAugment masks drawn per utterance
+        and epoch, applied by the kernel that assembles the batch (ssasr_gather_batch_aug)."""
+        self.epoch = self._next_epoch = 0
+        self.spec_augment = None
+        if spec_augment is None:
+            return
+        from . import ops
+        spec = ops.specaug_params(spec_augment)
+        if not (0 <= spec.n_freq <= 8 and 0 <= spec.n_time <= 8 and 0 <= spec.max_freq <= self.feature_dim and
+                spec.max_time >= 0 and 0 <= spec.time_permille <= 1000):
+            raise ValueError('spec_augment: out of range (at most 8 masks of a kind, 0 <= max_freq <= %d, '
+                             'max_time >= 0, 0 <= time_ratio <= 1): %r' % (self.feature_dim, spec_augment))
+        self.spec_augment = spec
+        # an utterance's masks follow its index in the corpus, not its batch or slot
+        self.utt_ids = torch.arange(len(self.x_lens), dtype=torch.int32, device=self.device)
+
+    def set_epoch(self, epoch):
+        """The epoch the next pass over the loader draws its masks for (resuming a run)."""
+        self.epoch = self._next_epoch = int(epoch)
+
     def batch(self, b):
         from . import ops
         s = self.starts[b]
         lens = self.x_lens[s:s + self.batch_size]
         m = self.time_multiple
         T = (max(max(lens), 1) + m - 1) // m * m
-        x = ops.gather_batch(self.frames, self.offsets[s:s + self.batch_size],
-                             self.lens_dev[s:s + self.batch_size], T)
+        if self.spec_augment is None:
+            x = ops.gather_batch(self.frames, self.offsets[s:s + self.batch_size],
+                                 self.lens_dev[s:s + self.batch_size], T)
+        else:
+            self.spec_augment.epoch = self.epoch
+            x = ops.gather_batch_aug(self.frames, self.offsets[s:s + self.batch_size],
+                                     self.lens_dev[s:s + self.batch_size], self.utt_ids[s:s + self.batch_size], T,
+                                     self.spec_augment)
         return x, list(lens), self.y[b], list(self.y_lens[b])
 
     def __iter__(self):
+        # every pass over the loader is one epoch of the mask draws: 0, 1, ... (or from set_epoch's value)
+        self.epoch = self._next_epoch
+        self._next_epoch += 1
         for b in rank_batches(len(self.starts), self.rank, self.world):
             yield (b,) + self.batch(b)

@@ -837,6 +837,35 @@ class _CELoss(torch.autograd.Function):
         return dlogits, None
 
 
+class _CELossLS(torch.autograd.Function):
+    """_CELoss with label smoothing eps in (0, 1): ssasr_ce_loss_ls_fwd / _bwd."""
+
+    @staticmethod
+    def forward(ctx, logits, y32, eps):
+        lib = _lib.load()
+        _need_gpu(logits, y32)
+        logits = _f32c(logits)
+        B, U, V = logits.shape
+        lse = torch.empty(B * U + 9 * B, device=logits.device, dtype=torch.float32)
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        check(lib.ssasr_ce_loss_ls_fwd(_p(logits), _p(y32), y32.stride(0), y32.shape[1], B, U, V, eps, _p(lse),
+                                       _p(loss), _stream()), 'ssasr_ce_loss_ls_fwd')
+        ctx.save_for_backward(logits, y32, lse)
+        ctx.eps = eps
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        lib = _lib.load()
+        logits, y32, lse = ctx.saved_tensors
+        B, U, V = logits.shape
+        dloss = dloss.to(torch.float32).contiguous()
+        dlogits = torch.empty_like(logits)
+        check(lib.ssasr_ce_loss_ls_bwd(_p(logits), _p(y32), y32.stride(0), _p(lse), _p(dloss), B, U, V, ctx.eps,
+                                       _p(dlogits), _stream()), 'ssasr_ce_loss_ls_bwd')
+        return dlogits, None, None
+
+
 _i32_cache = (None, None, None)      # (weak reference to the source tensor, its version, the int32 copy)
 
 
@@ -856,12 +885,19 @@ def as_i32(t):
     return copy
 
 
-def masked_ce_loss(logits, y, ans_len):
+def masked_ce_loss(logits, y, ans_len, label_smoothing=0.0):
     """src/trainer.py:426-434.  logits [B,U,V] (U >= ans_len), y [B,L] int, L > ans_len: the
-    labels are y[:, 1:ans_len + 1], read in place; rows are normalised by count(y != 0)."""
+    labels are y[:, 1:ans_len + 1], read in place; rows are normalised by count(y != 0).
+    label_smoothing in [0, 1) (build-defined, the reference has none): the token loss of
+    torch's cross_entropy(label_smoothing=...), uniform over all V classes; 0 is the reference's loss."""
+    label_smoothing = float(label_smoothing)
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError('label_smoothing must lie in [0, 1), got %r' % label_smoothing)
     if logits.shape[1] != ans_len:
         logits = logits[:, :ans_len].contiguous()
-    return _CELoss.apply(logits, as_i32(y))
+    if label_smoothing == 0.0:
+        return _CELoss.apply(logits, as_i32(y))
+    return _CELossLS.apply(logits, as_i32(y), label_smoothing)
 
 
 # ---------------------------------------------------------------------------
@@ -978,6 +1014,49 @@ def gather_batch(frames, offsets, lens, T):
     out = torch.empty(B, T, F, device=frames.device, dtype=torch.float32)
     check(lib.ssasr_gather_batch(_p(frames), _p(offsets), _p(lens), B, T, F, _p(out), _stream()),
           'ssasr_gather_batch')
+    return out
+
+
+def specaug_params(spec, epoch=0):
+    """struct ssasr_specaug from a dict of its fields (n_freq, max_freq, n_time, max_time, fill, seed, and the
+    time cap as `time_ratio` in [0, 1] -> time_permille = round(1000 * ratio), or `time_permille` itself)."""
+    spec = dict(spec)
+    if 'time_ratio' in spec:
+        spec['time_permille'] = int(round(1000 * spec.pop('time_ratio')))
+    unknown = set(spec) - {f[0] for f in _lib.SpecAug._fields_}
+    if unknown:
+        raise ValueError('spec_augment: unknown keys %s' % sorted(unknown))
+    return _lib.SpecAug(int(spec.get('n_freq', 0)), int(spec.get('max_freq', 0)), int(spec.get('n_time', 0)),
+                        int(spec.get('max_time', 0)), int(spec.get('time_permille', 1000)),
+                        float(spec.get('fill', 0.0)), int(spec.get('seed', 0)), int(spec.get('epoch', epoch)))
+
+
+def specaug_plan(spec, utt_id, length, F):
+    """The (start, width) rows of one utterance's masks, frequency masks first (ssasr_specaug_plan: host only)."""
+    import ctypes
+    lib = _lib.load()
+    n = spec.n_freq + spec.n_time
+    masks = (ctypes.c_int32 * (2 * max(n, 1)))()
+    check(lib.ssasr_specaug_plan(ctypes.byref(spec), utt_id, length, F, masks), 'ssasr_specaug_plan')
+    return [(masks[2 * j], masks[2 * j + 1]) for j in range(n)]
+
+
+def gather_batch_aug(frames, offsets, lens, utt_ids, T, spec, out=None):
+    """gather_batch with the utterances' SpecAugment masks applied in the same pass (see include/ssasr.h).
+    utt_ids int32 [B] on the GPU: corpus indices; spec: a _lib.SpecAug (specaug_params); out: the [B, T, F]
+    float32 tensor to fill, allocated when None."""
+    import ctypes
+    lib = _lib.load()
+    _need_gpu(frames, offsets, lens, utt_ids)
+    B, F = offsets.shape[0], frames.shape[1]
+    if out is None:
+        out = torch.empty(B, T, F, device=frames.device, dtype=torch.float32)
+    elif out.shape != (B, T, F) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != frames.device:
+        raise ValueError('gather_batch_aug: out must be a contiguous float32 [B, T, F] tensor on the frames\' device')
+    if utt_ids.dtype != torch.int32 or utt_ids.shape != (B,) or not utt_ids.is_contiguous():
+        raise TypeError('gather_batch_aug: utt_ids must be a contiguous int32 [B] tensor')
+    check(lib.ssasr_gather_batch_aug(_p(frames), _p(offsets), _p(lens), _p(utt_ids), B, T, F, ctypes.byref(spec),
+                                     _p(out), _stream()), 'ssasr_gather_batch_aug')
     return out
 
 

@@ -249,8 +249,60 @@ LMTrainer = CHARLMTrainer
 
 
 class ASRTrainer(Solver):
+    """src/trainer.py:377-537.  BUILD-DEFINED keys (the reference's recipe has neither; both absent: off, and
+    training is the reference's plain masked CE on unaugmented filterbanks):
+    asr.label_smoothing in [0, 1): the train loss is the smoothed CE of ops.masked_ce_loss (the attention branch
+    only under the joint CTC loss); the logged `train_loss` is then the SMOOTHED loss, while valid() keeps
+    reporting the unsmoothed metrics.
+    asr.spec_augment: {freq_masks, freq_width, time_masks, time_width, time_ratio, fill, seed}: SpecAugment
+    masks (at most 8 of a kind; widths drawn from 0 .. *_width, time masks no wider than time_ratio of the
+    utterance) applied by the resident loader's batch assembly (GpuResidentLoader, ssasr_gather_batch_aug),
+    redrawn every epoch; it needs that loader and raises where it is not in use."""
+    SPEC_AUGMENT_KEYS = ('freq_masks', 'freq_width', 'time_masks', 'time_width', 'time_ratio', 'fill', 'seed')
+
+    @classmethod
+    def regularisers(cls, asr_config):
+        """(label smoothing, GpuResidentLoader's spec_augment dict or None) of asr_config, validated."""
+        import math
+
+        def number(key, v):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError('asr.{} must be a finite number, got {!r}'.format(key, v))
+            return v
+
+        def integer(key, v, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError('asr.{} must be an integer in {} .. {}, got {!r}'.format(key, lo, hi, v))
+            return v
+
+        eps = asr_config.get('label_smoothing')
+        eps = 0.0 if eps is None else float(number('label_smoothing', eps))
+        if not 0.0 <= eps < 1.0:
+            raise ValueError('asr.label_smoothing must lie in [0, 1), got {!r}'.format(eps))
+        conf = asr_config.get('spec_augment')
+        if conf is None:
+            return eps, None
+        if not isinstance(conf, dict):
+            raise ValueError('asr.spec_augment must be a mapping of {}, got {!r}'.format(cls.SPEC_AUGMENT_KEYS, conf))
+        unknown = sorted(set(conf) - set(cls.SPEC_AUGMENT_KEYS))
+        if unknown:
+            raise ValueError('asr.spec_augment: unknown keys {} (known: {})'.format(unknown, cls.SPEC_AUGMENT_KEYS))
+        feat = asr_config.get('mdl', {}).get('feature_dim')
+        ratio = number('spec_augment.time_ratio', conf.get('time_ratio', 1.0))
+        if not 0.0 <= ratio <= 1.0:
+            raise ValueError('asr.spec_augment.time_ratio must lie in [0, 1], got {!r}'.format(ratio))
+        return eps, dict(
+            n_freq=integer('spec_augment.freq_masks', conf.get('freq_masks', 0), 0, 8),
+            max_freq=integer('spec_augment.freq_width', conf.get('freq_width', 0), 0,
+                             feat if isinstance(feat, int) else 2 ** 31 - 1),
+            n_time=integer('spec_augment.time_masks', conf.get('time_masks', 0), 0, 8),
+            max_time=integer('spec_augment.time_width', conf.get('time_width', 0), 0, 2 ** 31 - 1),
+            time_ratio=ratio, fill=float(number('spec_augment.fill', conf.get('fill', 0.0))),
+            seed=integer('spec_augment.seed', conf.get('seed', 0), 0, 2 ** 64 - 1))
+
     def __init__(self, config, paras):
         super().__init__(config, paras, 'asr')
+        self.label_smoothing, self.spec_augment = self.regularisers(self.config['asr'])
 
     def load_data(self):
         """Index files must be sorted so that every batch is in decreasing
@@ -273,9 +325,14 @@ class ASRTrainer(Solver):
                 r['unpadded_num_frames'] for r in self.train_set.dataset._rows)
             if est < free // 4:
                 self.gpu_loader = GpuResidentLoader(self.config['asr']['train_index'], self.train_batch_size,
-                                                    self.device, rank=self.rank, world=self.world)
+                                                    self.device, rank=self.rank, world=self.world,
+                                                    spec_augment=self.spec_augment)
                 self.verbose('Training corpus resident on the GPU: {:.1f} MB'.format(
                     self.gpu_loader.bytes_resident() / 1e6))
+        if self.spec_augment is not None and self.gpu_loader is None:
+            raise RuntimeError('asr.spec_augment is applied by the GPU-resident loader\'s batch assembly, which is '
+                               'not in use here (no GPU, asr.gpu_resident_loader: false, or a corpus too large to '
+                               'keep on the device): refusing to train unaugmented')
 
     def _train_batches(self):
         """(batch index, x, x_lens, y, y_lens) for this rank's batches of one epoch.  Every rank
@@ -312,7 +369,8 @@ class ASRTrainer(Solver):
             # the fused step (engine.ASRTrainStep): what bench.py times is what trains
             from .engine import ASRTrainStep
             step_cls = JointCTCTrainStep if joint else ASRTrainStep
-            self.train_step = step_cls(self.asr_model, lr=opt['learning_rate'], eps=1e-8, grad_clip=5.0)
+            self.train_step = step_cls(self.asr_model, lr=opt['learning_rate'], eps=1e-8, grad_clip=5.0,
+                                       label_smoothing=self.label_smoothing)
             self.flat, self.optim = self.train_step.flat, self.train_step.optim
         elif joint:
             raise RuntimeError('the joint CTC+attention loss runs on the fused step only (Adadelta on the GPU)')
@@ -320,10 +378,10 @@ class ASRTrainer(Solver):
             self.optim = getattr(torch.optim, opt['type'])(
                 self.asr_model.parameters(), lr=opt['learning_rate'], eps=1e-8)
 
-    def _loss(self, prediction, y, ans_len):
-        """src/trainer.py:426-434."""
+    def _loss(self, prediction, y, ans_len, label_smoothing=0.0):
+        """src/trainer.py:426-434 (valid() calls it unsmoothed)."""
         if prediction.is_cuda:
-            return ops.masked_ce_loss(prediction, y, ans_len)
+            return ops.masked_ce_loss(prediction, y, ans_len, label_smoothing)
         raise RuntimeError('ss_asr_amd computes on the GPU only')
 
     def exec(self):
@@ -349,7 +407,7 @@ class ASRTrainer(Solver):
                 else:
                     self.optim.zero_grad()
                     _, prediction, _ = self.asr_model(x, ans_len, teacher=y, state_len=state_len)
-                    loss = self._loss(prediction, y, ans_len)
+                    loss = self._loss(prediction, y, ans_len, self.label_smoothing)
                     loss.backward()
                     self.step(self.asr_model.parameters(), self.optim)
                     if self.tr.step % self.logging_step == 0:

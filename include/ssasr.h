@@ -27,7 +27,8 @@
  * ssasr_beam, ssasr_decode_beam_ws_bytes, ssasr_decode_beam; joint CTC / attention decoding -- ssasr_ctc_prefix,
  * ssasr_decode_beam_ctc_ws_bytes, ssasr_decode_beam_ctc; length bonus, coverage term and end detection in the beam
  * search -- ssasr_beam_terms, ssasr_decode_beam_ex_ws_bytes, ssasr_decode_beam_ex; SpecAugment in batch assembly and label smoothing in the
- * masked CE -- ssasr_specaug, ssasr_gather_batch_aug, ssasr_specaug_plan, ssasr_ce_loss_ls_fwd, ssasr_ce_loss_ls_bwd.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
+ * masked CE -- ssasr_specaug, ssasr_gather_batch_aug, ssasr_specaug_plan, ssasr_ce_loss_ls_fwd, ssasr_ce_loss_ls_bwd; CTC forced
+ * alignment -- ssasr_ctc_align_ws_bytes, ssasr_ctc_align.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
  * (nothing older changed).  15: inference -- ssasr_charlm, ssasr_charlm_step, ssasr_infer, ssasr_decode_greedy (nothing
  * older changed).  14 and before: the training entry points below.
  *
@@ -409,6 +410,45 @@ int ssasr_ctc_loss_bwd(const float* logits, const int32_t* frame_lens, const int
                        const int32_t* label_lens, int64_t B, int64_t T, int64_t V, int64_t Lmax,
                        int blank, float* ws, const float* dloss, float* dlogits, float* dbias,
                        void* stream);
+
+/* ---- CTC forced alignment (added under ABI 16) ------------------------------------------------------------------
+ * BUILD-DEFINED: the reference has no CTC.  The most probable CTC path (Viterbi) of given labels through the frames
+ * of the head that ssasr_ctc_loss_fwd trains: when each character was spoken, and how confident the head is of it.
+ * logits [B][T][V] are the raw head outputs, as ssasr_ctc_loss_fwd takes them; frame_lens, y, y_ld, label_lens,
+ * Lmax and blank are that entry's too.
+ *   Lattice, per utterance: len = min(frame_lens[b], T), L = label_lens[b]; the extended sequence has S = 2 L + 1
+ *   states, lab_s = blank at even s, label (s - 1) / 2 at odd s.  It is held in double and runs on the RAW logits,
+ *   not on log-softmax values -- every path visits every frame exactly once, so the per-frame normaliser cannot
+ *   change which path wins:
+ *     d[0][s] = (double)logit[0][lab_s] for s < 2, -inf otherwise
+ *     d[t][s] = best(d[t-1][s], d[t-1][s-1], d[t-1][s-2] if the skip is allowed) + (double)logit[t][lab_s]
+ *   the skip being allowed as in the loss: s odd, s >= 3, lab_s != lab_{s-2}.
+ *   Tie rule: the larger value wins; among equal values staying (s) wins over s - 1, which wins over s - 2; at the
+ *   end s = S - 1 wins over S - 2 (S > 1).
+ *   Exactness: each lattice value is ONE double add and comparisons, taken in frame order, so a float64 restatement
+ *   that does the same operations gets the same bits, and the path is defined exactly -- tests compare it for
+ *   equality, with no gap rule.  (A form of the kernel that reorders the sum or holds a float lattice is wrong.)
+ *   Outputs: path[b][t] = the state 0 .. 2 L of frame t < len (character (s - 1) / 2 for odd s, blank for even s),
+ *   -1 from len on; first[b][j] / last[b][j] = the first / last (inclusive) frame whose state is 2 j + 1, -1 for
+ *   j >= L; char_logp[b][j] = sum over those frames of logit[t][y_j] - lse_t, 0 for j >= L; score[b] = d_end -
+ *   sum_{t < len} lse_t, the log-probability of the path.  lse_t is the frame's log-sum-exp, (double)max +
+ *   (double)logf(sum expf(x - max)) as the loss kernels' table computes it, accumulated in double.
+ *   No alignment (len < 1, L < 0, L > Lmax, or len < L + the number of adjacent equal labels): score = -inf, the
+ *   row's path, first and last are -1 and its char_logp 0.  Nothing is left unwritten.
+ * Accepted: what ssasr_ctc_loss_fwd accepts (2 * Lmax + 1 <= 1024, V <= 1024, B <= 65535), 0 <= blank < V, ws
+ * 8-byte aligned with ws_bytes >= ssasr_ctc_align_ws_bytes(...) (0: no kernel for the shape).  Lmax == 0 is legal:
+ * first, last and char_logp may then be NULL.  Argument errors return before any HIP call.
+ * One launch, one workgroup per utterance, one state per thread.  A step's back-pointers (two bits per state, packed
+ * per 64 states) stay in LDS while T * ceil((2 * Lmax + 1) / 64) * 16 bytes <= 128 KB, i.e. for
+ * T <= 8192 / ceil((2 * Lmax + 1) / 64) (integer division: 8192 frames up to Lmax 31, 819 at Lmax 300, 512 at Lmax
+ * 511); from one frame more they go through the workspace.  Both forms give the same bits.  The workspace holds the
+ * normalisers [B][T] (double), the back-pointers of the second form, and in its last 4 x B 64-bit words each
+ * utterance's wall_clock64 at the start, before and after the traceback and at the end (tools/align_time.py). */
+int64_t ssasr_ctc_align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t Lmax);
+int ssasr_ctc_align(const float* logits, const int32_t* frame_lens, const int32_t* y, int64_t y_ld,
+                    const int32_t* label_lens, int64_t B, int64_t T, int64_t V, int64_t Lmax, int blank,
+                    void* ws, int64_t ws_bytes, int32_t* path, int32_t* first, int32_t* last,
+                    float* char_logp, double* score, void* stream);
 
 /* Solver.step (src/trainer.py:131-148) with torch.optim.Adadelta
  * (src/trainer.py:401-403) on flat buffers of n floats: total L2 norm of

@@ -134,6 +134,8 @@ SIGNATURES = {
     'ssasr_ctc_ws_floats': (I64, [I64, I64, I64, I64]),
     'ssasr_ctc_loss_fwd': (I32, [P, P, P, I64, P, I64, I64, I64, I64, I32, P, P, P]),
     'ssasr_ctc_loss_bwd': (I32, [P, P, P, I64, P, I64, I64, I64, I64, I32, P, P, P, P, P]),
+    'ssasr_ctc_align_ws_bytes': (I64, [I64, I64, I64, I64]),
+    'ssasr_ctc_align': (I32, [P, P, P, I64, P, I64, I64, I64, I64, I32, P, I64, P, P, P, P, P, P]),
     'ssasr_clip_adadelta_ws': (I64, [I64]),
     'ssasr_clip_adadelta': (I32, [P, P, P, P, I64, F32, F32, F32, F32, F32, P, P, I32, P]),
     'ssasr_adam_ws': (I64, [I64]),

@@ -8,6 +8,7 @@ nn.Embedding) are parameter containers only: they give the same
 the reference, so checkpoints and seeded initialisations interchange.  Their
 ``forward`` is never called; all arithmetic goes through ``ss_asr_amd.ops``.
 """
+import collections
 import math
 import os
 import random
@@ -16,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .preprocess import EOS_TKN
+from .preprocess import EOS_TKN, SOS_TKN
 
 
 def _dev_i32(values, device):
@@ -29,6 +30,23 @@ def _dev_i32(values, device):
     return t.pin_memory().to(device, non_blocking=True)
 
 EOS_INDEX = 1   # '>' in TOKENS + ALL_CHARS (src/preprocess.py:17-27)
+
+ENCODER_STRIDE = 8      # input frames per encoder frame: three pBLSTM layers, each halving the time axis
+
+# ASR.align's result for one utterance (BUILD-DEFINED).  score: log-probability of the best CTC path (float, -inf
+# when no alignment fits); chars: [(char, first_frame, last_frame_exclusive, logp)] in input frames (seconds with
+# frame_shift), or None when no alignment fits.
+Alignment = collections.namedtuple('Alignment', ('score', 'chars'))
+
+
+def input_span(first, last, n_frames, frame_shift=None):
+    """Encoder frames first .. last (inclusive) -> the input frames [lo, hi) they cover: encoder frame j covers
+    input frames [8 j, 8 j + 8), clipped to the utterance's n_frames.  frame_shift (seconds per input frame): both
+    ends in seconds."""
+    lo, hi = min(ENCODER_STRIDE * first, n_frames), min(ENCODER_STRIDE * (last + 1), n_frames)
+    if frame_shift is None:
+        return lo, hi
+    return lo * float(frame_shift), hi * float(frame_shift)
 
 
 def _check_lengths(state_len, tmax):
@@ -260,6 +278,11 @@ class ASR(nn.Module):
         self.last_beam = None
         # n_steps [N] int32 of the last decode_nbest call that had a length bonus, a coverage term or end detection on
         self.last_beam_steps = None
+        # _encode_packed's most recent result: (features [N, T'max, E], int32 [N] frame counts), what align() reuses
+        self.last_encoded_packed = None
+        # align's device results: (path [N, T'], first [N, Lmax], last [N, Lmax], char_logp [N, Lmax], score [N] double,
+        # logits [N, T', V])
+        self.last_align = None
         self.init_parameters()
 
     def init_parameters(self):
@@ -334,6 +357,8 @@ class ASR(nn.Module):
             host = att.detach().cpu()
         return encode_len, logits, host
 
+    _NO_CTC_HEAD = 'ctc_weight > 0 needs a model with a ctc_head (ctc.JointCTCASR); %s has none'
+
     def _ctc_head(self, ctc_weight):
         """None for ctc_weight 0 (today's path), else (ctc_head weight, bias, ctc_weight) of a model that has one."""
         ctc_weight = float(ctc_weight)
@@ -343,8 +368,7 @@ class ASR(nn.Module):
             return None
         head = getattr(self, 'ctc_head', None)
         if head is None:
-            raise ValueError('ctc_weight > 0 needs a model with a ctc_head (ctc.JointCTCASR); %s has none'
-                             % type(self).__name__)
+            raise ValueError(self._NO_CTC_HEAD % type(self).__name__)
         return head.weight, head.bias, ctc_weight
 
     @staticmethod
@@ -398,7 +422,56 @@ class ASR(nn.Module):
             packed = torch.zeros(len(feats), tmax, feats[0].shape[2], device=dev, dtype=torch.float32)
             for n, f in enumerate(feats):
                 packed[n, :f.shape[1]] = f[0]
-        return packed, _dev_i32(enc_lens, dev)
+        self.last_encoded_packed = (packed, _dev_i32(enc_lens, dev))
+        return self.last_encoded_packed
+
+    def align(self, xs, x_lens, texts, mapper, *, frame_shift=None, encoded=None):
+        """BUILD-DEFINED: CTC forced alignment of texts[i] to utterance i (xs, x_lens as decode_many takes them) on a
+        model with a ctc_head: the most probable CTC path of the text through the head's frames (ssasr_ctc_align,
+        include/ssasr.h).  `<` and `>` are stripped from the texts, <eos> is not aligned; a character the mapper does
+        not know is a ValueError.  Each utterance is encoded alone (_encode_packed), then ONE align launch serves the
+        group.  encoded: a (features, frame counts) pair that _encode_packed already returned for these utterances
+        (last_encoded_packed after a decode), used instead of encoding again.
+        Returns one Alignment(score, chars) per utterance: chars = [(char, first_frame, last_frame_exclusive, logp)]
+        in INPUT frames (input_span: encoder frame j covers input frames [8 j, 8 j + 8), clipped to the utterance's
+        length; seconds when frame_shift, the seconds per input frame, is given), logp = the head's log-probability
+        of the character summed over its frames; chars is None and score -inf when no alignment fits.  last_align
+        keeps (path, first, last, char_logp, score, logits) on the device, in encoder frames."""
+        head = getattr(self, 'ctc_head', None)
+        if head is None:
+            raise ValueError(self._NO_CTC_HEAD % type(self).__name__)
+        if not len(xs) == len(x_lens) == len(texts):
+            raise ValueError('align: %d utterances, %d lengths, %d texts' % (len(xs), len(x_lens), len(texts)))
+        texts = [t.replace(SOS_TKN, '').replace(EOS_TKN, '') for t in texts]
+        labels = []
+        for text in texts:
+            try:
+                labels.append([int(mapper.char_to_ind(c)) for c in text])
+            except (KeyError, ValueError):
+                raise ValueError('align: %r has a character the mapper does not know' % (text,)) from None
+        lmax = max(len(row) for row in labels)
+        with torch.no_grad():
+            packed, enc_lens = encoded if encoded is not None else self._encode_packed(xs, x_lens)
+            if packed.shape[0] != len(texts):
+                raise ValueError('align: the encoded group holds %d utterances, not %d' % (packed.shape[0], len(texts)))
+            y = torch.zeros(len(labels), max(lmax, 1), dtype=torch.int32)
+            for i, row in enumerate(labels):
+                y[i, :len(row)] = torch.tensor(row, dtype=torch.int32)
+            y = y.to(packed.device)
+            self.last_align = ops.ctc_head_align(packed, head.weight, head.bias, enc_lens, y,
+                                                 _dev_i32([len(row) for row in labels], packed.device), lmax,
+                                                 ops.CTC_BLANK)
+        _, first, last, char_logp, score, _ = self.last_align
+        first, last, char_logp, score = first.cpu().tolist(), last.cpu().tolist(), char_logp.cpu().tolist(), score.cpu().tolist()
+        out = []
+        for i, text in enumerate(texts):
+            if score[i] == -math.inf:
+                out.append(Alignment(score[i], None))
+                continue
+            n = int(x_lens[i][0])
+            out.append(Alignment(score[i], [(c,) + input_span(first[i][j], last[i][j], n, frame_shift) + (char_logp[i][j],)
+                                            for j, c in enumerate(text)]))
+        return out
 
     def decode_many(self, xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1,
                     ctc_weight=0.0, length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None):

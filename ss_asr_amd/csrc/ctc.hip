@@ -266,7 +266,234 @@ int check_shape(int64_t B, int64_t T, int64_t V, int64_t Lmax) {
   return SSASR_OK;
 }
 
+// ---- forced alignment: the max-product lattice with back-pointers and a traceback (include/ssasr.h) ----------
+// BUILD-DEFINED like the rest of this file.  The lattice runs on the RAW logits: every path visits every frame
+// once, so the per-frame normaliser cannot change which path wins, and each lattice value is then one double add
+// and comparisons in frame order -- a float64 restatement that does the same operations gets the same bits, which
+// is why the tests demand the exact path.  The normalisers lse_t (ctc_table's formula) only enter score and
+// char_logp.
+//
+// One workgroup per utterance, one state per thread, two LDS lines, one barrier per frame, the frame's logit
+// loaded one step ahead (no table: a state reads ONE class per frame).  A step's back-pointer is two bits per
+// state; a wave packs its 64 states with two ballots into two 64-bit words, so a frame's row is
+// ceil(Sp / 64) * 16 bytes.  The rows stay in LDS while T * ceil(Sp / 64) * 16 <= 128 KB (T <= 819 at Sp = 601,
+// T <= 512 at Sp = 1023) and go to the workspace otherwise.  The traceback is wave 0's: per 64 frames every lane
+// loads its frame's words for the (at most three) 64-state groups the path can reach in 64 steps, then the 64
+// dependent steps run on registers and cross-lane reads, so the chain pays one memory latency per 64 frames.
+constexpr int64_t ALIGN_LDS_BP_BYTES = 128 * 1024;
+constexpr int ALIGN_RED_DOUBLES = 16;                       // one partial sum per wave
+
+struct AlignArgs {
+  const float* logits;       // [B][T][V]
+  const int32_t* frame_lens; // [B]
+  const int32_t* y;
+  int64_t y_ld;
+  const int32_t* label_lens; // [B]
+  int T, V, Sp, Lmax, blank;
+  int groups;                // ceil(Sp / 64): 64-state groups of a back-pointer row
+  double* lse;               // [B][T] the frames' log-sum-exp
+  unsigned long long* bp;    // [B][T][groups][2] or nullptr when the rows fit LDS
+  int32_t* path;             // [B][T]
+  int32_t* first;            // [B][Lmax]
+  int32_t* last;             // [B][Lmax]
+  float* char_logp;          // [B][Lmax]
+  double* score;             // [B]
+  long long* stamps;         // [B][4] wall_clock64 at the start, before and after the traceback, at the end (tools/align_time.py)
+};
+
+template <int NT>
+__device__ void align_none(const AlignArgs& a, int b) {
+  for (int t = threadIdx.x; t < a.T; t += NT) a.path[(int64_t)b * a.T + t] = -1;
+  for (int j = threadIdx.x; j < a.Lmax; j += NT) {
+    a.first[(int64_t)b * a.Lmax + j] = -1;
+    a.last[(int64_t)b * a.Lmax + j] = -1;
+    a.char_logp[(int64_t)b * a.Lmax + j] = 0.f;
+  }
+  if (threadIdx.x == 0) a.score[b] = NEG_INF;
+}
+
+template <bool LDS_BP, int NT>
+__global__ __launch_bounds__(NT) void ctc_align_kernel(AlignArgs a) {
+  extern __shared__ double smem_d[];
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int len = min(a.frame_lens[b], a.T), L = a.label_lens[b], S = 2 * L + 1, V = a.V;
+  if (len < 1 || L < 0 || S > a.Sp) {        // nothing to align
+    align_none<NT>(a, b);
+    return;
+  }
+  double* line0 = smem_d;                    // [2 pads][Sp]
+  double* line1 = line0 + ctc_line_doubles(a.Sp);
+  double* red = line1 + ctc_line_doubles(a.Sp);
+  unsigned long long* bp_lds = reinterpret_cast<unsigned long long*>(red + ALIGN_RED_DOUBLES);
+  unsigned long long* bp = LDS_BP ? bp_lds : a.bp + (int64_t)b * a.T * a.groups * 2;
+  int* sl = reinterpret_cast<int*>(bp_lds + (LDS_BP ? (int64_t)a.T * a.groups * 2 : 0));
+  const float* logits = a.logits + (int64_t)b * a.T * V;
+  const int32_t* yr = a.y + (int64_t)b * a.y_ld;
+  double* lse = a.lse + (int64_t)b * a.T;
+  int32_t* path = a.path + (int64_t)b * a.T;
+  long long* stamps = a.stamps + (int64_t)b * 4;
+  if (tid == 0) stamps[0] = wall_clock64();
+
+  for (int s = tid; s < S; s += NT) sl[s] = (s & 1) ? yr[s >> 1] : a.blank;
+  // the frames' normalisers, one wave per frame (ctc_table's arithmetic)
+  for (int t = wave; t < len; t += NT / 64) {
+    const float* row = logits + (int64_t)t * V;
+    float m = -INFINITY;
+    for (int v = lane; v < V; v += 64) m = fmaxf(m, row[v]);
+    m = wave_max(m);
+    float sum = 0.f;
+    for (int v = lane; v < V; v += 64) sum += expf(row[v] - m);
+    sum = wave_sum(sum);
+    if (lane == 0) lse[t] = (double)m + (double)logf(sum);
+  }
+  __syncthreads();
+
+  const int s = tid;
+  const int lab = s < S ? sl[s] : a.blank;
+  const bool skip = s < S && (s & 1) && s >= 3 && sl[s] != sl[s - 2];
+  const float* col = logits + lab;
+  if (tid < 2) { line0[tid] = NEG_INF; line1[tid] = NEG_INF; }
+  if (s < S) line0[2 + s] = s < 2 ? (double)col[0] : NEG_INF;
+  float x_next = len > 1 ? col[V] : 0.f;
+  __syncthreads();
+  double* prev = line0;
+  double* cur = line1;
+  for (int t = 1; t < len; ++t) {
+    const float x = x_next;
+    if (t + 1 < len) x_next = col[(int64_t)(t + 1) * V];
+    int from = 0;
+    if (s < S) {
+      double best = prev[2 + s];                              // stay wins a tie, then s - 1, then s - 2
+      const double one = prev[1 + s], two = skip ? prev[s] : NEG_INF;
+      if (one > best) { best = one; from = 1; }
+      if (two > best) { best = two; from = 2; }
+      cur[2 + s] = best + (double)x;
+    }
+    const unsigned long long lo = __ballot(from & 1), hi = __ballot(from >> 1);
+    if (lane == 0 && wave < a.groups) {
+      unsigned long long* w = bp + ((int64_t)t * a.groups + wave) * 2;
+      w[0] = lo;
+      w[1] = hi;
+    }
+    __syncthreads();
+    double* tmp = prev; prev = cur; cur = tmp;
+  }
+  const double end1 = prev[2 + S - 1], end2 = S > 1 ? prev[2 + S - 2] : NEG_INF;
+  const double d_end = end2 > end1 ? end2 : end1;            // S - 1 wins a tie
+  if (!(d_end > NEG_INF)) {                                  // the frames cannot hold the labels
+    align_none<NT>(a, b);
+    return;
+  }
+  if (tid == 0) stamps[1] = wall_clock64();
+  if (wave == 0) {
+    int st = end2 > end1 ? S - 2 : S - 1;
+    for (int t0 = len - 1; t0 >= 0; t0 -= 64) {
+      const int t = t0 - lane, top = st >> 6;
+      unsigned long long m0[3] = {0, 0, 0}, m1[3] = {0, 0, 0};   // frame t's words of groups top, top - 1, top - 2
+      if (t >= 1) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+          if (top - k >= 0) {
+            const unsigned long long* w = bp + ((int64_t)t * a.groups + (top - k)) * 2;
+            m0[k] = w[0];
+            m1[k] = w[1];
+          }
+      }
+      int mine = -1;
+      const int n = min(64, t0 + 1);
+      for (int i = 0; i < n; ++i) {                          // st falls by at most 2 per step: it stays in the three groups
+        if (lane == i) mine = st;
+        const int k = top - (st >> 6);
+        const unsigned long long lo = __shfl(k == 0 ? m0[0] : k == 1 ? m0[1] : m0[2], i);
+        const unsigned long long hi = __shfl(k == 0 ? m1[0] : k == 1 ? m1[1] : m1[2], i);
+        const int sh = st & 63;
+        st = max(st - (int)((lo >> sh) & 1) - 2 * (int)((hi >> sh) & 1), 0);
+      }
+      if (t >= 0) path[t] = mine;
+    }
+    if (tid == 0) stamps[2] = wall_clock64();
+  }
+  __syncthreads();
+  // derived outputs, in parallel from the path
+  for (int t = len + tid; t < a.T; t += NT) path[t] = -1;
+  int32_t* first = a.first + (int64_t)b * a.Lmax;
+  int32_t* last = a.last + (int64_t)b * a.Lmax;
+  float* clp = a.char_logp + (int64_t)b * a.Lmax;
+  for (int j = L + tid; j < a.Lmax; j += NT) { first[j] = -1; last[j] = -1; clp[j] = 0.f; }
+  double part = 0.0;
+  for (int t = tid; t < len; t += NT) {
+    part += lse[t];
+    const int q = path[t];
+    if (q & 1) {
+      if (t == 0 || path[t - 1] != q) first[q >> 1] = t;
+      if (t == len - 1 || path[t + 1] != q) last[q >> 1] = t;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) part += __shfl_xor(part, off);
+  if (lane == 0) red[wave] = part;
+  __syncthreads();
+  if (tid == 0) {
+    double total = 0.0;
+    for (int w = 0; w < NT / 64; ++w) total += red[w];
+    a.score[b] = d_end - total;
+  }
+  for (int j = tid; j < L; j += NT) {
+    const float* cj = logits + yr[j];
+    double acc = 0.0;
+    const int t_end = min(last[j], len - 1);
+    for (int t = max(first[j], 0); t <= t_end; ++t) acc += (double)cj[(int64_t)t * V] - lse[t];
+    clp[j] = (float)acc;
+  }
+  if (tid == 0) stamps[3] = wall_clock64();
+}
+
+int align_groups(int64_t Lmax) { return (int)((2 * Lmax + 1 + 63) / 64); }
+
+bool align_bp_in_lds(int64_t T, int64_t Lmax) { return T * align_groups(Lmax) * 16 <= ALIGN_LDS_BP_BYTES; }
+
+int align_check_shape(int64_t B, int64_t T, int64_t V, int64_t Lmax) {
+  if (check_shape(B, T, V, Lmax) != SSASR_OK || T > INT32_MAX) return SSASR_EARG;
+  return SSASR_OK;
+}
+
 }  // namespace
+
+extern "C" int64_t ssasr_ctc_align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t Lmax) {
+  if (align_check_shape(B, T, V, Lmax) != SSASR_OK) return 0;
+  return B * T * 8 + (align_bp_in_lds(T, Lmax) ? 0 : B * T * align_groups(Lmax) * 16) + B * 32;   // lse, back-pointers, stamps
+}
+
+extern "C" int ssasr_ctc_align(const float* logits, const int32_t* frame_lens, const int32_t* y, int64_t y_ld,
+                               const int32_t* label_lens, int64_t B, int64_t T, int64_t V, int64_t Lmax, int blank,
+                               void* ws, int64_t ws_bytes, int32_t* path, int32_t* first, int32_t* last,
+                               float* char_logp, double* score, void* stream) {
+  if (!logits || !frame_lens || !y || !label_lens || !ws || !path || !score) return SSASR_EARG;
+  if (align_check_shape(B, T, V, Lmax) != SSASR_OK || blank < 0 || blank >= V) return SSASR_EARG;
+  if (Lmax > 0 && (!first || !last || !char_logp)) return SSASR_EARG;
+  if ((reinterpret_cast<uintptr_t>(ws) & 7) || ws_bytes < ssasr_ctc_align_ws_bytes(B, T, V, Lmax)) return SSASR_EARG;
+  hipStream_t st = (hipStream_t)stream;
+  AlignArgs a{};
+  a.logits = logits; a.frame_lens = frame_lens; a.y = y; a.y_ld = y_ld; a.label_lens = label_lens;
+  a.T = (int)T; a.V = (int)V; a.Sp = (int)(2 * Lmax + 1); a.Lmax = (int)Lmax; a.blank = blank;
+  a.groups = align_groups(Lmax);
+  a.lse = reinterpret_cast<double*>(ws);
+  const bool in_lds = align_bp_in_lds(T, Lmax);
+  a.bp = in_lds ? nullptr : reinterpret_cast<unsigned long long*>(a.lse + B * T);
+  a.stamps = reinterpret_cast<long long*>(a.lse + B * T + (in_lds ? 0 : B * T * a.groups * 2));
+  a.path = path; a.first = first; a.last = last; a.char_logp = char_logp; a.score = score;
+  const size_t lds = (size_t)(a.Sp + 2) * 16 + ALIGN_RED_DOUBLES * 8 + (in_lds ? (size_t)T * a.groups * 16 : 0) +
+                     (size_t)a.Sp * 4;
+  const int nt = ctc_threads(a.Sp, 0);                       // one state per thread; classes are read by whole waves
+  void (*fn)(AlignArgs) = nullptr;
+  if (nt == 256) fn = in_lds ? ctc_align_kernel<true, 256> : ctc_align_kernel<false, 256>;
+  else if (nt == 512) fn = in_lds ? ctc_align_kernel<true, 512> : ctc_align_kernel<false, 512>;
+  else fn = in_lds ? ctc_align_kernel<true, 1024> : ctc_align_kernel<false, 1024>;
+  SSASR_HIP(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(fn, dim3((unsigned)B), dim3(nt), lds, st, a);
+  SSASR_LAUNCH_CHECK();
+  return SSASR_OK;
+}
 
 extern "C" int64_t ssasr_ctc_ws_floats(int64_t B, int64_t T, int64_t V, int64_t Lmax) {
   if (check_shape(B, T, V, Lmax) != SSASR_OK) return 0;

@@ -991,6 +991,47 @@ def ctc_head_loss(feat, weight, bias, frame_lens, y, label_lens, lmax, blank=0):
     return _CTCHead.apply(feat, weight, bias, frame_lens, y, label_lens, int(lmax), int(blank))
 
 
+def ctc_align(logits, frame_lens, y32, label_lens, lmax, blank=0):
+    """ssasr_ctc_align: the most probable CTC path (Viterbi) of each row's labels through its frames, on the raw
+    logits [B, T, V] (include/ssasr.h).  Arguments as ctc_loss.  -> (path [B, T] int32: the lattice state per
+    frame, -1 past the row's frames; first, last [B, lmax] int32: each character's first / last (inclusive) frame,
+    -1 past the row's labels; char_logp [B, lmax] float32; score [B] float64, -inf: no alignment fits) on the
+    device.  No autograd."""
+    lib = _lib.load()
+    lmax, blank = int(lmax), int(blank)
+    _need_gpu(logits, frame_lens, y32, label_lens)
+    logits = _f32c(logits.detach())
+    B, T, V = logits.shape
+    if y32.dtype != torch.int32 or y32.stride(-1) != 1:
+        raise TypeError('ctc_align: labels must be int32 with unit column stride')
+    if lmax > y32.shape[1]:
+        raise ValueError('ctc_align: Lmax exceeds the label matrix')
+    need = int(lib.ssasr_ctc_align_ws_bytes(B, T, V, lmax))
+    if need <= 0:
+        raise ValueError('ctc_align: shape B=%d T=%d V=%d Lmax=%d has no kernel' % (B, T, V, lmax))
+    dev = logits.device
+    ws = torch.empty(need // 8, device=dev, dtype=torch.float64)
+    path = torch.empty(B, T, device=dev, dtype=torch.int32)
+    first = torch.empty(B, lmax, device=dev, dtype=torch.int32)
+    last = torch.empty(B, lmax, device=dev, dtype=torch.int32)
+    char_logp = torch.empty(B, lmax, device=dev, dtype=torch.float32)
+    score = torch.empty(B, device=dev, dtype=torch.float64)
+    check(lib.ssasr_ctc_align(_p(logits), _p(frame_lens), _p(y32), y32.stride(0), _p(label_lens), B, T, V, lmax, blank,
+                              _p(ws), need, _p(path), _p(first) if lmax else None, _p(last) if lmax else None,
+                              _p(char_logp) if lmax else None, _p(score), _stream()), 'ssasr_ctc_align')
+    return path, first, last, char_logp, score
+
+
+def ctc_head_align(feat, weight, bias, frame_lens, y32, label_lens, lmax, blank=0):
+    """ctc_align on the head's logits, the product issued exactly as the training node issues it (_CTCHead.forward).
+    -> ctc_align's five tensors and the logits [B, T, V] they were aligned on.  No autograd."""
+    _need_gpu(feat, weight, bias)
+    feat, w, b = _f32c(feat.detach()), _f32c(weight.detach()), _f32c(bias.detach())
+    B, T, E = feat.shape
+    logits = gemm(feat.view(B * T, E), w, bias=b).view(B, T, w.shape[0])
+    return ctc_align(logits, frame_lens, y32, label_lens, lmax, blank) + (logits,)
+
+
 # ---------------------------------------------------------------------------
 # misc
 # ---------------------------------------------------------------------------

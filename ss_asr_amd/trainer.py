@@ -527,7 +527,11 @@ class ASRTester(Solver):
     asr.decode_length_bonus, asr.decode_coverage_weight (with asr.decode_coverage_threshold, absent: 0.5) and
     asr.decode_end_margin (absent: off) are the beam search's length bonus, coverage term and end detection
     (ssasr_decode_beam_ex, any beam size); `decode_file` gains `_lb<bonus>`, `_cov<weight>`, `_end<margin>` for the
-    terms that are on."""
+    terms that are on.
+    asr.decode_align: true (absent: off; needs 'ctc_weight' in asr.mdl, else set_model raises): after each group is
+    decoded its hypotheses are force-aligned to the group's encoder outputs (ASR.align, ssasr_ctc_align); exec()
+    still returns the strings, `last_alignments` holds one asr.Alignment per utterance in index order, and
+    `decode_file` gains `_align`."""
     decode_group = 32
     TERM_KEYS = ('decode_length_bonus', 'decode_coverage_weight', 'decode_coverage_threshold', 'decode_end_margin')
 
@@ -572,6 +576,10 @@ class ASRTester(Solver):
             n_jobs=self.set_if_exists('loader_jobs', 8), use_gpu=self.paras.gpu)
 
     def set_model(self):
+        self.decode_align = bool(self.config['asr'].get('decode_align', False))
+        if self.decode_align and 'ctc_weight' not in self.config['asr']['mdl']:
+            raise ValueError('asr.decode_align needs a model with a ctc_head: set asr.mdl.ctc_weight '
+                             '(ctc.JointCTCASR)')
         asr_cls = ASR
         if 'ctc_weight' in self.config['asr']['mdl']:
             from .ctc import JointCTCASR
@@ -599,6 +607,8 @@ class ASRTester(Solver):
             self.decode_file += '_ctc{:}'.format(self.decode_ctc_weight)
         self.decode_term_args, suffix = self.decode_terms(self.config['asr'])
         self.decode_file += suffix
+        if self.decode_align:
+            self.decode_file += '_align'
 
     def exec(self, lm_weight=None):
         """-> the decoded strings, one per utterance of the test index, in index order."""
@@ -617,11 +627,17 @@ class ASRTester(Solver):
             ''.join(', {} {}'.format(k.replace('_', ' '), v) for k, v in terms.items())))
         self.verbose('Number of utts to decode : {}, {} per launch.'.format(len(self.test_set), self.decode_group))
         results, xs, x_lens = [], [], []
+        if self.decode_align:
+            self.last_alignments = []
 
         def flush():
             if xs:
-                results.extend(self.asr_model.decode_many(xs, x_lens, self.lm, self.mapper, lm_weight,
-                                                          beam_size=beam, ctc_weight=ctc_weight, **terms))
+                texts = self.asr_model.decode_many(xs, x_lens, self.lm, self.mapper, lm_weight,
+                                                   beam_size=beam, ctc_weight=ctc_weight, **terms)
+                results.extend(texts)
+                if self.decode_align:            # on the group's encoder outputs: no second encode
+                    self.last_alignments.extend(self.asr_model.align(
+                        xs, x_lens, texts, self.mapper, encoded=self.asr_model.last_encoded_packed))
                 del xs[:], x_lens[:]
 
         for b_ind, (x, y) in enumerate(self.test_set):

@@ -28,7 +28,7 @@
  * ssasr_decode_beam_ctc_ws_bytes, ssasr_decode_beam_ctc; length bonus, coverage term and end detection in the beam
  * search -- ssasr_beam_terms, ssasr_decode_beam_ex_ws_bytes, ssasr_decode_beam_ex; SpecAugment in batch assembly and label smoothing in the
  * masked CE -- ssasr_specaug, ssasr_gather_batch_aug, ssasr_specaug_plan, ssasr_ce_loss_ls_fwd, ssasr_ce_loss_ls_bwd; CTC forced
- * alignment -- ssasr_ctc_align_ws_bytes, ssasr_ctc_align.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
+ * alignment -- ssasr_ctc_align_ws_bytes, ssasr_ctc_align; edit-distance scoring -- ssasr_edit_score.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
  * (nothing older changed).  15: inference -- ssasr_charlm, ssasr_charlm_step, ssasr_infer, ssasr_decode_greedy (nothing
  * older changed).  14 and before: the training entry points below.
  *
@@ -449,6 +449,35 @@ int ssasr_ctc_align(const float* logits, const int32_t* frame_lens, const int32_
                     const int32_t* label_lens, int64_t B, int64_t T, int64_t V, int64_t Lmax, int blank,
                     void* ws, int64_t ws_bytes, int32_t* path, int32_t* first, int32_t* last,
                     float* char_logp, double* score, void* stream);
+
+/* ---- Edit-distance scoring (added under ABI 16) -----------------------------------------------------------------
+ * BUILD-DEFINED: the reference scores on the host (its calc_err).  Character and word error counts of P
+ * (hypothesis, reference) pairs in ONE launch, one workgroup per pair: what CER, WER and an n-best list's oracle
+ * error rate are sums of.
+ *   Sequences: pair p reads hyp[p * hyp_ld + 0 .. min(hyp_lens[p], Hmax)) and, with r = ref_of[p] (p when ref_of is
+ *   NULL, so that K hypotheses can share one row), ref[r * ref_ld + 0 .. min(ref_lens[r], Rmax)); negative lengths
+ *   count as 0.  Every id < first_char is dropped first (with the Mapper first_char = 2: `<`, which is also the pad,
+ *   and `>` go, `$` stays).  Words are the maximal runs of tokens != space (str.split(): no empty words, an empty
+ *   sequence has none); two words are equal when their tokens are.
+ *   Metric: an alignment of the hypothesis against the reference costs (S + D + I, S); the result is the
+ *   lexicographic minimum over all alignments -- fewest edits, among those fewest substitutions:
+ *     cell(i, j) = min(cell(i-1, j-1) + (ne, ne), cell(i-1, j) + (1, 0), cell(i, j-1) + (1, 0))
+ *   with cell(i, 0) = (i, 0), cell(0, j) = (j, 0), i over the hypothesis, j over the reference.  With I - D = H - R
+ *   and S + D + I = dist the counts are unique: no traceback, no dependence on a traversal order, so a host
+ *   restatement (postprocess.edit_ops) is matched exactly.  Reference `ab` against hypothesis `ba` scores S = 0,
+ *   D = 1, I = 1, not S = 2.
+ *   out [P][8] = character S, D, I and the reference's character count, then word S, D, I and the reference's
+ *   word count, all after dropping.
+ * Accepted: 0 <= P <= INT32_MAX (P == 0 launches nothing), 0 <= Rmax <= 1023, 0 <= Hmax <= 8191 (both counted
+ * before dropping), hyp_ld >= Hmax, ref_ld >= Rmax, non-NULL hyp_lens, ref_lens, out, hyp (unless Hmax == 0) and ref
+ * (unless Rmax == 0).  Argument errors return before any HIP call.  ref_of's entries are not checked: the caller
+ * keeps them inside ref's rows.
+ * The block has 64 * ceil((Rmax + 1) / 64) threads, one per reference column; the dynamic LDS holds the kept
+ * tokens, the word boundaries and the word ids (at most 63 KB). */
+int ssasr_edit_score(const int32_t* hyp, int64_t hyp_ld, const int32_t* hyp_lens,
+                     const int32_t* ref, int64_t ref_ld, const int32_t* ref_lens,
+                     const int32_t* ref_of, int64_t P, int64_t Hmax, int64_t Rmax,
+                     int32_t first_char, int32_t space, int32_t* out, void* stream);
 
 /* Solver.step (src/trainer.py:131-148) with torch.optim.Adadelta
  * (src/trainer.py:401-403) on flat buffers of n floats: total L2 norm of

@@ -16,8 +16,8 @@ import random
 import torch
 import torch.nn as nn
 
-from . import ops
-from .preprocess import EOS_TKN, SOS_TKN
+from . import ops, postprocess
+from .preprocess import EOS_TKN, SOS_TKN, TOKENS, UNK_TKN
 
 
 def _dev_i32(values, device):
@@ -37,6 +37,11 @@ ENCODER_STRIDE = 8      # input frames per encoder frame: three pBLSTM layers, e
 # when no alignment fits); chars: [(char, first_frame, last_frame_exclusive, logp)] in input frames (seconds with
 # frame_shift), or None when no alignment fits.
 Alignment = collections.namedtuple('Alignment', ('score', 'chars'))
+
+# ASR.score's result for one utterance (BUILD-DEFINED).  chars, words: (S, D, I, N) of the best hypothesis against
+# the reference, N the reference's count; oracle: (k, chars, words) of the n-best entry with the fewest word errors
+# (ties: fewest character errors, then lowest k), the best entry itself for a greedy decode.
+Score = collections.namedtuple('Score', ('chars', 'words', 'oracle'))
 
 
 def input_span(first, last, n_frames, frame_shift=None):
@@ -283,6 +288,9 @@ class ASR(nn.Module):
         # align's device results: (path [N, T'], first [N, Lmax], last [N, Lmax], char_logp [N, Lmax], score [N] double,
         # logits [N, T', V])
         self.last_align = None
+        # what the most recent decode_many / decode_nbest call left to score(): (chars [N, K, steps] int32,
+        # n_chars [N, K] int32, n_hyps [N] int32), views of last_decode (K = 1) or last_beam
+        self.last_hyps = None
         self.init_parameters()
 
     def init_parameters(self):
@@ -473,6 +481,54 @@ class ASR(nn.Module):
                                             for j, c in enumerate(text)]))
         return out
 
+    def score(self, refs, mapper):
+        """BUILD-DEFINED: edit-distance scores of the hypotheses that the last decode_many / decode_nbest call left on
+        the device (last_hyps) against refs, one per utterance of that call: a row of label ids (list or tensor; pads,
+        `<` and `>` are dropped) or a string.  ONE launch scores every (hypothesis, reference) pair of the group at
+        character and word level (ssasr_edit_score, include/ssasr.h); no transcript is copied to the host to be
+        scored.  Returns one Score(chars=(S, D, I, N), words=(S, D, I, N), oracle=(k, chars, words)) per utterance:
+        chars / words of the best hypothesis, oracle the n-best entry with the fewest word errors (ties: fewest
+        character errors, then lowest k).  Rows past the kernel's limits (a reference of more than 1,023 ids, more
+        than 8,191 decoding steps) are scored by postprocess.edit_counts on the host.  A call before any decode, or
+        with another number of references than that decode had utterances, is a ValueError."""
+        if self.last_hyps is None:
+            raise ValueError('score: nothing decoded yet (decode_many / decode_nbest leave the hypotheses)')
+        chars, n_chars, n_hyps = self.last_hyps
+        N, K, steps = chars.shape
+        if len(refs) != N:
+            raise ValueError('score: %d references for the %d utterances of the last decode' % (len(refs), N))
+        rows = []
+        for ref in refs:
+            if isinstance(ref, str):
+                try:
+                    rows.append([int(mapper.char_to_ind(c)) for c in ref])
+                except (KeyError, ValueError):
+                    raise ValueError('score: %r has a character the mapper does not know' % (ref,)) from None
+            else:
+                rows.append([int(c) for c in (ref.reshape(-1).tolist() if torch.is_tensor(ref) else ref)])
+        space, first_char = int(mapper.char_to_ind(' ')), TOKENS.index(UNK_TKN)
+        rmax = max(len(row) for row in rows) if rows else 0
+        n_hyps_host = n_hyps.cpu().tolist()
+        if rmax <= ops.EDIT_SCORE_MAX_REF and steps <= ops.EDIT_SCORE_MAX_HYP:
+            dev = chars.device
+            ref = torch.zeros(N, max(rmax, 1), dtype=torch.int32)
+            for i, row in enumerate(rows):
+                ref[i, :len(row)] = torch.tensor(row, dtype=torch.int32)
+            ref_of = torch.arange(N, dtype=torch.int32).repeat_interleave(K)
+            out = ops.edit_score(chars.reshape(N * K, steps), n_chars.reshape(N * K), ref.to(dev),
+                                 _dev_i32([len(row) for row in rows], dev), ref_of.to(dev),
+                                 first_char=first_char, space=space).view(N, K, 8).cpu().tolist()
+        else:
+            hyp, lens = chars.cpu().tolist(), n_chars.cpu().tolist()
+            out = [[postprocess.edit_counts(hyp[i][k][:max(lens[i][k], 0)], rows[i], space, first_char)
+                    for k in range(K)] for i in range(N)]
+        scores = []
+        for i in range(N):
+            cand = out[i][:max(min(n_hyps_host[i], K), 1)]
+            k = min(range(len(cand)), key=lambda k: (sum(cand[k][4:7]), sum(cand[k][0:3]), k))
+            scores.append(Score(tuple(cand[0][:4]), tuple(cand[0][4:]), (k, tuple(cand[k][:4]), tuple(cand[k][4:]))))
+        return scores
+
     def decode_many(self, xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1,
                     ctc_weight=0.0, length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None):
         """decode() for a list of single utterances in ONE decode launch.  Each utterance is encoded alone
@@ -498,6 +554,8 @@ class ASR(nn.Module):
                 packed, enc_lens, self._decoder_params(),
                 (self.attention.psi.weight, self.attention.psi.bias), rnn_lm, lm_weight,
                 mapper.char_to_ind(EOS_TKN), max_decoding_steps)
+            self.last_hyps = (self.last_decode[0].unsqueeze(1), self.last_decode[1].unsqueeze(1),
+                              torch.ones_like(self.last_decode[1]))
         chars, n_chars = self.last_decode[0].cpu().tolist(), self.last_decode[1].cpu().tolist()
         return [''.join(mapper.ind_to_char(c) for c in row[:n]) for row, n in zip(chars, n_chars)]
 
@@ -541,6 +599,7 @@ class ASR(nn.Module):
                 self.last_beam, self.last_beam_steps = out[:4], out[4]
             else:
                 self.last_beam = ops.decode_beam(*args) if ctc is None else ops.decode_beam_ctc(*args, ctc)
+            self.last_hyps = (self.last_beam[0], self.last_beam[1], self.last_beam[3])
         chars, n_chars, hyp_scores, n_hyps = [t.cpu().tolist() for t in self.last_beam]
         return [[(''.join(mapper.ind_to_char(c) for c in chars[i][k][:n_chars[i][k]]), hyp_scores[i][k])
                  for k in range(n_hyps[i])] for i in range(len(xs))]

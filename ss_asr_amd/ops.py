@@ -1032,6 +1032,47 @@ def ctc_head_align(feat, weight, bias, frame_lens, y32, label_lens, lmax, blank=
     return ctc_align(logits, frame_lens, y32, label_lens, lmax, blank) + (logits,)
 
 
+EDIT_SCORE_MAX_HYP = 8191      # ssasr_edit_score's limits on a row's tokens, counted before dropping
+EDIT_SCORE_MAX_REF = 1023
+
+
+def edit_score(hyp, hyp_lens, ref, ref_lens, ref_of=None, *, first_char=2, space):
+    """ssasr_edit_score: character and word edit counts of P (hypothesis, reference) pairs in one launch
+    (include/ssasr.h).  hyp [P, Hmax] and ref [rows, Rmax] int32 with unit column stride (rows may be padded: the
+    row stride is passed), hyp_lens [P] and ref_lens [rows] int32; ref_of [P] int32: the ref row of pair p, None:
+    row p.  Ids < first_char are dropped, words split at `space`.  -> int32 [P, 8] on the device: character S, D,
+    I, N, then word S, D, I, N.  Shapes past the kernel's limits raise ValueError (postprocess.edit_counts is the
+    host form)."""
+    lib = _lib.load()
+    _need_gpu(hyp, hyp_lens, ref, ref_lens, ref_of)
+    for name, t in (('hyp', hyp), ('ref', ref)):
+        if (t.dtype != torch.int32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1) or
+                (t.shape[0] > 1 and t.stride(0) < t.shape[1])):
+            raise TypeError('edit_score: %s must be a 2-D int32 matrix with unit column stride and disjoint rows' % name)
+    for name, t in (('hyp_lens', hyp_lens), ('ref_lens', ref_lens), ('ref_of', ref_of)):
+        if t is not None and (t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous()):
+            raise TypeError('edit_score: %s must be a contiguous int32 vector' % name)
+    P, hmax = hyp.shape
+    rows, rmax = ref.shape
+    if hmax > EDIT_SCORE_MAX_HYP or rmax > EDIT_SCORE_MAX_REF:
+        raise ValueError('edit_score: %d hypothesis / %d reference columns exceed the kernel\'s %d / %d'
+                         % (hmax, rmax, EDIT_SCORE_MAX_HYP, EDIT_SCORE_MAX_REF))
+    if hyp_lens.shape[0] != P or ref_lens.shape[0] != rows:
+        raise ValueError('edit_score: one length per row')
+    if ref_of is None:
+        if rows != P:
+            raise ValueError('edit_score: %d hypotheses against %d references need ref_of' % (P, rows))
+    elif ref_of.shape[0] != P or (P and bool(((ref_of < 0) | (ref_of >= rows)).any())):
+        raise ValueError('edit_score: ref_of must name one of the %d reference rows per pair' % rows)
+    out = torch.empty(P, 8, device=hyp.device, dtype=torch.int32)
+    hyp_ld = hyp.stride(0) if P > 1 else max(hmax, 1)
+    ref_ld = ref.stride(0) if rows > 1 else max(rmax, 1)
+    check(lib.ssasr_edit_score(_p(hyp), max(hyp_ld, hmax), _p(hyp_lens), _p(ref), max(ref_ld, rmax), _p(ref_lens),
+                               _p(ref_of), P, hmax, rmax, int(first_char), int(space), _p(out), _stream()),
+          'ssasr_edit_score')
+    return out
+
+
 # ---------------------------------------------------------------------------
 # misc
 # ---------------------------------------------------------------------------

@@ -36,7 +36,7 @@ from .charlm import CharLM
 from .LMDataset import load_lm_dataset
 from .preprocess import SOS_TKN
 from .optim import FusedAdadelta
-from .postprocess import calc_acc, calc_err, draw_att
+from .postprocess import ErrorStats, calc_acc, calc_err, draw_att
 
 
 class Solver:
@@ -531,7 +531,14 @@ class ASRTester(Solver):
     asr.decode_align: true (absent: off; needs 'ctc_weight' in asr.mdl, else set_model raises): after each group is
     decoded its hypotheses are force-aligned to the group's encoder outputs (ASR.align, ssasr_ctc_align); exec()
     still returns the strings, `last_alignments` holds one asr.Alignment per utterance in index order, and
-    `decode_file` gains `_align`."""
+    `decode_file` gains `_align`.
+    asr.decode_score: true (absent: off): each utterance's labels are kept and every decoded group is scored against
+    them in one launch (ASR.score, ssasr_edit_score) after the decode and before the optional align.  exec() still
+    returns the strings and `decode_file` is unchanged (scoring alters no transcript); `last_scores` holds one
+    asr.Score per utterance in index order and `last_error_rates` the corpus-level {'cer', 'wer', 'oracle_cer',
+    'oracle_wer', 'chars': (S, D, I, N), 'words': (S, D, I, N)} (postprocess.ErrorStats: summed errors over summed
+    reference lengths; oracle_*: of each n-best list's entry with the fewest word errors), printed as one verbose
+    line."""
     decode_group = 32
     TERM_KEYS = ('decode_length_bonus', 'decode_coverage_weight', 'decode_coverage_threshold', 'decode_end_margin')
 
@@ -576,6 +583,7 @@ class ASRTester(Solver):
             n_jobs=self.set_if_exists('loader_jobs', 8), use_gpu=self.paras.gpu)
 
     def set_model(self):
+        self.decode_score = bool(self.config['asr'].get('decode_score', False))
         self.decode_align = bool(self.config['asr'].get('decode_align', False))
         if self.decode_align and 'ctc_weight' not in self.config['asr']['mdl']:
             raise ValueError('asr.decode_align needs a model with a ctc_head: set asr.mdl.ctc_weight '
@@ -626,28 +634,44 @@ class ASRTester(Solver):
             ', joint CTC / attention scores, CTC weight {}'.format(ctc_weight) if ctc_weight > 0 else '',
             ''.join(', {} {}'.format(k.replace('_', ' '), v) for k, v in terms.items())))
         self.verbose('Number of utts to decode : {}, {} per launch.'.format(len(self.test_set), self.decode_group))
-        results, xs, x_lens = [], [], []
+        results, xs, x_lens, ys = [], [], [], []
         if self.decode_align:
             self.last_alignments = []
+        if self.decode_score:
+            self.last_scores = []
 
         def flush():
             if xs:
                 texts = self.asr_model.decode_many(xs, x_lens, self.lm, self.mapper, lm_weight,
                                                    beam_size=beam, ctc_weight=ctc_weight, **terms)
                 results.extend(texts)
+                if self.decode_score:            # the hypotheses are still on the device: one launch for the group
+                    self.last_scores.extend(self.asr_model.score(ys, self.mapper))
                 if self.decode_align:            # on the group's encoder outputs: no second encode
                     self.last_alignments.extend(self.asr_model.align(
                         xs, x_lens, texts, self.mapper, encoded=self.asr_model.last_encoded_packed))
-                del xs[:], x_lens[:]
+                del xs[:], x_lens[:], ys[:]
 
         for b_ind, (x, y) in enumerate(self.test_set):
             x, x_len = prepare_x(x, self.device)
             for i in range(x.shape[0]):              # test_batch_size is 1 in the reference's configs
                 xs.append(x[i:i + 1, :x_len[i]])
                 x_lens.append([x_len[i]])
+                if self.decode_score:
+                    ys.append(y.squeeze(0)[i])
             if len(xs) >= self.decode_group:
                 flush()
         flush()
+        if self.decode_score:
+            best, oracle = ErrorStats(), ErrorStats()
+            for sc in self.last_scores:
+                best.add(sc.chars, sc.words)
+                oracle.add(sc.oracle[1], sc.oracle[2])
+            self.last_error_rates = {'cer': best.cer, 'wer': best.wer, 'oracle_cer': oracle.cer,
+                                     'oracle_wer': oracle.wer, 'chars': tuple(best.chars), 'words': tuple(best.words)}
+            self.verbose('CER {:.4f} WER {:.4f} (oracle CER {:.4f} WER {:.4f}); characters S/D/I/N {}/{}/{}/{}, '
+                         'words S/D/I/N {}/{}/{}/{}'.format(best.cer, best.wer, oracle.cer, oracle.wer,
+                                                            *(best.chars + best.words)))
         return results
 
 

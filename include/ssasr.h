@@ -28,7 +28,8 @@
  * ssasr_decode_beam_ctc_ws_bytes, ssasr_decode_beam_ctc; length bonus, coverage term and end detection in the beam
  * search -- ssasr_beam_terms, ssasr_decode_beam_ex_ws_bytes, ssasr_decode_beam_ex; SpecAugment in batch assembly and label smoothing in the
  * masked CE -- ssasr_specaug, ssasr_gather_batch_aug, ssasr_specaug_plan, ssasr_ce_loss_ls_fwd, ssasr_ce_loss_ls_bwd; CTC forced
- * alignment -- ssasr_ctc_align_ws_bytes, ssasr_ctc_align; edit-distance scoring -- ssasr_edit_score.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
+ * alignment -- ssasr_ctc_align_ws_bytes, ssasr_ctc_align; edit-distance scoring -- ssasr_edit_score; MWER training --
+ * ssasr_mwer_ws_bytes, ssasr_mwer_loss_fwd, ssasr_mwer_loss_bwd, ssasr_mwer_pack, ssasr_rows_repeat_fwd, ssasr_rows_repeat_bwd.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
  * (nothing older changed).  15: inference -- ssasr_charlm, ssasr_charlm_step, ssasr_infer, ssasr_decode_greedy (nothing
  * older changed).  14 and before: the training entry points below.
  *
@@ -478,6 +479,69 @@ int ssasr_edit_score(const int32_t* hyp, int64_t hyp_ld, const int32_t* hyp_lens
                      const int32_t* ref, int64_t ref_ld, const int32_t* ref_lens,
                      const int32_t* ref_of, int64_t P, int64_t Hmax, int64_t Rmax,
                      int32_t first_char, int32_t space, int32_t* out, void* stream);
+
+/* ---- MWER training (added under ABI 16) ------------------------------------------------------------------------
+ * BUILD-DEFINED: the reference trains on the masked CE alone.  Minimum word error rate training (Prabhavalkar et al.
+ * 2018) minimises the expected number of errors over an n-best list, interpolated with CE.  The loss works on GROUPS
+ * of teacher-forced rows: logits [R][U][V] with R = G * M, row r = g * M + k being candidate k of group (utterance) g.
+ *   y int32 [R][y_cols], row stride y_ld: labels and masking are ssasr_ce_loss_fwd's -- the label of step t is
+ *   y[r][t + 1], 0 is unlabelled, columns past y_cols read as 0.  An id outside 1 .. V - 1 counts as unlabelled too
+ *   (nothing is read out of bounds).
+ *   n_hyps int32 [G]: the set S_g is the rows k < clamp(n_hyps[g], 0, M).
+ *   counts int32 [R][8]: ssasr_edit_score's out.  unit 0: characters, 1: words; risk_r = S + D + I of that unit.
+ *   ce_w float [R] or NULL (all 0): the ABSOLUTE weight of the row's plain negative log-likelihood; the caller
+ *   folds any 1 / (B denominator) into it.
+ * Definition, every sequence-level quantity in double:
+ *   logP_r  = sum over labelled t of (z[t][lab] - lse_t),  lse_t = (double)max + log(sum exp((double)z - max))
+ *   p_k     = exp(logP_k - LSE_{j in S_g} logP_j) for k in S_g (the maximum is subtracted first: logP values 1e3
+ *             apart give a one-hot p, never a NaN), 0 outside S_g
+ *   Rbar_g  = sum_{k in S_g} p_k risk_k   (an empty S_g: 0)
+ *   loss    = (1 / G) sum_g Rbar_g + sum_r ce_w[r] (-logP_r)   -- summed in a fixed order, no atomics
+ *   _bwd:   dlogits[r][t][v] = dloss w_r (softmax(z[t])_v - [v == lab]) on labelled steps, 0 on unlabelled ones, with
+ *           the row's sequence-level weight w_r = ce_w[r] - (1 / G) p_r (risk_r - Rbar_g); formed in double and
+ *           rounded once.  Nothing is left unwritten.
+ * ws: ssasr_mwer_ws_bytes(G, M, U) bytes, 8-byte aligned, written by _fwd and read by _bwd: doubles logP [R], p [R],
+ * w [R], Rbar [G], then G + 8 R doubles of scratch and the log-sum-exp [R][U] in double (what _bwd normalises by, so
+ * that a step's dlogits sum to zero as closely as float storage allows), then lse [R][U] as float (the correctly
+ * rounded value).  _fwd also writes risk_out float [G] (= Rbar_g) and loss (one float).
+ * Accepted: V > 0, U > 0, 1 <= M <= 33, G * M <= 65535, unit 0 | 1, y_cols >= U + 1, y_ld >= y_cols, ws as above
+ * (ssasr_mwer_ws_bytes returns 0 for sizes outside these).  G == 0 launches nothing; _fwd then writes loss = 0 and
+ * needs neither ws nor the inputs.  Argument errors return before any HIP call.
+ * _fwd: grid (R, 8) x 256 threads, a wave per step, the step's logits held in registers (read once for V <= 256),
+ * then ONE block of 256 threads, a wave per group and a lane per candidate.  _bwd: a wave per (r, t) step. */
+int64_t ssasr_mwer_ws_bytes(int64_t G, int64_t M, int64_t U);
+int ssasr_mwer_loss_fwd(const float* logits, const int32_t* y, int64_t y_ld, int64_t y_cols,
+                        const int32_t* n_hyps, const int32_t* counts, int unit, const float* ce_w,
+                        int64_t G, int64_t M, int64_t U, int64_t V, void* ws, int64_t ws_bytes,
+                        float* risk_out, float* loss, void* stream);
+int ssasr_mwer_loss_bwd(const float* logits, const int32_t* y, int64_t y_ld, int64_t y_cols, int64_t G,
+                        int64_t M, int64_t U, int64_t V, const void* ws, int64_t ws_bytes,
+                        const float* dloss, float* dlogits, void* stream);
+
+/* The teacher / label matrix of an MWER step from device-resident results: ssasr_decode_beam's chars [N][K][steps],
+ * n_chars [N][K] and n_hyps [N], and the batch's label matrix y_ref [N][ref_cols] (row stride ref_ld; <sos> column
+ * first, 0-padded).  rows int32 [N * (K + 1)][L], every element written:
+ *   row (n, k < K), k < clamp(n_hyps[n], 0, K):  0, chars[n][k][0 .. len), eos, 0 ...  with len = clamp(n_chars[n][k],
+ *                                                 0, steps); eos is always appended, as references are formed
+ *   row (n, k < K) from that clamp on:            all 0
+ *   row (n, K):                                   y_ref[n][0 .. ref_cols), then 0
+ * hyp_lens int32 [N * (K + 1)]: len for a hypothesis row (0 for an unused one); for a reference row the count of
+ * non-zero ids minus one, the <eos>.  Column 1 onwards of `rows` with these lengths is what ssasr_edit_score takes
+ * for hypotheses and references alike.
+ * Accepted: N >= 0 (0 launches nothing), 1 <= K <= 32, steps >= 1, ref_ld >= ref_cols >= 0, L >= steps + 2 and
+ * L >= ref_cols.  Argument errors return before any HIP call.  One block of 64 threads per row. */
+int ssasr_mwer_pack(const int32_t* chars, const int32_t* n_chars, const int32_t* n_hyps, const int32_t* y_ref,
+                    int64_t ref_ld, int64_t ref_cols, int64_t N, int64_t K, int64_t steps, int32_t eos, int64_t L,
+                    int32_t* rows, int32_t* hyp_lens, void* stream);
+
+/* Row repeat: one encoder output serves the M rows of its group.  _fwd: dst[g * M + k][0 .. n) = src[g][0 .. n), a
+ * bit copy of 32-bit words (float or int32).  _bwd: dsrc[g][i] = sum_k ddst[g * M + k][i], added in float in the order
+ * k = 0 .. M - 1 by the output's one owner thread: deterministic, no atomics.
+ * Accepted: 0 <= G <= 65535 (0 launches nothing), 1 <= M <= 65535, n > 0, pointers 4-byte aligned.  Argument errors
+ * return before any HIP call.  grid (ceil(n / 1024), G) x 256 threads, four words per thread (128-bit accesses when
+ * n % 4 == 0 and both pointers are 16-byte aligned). */
+int ssasr_rows_repeat_fwd(const void* src, int64_t G, int64_t M, int64_t n, void* dst, void* stream);
+int ssasr_rows_repeat_bwd(const float* ddst, int64_t G, int64_t M, int64_t n, float* dsrc, void* stream);
 
 /* Solver.step (src/trainer.py:131-148) with torch.optim.Adadelta
  * (src/trainer.py:401-403) on flat buffers of n floats: total L2 norm of

@@ -137,6 +137,12 @@ SIGNATURES = {
     'ssasr_ctc_align_ws_bytes': (I64, [I64, I64, I64, I64]),
     'ssasr_ctc_align': (I32, [P, P, P, I64, P, I64, I64, I64, I64, I32, P, I64, P, P, P, P, P, P]),
     'ssasr_edit_score': (I32, [P, I64, P, P, I64, P, P, I64, I64, I64, I32, I32, P, P]),
+    'ssasr_mwer_ws_bytes': (I64, [I64, I64, I64]),
+    'ssasr_mwer_loss_fwd': (I32, [P, P, I64, I64, P, P, I32, P, I64, I64, I64, I64, P, I64, P, P, P]),
+    'ssasr_mwer_loss_bwd': (I32, [P, P, I64, I64, I64, I64, I64, I64, P, I64, P, P, P]),
+    'ssasr_mwer_pack': (I32, [P, P, P, P, I64, I64, I64, I64, I64, I32, I64, P, P, P]),
+    'ssasr_rows_repeat_fwd': (I32, [P, I64, I64, I64, P, P]),
+    'ssasr_rows_repeat_bwd': (I32, [P, I64, I64, I64, P, P]),
     'ssasr_clip_adadelta_ws': (I64, [I64]),
     'ssasr_clip_adadelta': (I32, [P, P, P, P, I64, F32, F32, F32, F32, F32, P, P, I32, P]),
     'ssasr_adam_ws': (I64, [I64]),

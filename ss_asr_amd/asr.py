@@ -316,6 +316,31 @@ class ASR(nn.Module):
                     embed=self.embed.weight, w_ct=self.char_trans.weight,
                     b_ct=self.char_trans.bias)
 
+    def encode(self, audio_feature, state_len, decode_step=None, modes=()):
+        """The Listener on a batch, the half of forward() before the decode loop (src/asr.py:60-66), for callers
+        that run the loop themselves (engine.MWERTrainStep encodes ONCE and decodes K + 1 rows per utterance).
+        decode_step: the loop length whose exchange workspaces are reserved beside the encoder's, None for no
+        reservation; modes: per-step integers uploaded with the lengths.
+        Returns (features [B, T', E], encode_len list, the same as an int32 device tensor, the decode loop's
+        `slots` or None, modes on the device or None)."""
+        dev = audio_feature.device
+        # every per-step integer the device needs, in one upload
+        lens = Listener.layer_lengths(state_len)
+        l1, l2, l3, enc_len_dev, modes_dev = ops.upload_i32(dev, lens[0], lens[1], lens[2], lens[3], modes)
+        # exchange workspaces of the whole pass: two allocations, each armed by one fill
+        arenas = (ops.ExchangeArena(dev), ops.ExchangeArena(dev))
+        dec_slots = None
+        if decode_step is not None:
+            dec_slots = ops.decoder_reserve(arenas[0], arenas[1], audio_feature.shape[0], lens[3][0], decode_step,
+                                            A=self.attention.phi.weight.shape[0], E=self.encoder.out_dim,
+                                            D=self.decoder.state_size, V=self.char_trans.weight.shape[0])
+        encode_feature, encode_len = self.encoder(audio_feature, state_len, len_devs=(l1, l2, l3), arenas=arenas)
+        # what a second head on the encoder (ss_asr_amd/ctc.py) reads: output and its int32 frame counts
+        self.last_encoded = (encode_feature, enc_len_dev)
+        self.decoder.init_rnn(encode_feature.shape[0], dev)
+        self.attention.reset_enc_mem()
+        return encode_feature, encode_len, enc_len_dev, dec_slots, modes_dev if len(modes) else None
+
     def forward(self, audio_feature, decode_step, teacher=None, state_len=None):
         """Returns (encode_len: list[int], logits [B,U,V] on the device,
         attention [B,U,T'] on the host, detached) -- src/asr.py:52-110."""
@@ -327,19 +352,8 @@ class ASR(nn.Module):
         else:
             modes = [2] * decode_step
             teacher_i32 = None
-        # every per-step integer the device needs, in one upload
-        lens = Listener.layer_lengths(state_len)
-        l1, l2, l3, enc_len_dev, modes_dev = ops.upload_i32(dev, lens[0], lens[1], lens[2], lens[3], modes)
-        # exchange workspaces of the whole pass: two allocations, each armed by one fill
-        arenas = (ops.ExchangeArena(dev), ops.ExchangeArena(dev))
-        dec_slots = ops.decoder_reserve(arenas[0], arenas[1], audio_feature.shape[0], lens[3][0], decode_step,
-                                        A=self.attention.phi.weight.shape[0], E=self.encoder.out_dim,
-                                        D=self.decoder.state_size, V=self.char_trans.weight.shape[0])
-        encode_feature, encode_len = self.encoder(audio_feature, state_len, len_devs=(l1, l2, l3), arenas=arenas)
-        # what a second head on the encoder (ss_asr_amd/ctc.py) reads: output and its int32 frame counts
-        self.last_encoded = (encode_feature, enc_len_dev)
-        self.decoder.init_rnn(encode_feature.shape[0], dev)
-        self.attention.reset_enc_mem()
+        encode_feature, encode_len, enc_len_dev, dec_slots, modes_dev = self.encode(audio_feature, state_len,
+                                                                                    decode_step, modes)
         uniforms = None
         if 1 in modes:
             # Categorical(...).sample() of the reference (src/asr.py:97): one

@@ -100,6 +100,137 @@ class ASRTrainStep:
         return self.last_done
 
 
+class MWERTrainStep:
+    """BUILD-DEFINED (the reference trains on the masked CE alone): one step of minimum word error rate training
+    (Prabhavalkar et al. 2018), the second stage of an attention model -- the expected number of word (or
+    character) errors over an n-best list, plus ce_weight times the masked CE of the reference transcript.
+    Optimizer, gradient reduction, status row, poll / finish contract and NaN-skip accounting are ASRTrainStep's.
+
+    forward_loss: the Listener runs ONCE on the batch (blstm_4 recurs over the utterance axis, so a batch of
+    repeated utterances would be encoded differently); a beam search without grad on those very features gives K
+    hypotheses per utterance; ssasr_mwer_pack lays them and the reference out as M = K + 1 teacher / label rows per
+    utterance, ssasr_edit_score counts every row's errors against its reference; the features are repeated M
+    times (ops.rows_repeat) and the decode loop runs teacher-forced over all B * M rows (every step in mode 0,
+    whatever model.tf_rate is); ops.mwer_loss weighs the rows.  The reference row is teacher-forced for the CE term
+    only: it is not a member of the hypothesis set.  Nothing of the n-best list goes to the host but one integer, the
+    longest row's length.
+
+    B * (K + 1) > 32 rows are outside the persistent decode loop's shapes (include/ssasr.h: B <= 32) and take one
+    launch per stage and step: slower per row, the same results.  A ctc.JointCTCASR model may be trained, but its
+    CTC branch takes no part in this step (the head gets no gradient)."""
+
+    UNITS = {'char': 0, 'word': 1}
+
+    def __init__(self, model, beam_size, ce_weight=0.01, unit='word', lm=None, lm_weight=0.0, max_decoding_steps=200,
+                 lr=1.0, eps=1e-8, rho=0.9, grad_clip=5.0, eos=None, space=None):
+        """beam_size 1 .. 32 (K); ce_weight >= 0; unit 'word' | 'char': whose errors are the risk; lm, lm_weight: a
+        charlm.CharLM fused into the SEARCH only (the loss is the model's own likelihood); max_decoding_steps: the
+        search's step limit.  eos / space: the Mapper's ids of `>` and ` ` (its fixed alphabet's by default)."""
+        from .asr import EOS_INDEX
+        from .preprocess import ALL_CHARS, TOKENS, UNK_TKN
+        beam_size = int(beam_size)
+        if not 1 <= beam_size <= ops.MAX_BEAM:
+            raise ValueError('beam_size must be in 1..%d, got %d' % (ops.MAX_BEAM, beam_size))
+        if unit not in self.UNITS:
+            raise ValueError("unit must be 'word' or 'char', got %r" % (unit,))
+        if not float(ce_weight) >= 0.0:
+            raise ValueError('ce_weight must be >= 0, got %r' % (ce_weight,))
+        if int(max_decoding_steps) < 1:
+            raise ValueError('max_decoding_steps must be >= 1, got %r' % (max_decoding_steps,))
+        if not next(model.parameters()).is_cuda:
+            raise RuntimeError('MWERTrainStep needs the model on the GPU (no CPU path)')
+        self.model, self.beam_size, self.ce_weight, self.unit = model, beam_size, float(ce_weight), unit
+        self.lm, self.lm_weight, self.max_decoding_steps = lm, float(lm_weight), int(max_decoding_steps)
+        self.eos = EOS_INDEX if eos is None else int(eos)
+        self.space = (TOKENS + ALL_CHARS).index(' ') if space is None else int(space)
+        self.first_char = TOKENS.index(UNK_TKN)             # `<` (the pad) and `>` are dropped before scoring
+        self.flat = FlatParameters.of(model)
+        sdist.broadcast_flat(self.flat.data)
+        self.optim = FusedAdadelta(self.flat, lr=lr, rho=rho, eps=eps)
+        self.grad_clip = grad_clip
+        self.reducer = sdist.GradReducer(self.flat, list(model.encoder.blstm_1.parameters()))
+        ops.set_wgrad_listener(self.reducer.wgrad_enqueued)
+        self._one = torch.ones((), device=self.flat.data.device)
+        self._ref_of = {}
+        self.last_logits = None        # [B * (K + 1), U, V] of the most recent step
+        self.last_rows = None          # int32 [B * (K + 1), L]: its teacher / label rows
+        self.last_hyps = None          # (chars [B, K, steps], n_chars [B, K], n_hyps [B]) it was given or searched
+        self.last_counts = None        # int32 [B * (K + 1), 8]: every row's edit counts against its reference
+        self.last_risk = None          # float [B]: the expected risk per utterance, on the device
+        self.last_info = None          # ops.MWERInfo of its loss (p_hat, logp, weight, lse)
+        self.last_done = None
+        self.skipped_steps = 0
+
+    def search(self, feat, enc_len_dev):
+        """The n-best list of this batch's own features, without grad: (chars, n_chars, n_hyps) on the device."""
+        m = self.model
+        with torch.no_grad():
+            chars, n_chars, _, n_hyps = ops.decode_beam(
+                feat.detach(), enc_len_dev, m._decoder_params(), (m.attention.psi.weight, m.attention.psi.bias),
+                self.lm, self.lm_weight, self.eos, self.max_decoding_steps, self.beam_size)
+        return chars, n_chars, n_hyps
+
+    def _reference_rows(self, B, M, dev):
+        """ref_of of the scoring launch: every row of utterance b is scored against row b * M + K."""
+        key = (B, M, str(dev))
+        if key not in self._ref_of:
+            self._ref_of[key] = ((torch.arange(B * M, dtype=torch.int32) // M) * M + (M - 1)).to(dev)
+        return self._ref_of[key]
+
+    def forward_loss(self, x, y, x_lens, hyps=None):
+        """x [B, T, F], y [B, L] label rows (<sos> column first, 0-padded), x_lens host list (descending).
+        hyps: (chars [B, K, steps], n_chars [B, K], n_hyps [B]) int32 device tensors used instead of the search
+        (tests, reproducible runs).  Returns (loss, logits [B * (K + 1), U, V])."""
+        m = self.model
+        feat, _, enc_len_dev, _, _ = m.encode(x, x_lens)                       # 1. encode once, with grad
+        if hyps is None:
+            hyps = self.search(feat, enc_len_dev)                              # 2. search on these features
+        chars, n_chars, n_hyps = [t.to(torch.int32).contiguous() for t in hyps]
+        B, K = chars.shape[0], chars.shape[1]
+        if B != x.shape[0] or K > ops.MAX_BEAM:
+            raise ValueError('MWERTrainStep: hypotheses [%d, %d, ...] for a batch of %d (at most %d per utterance)'
+                             % (B, K, x.shape[0], ops.MAX_BEAM))
+        M = K + 1
+        y32 = ops.as_i32(y)
+        rows, hyp_lens = ops.mwer_pack(chars, n_chars, n_hyps, y32, self.eos)  # 3. pack and score
+        counts = ops.edit_score(rows[:, 1:], hyp_lens, rows[:, 1:max(y32.shape[1], 2)], hyp_lens,
+                                self._reference_rows(B, M, rows.device), first_char=self.first_char,
+                                space=self.space, check_ref_of=False)
+        # 4. the teacher-forced pass over B * M rows; its length is the one integer the host reads
+        U = int(hyp_lens.max()) + 1
+        logits, _, _ = ops.decoder_loop(ops.rows_repeat(feat, M), None, ops.rows_repeat(enc_len_dev, M), rows,
+                                        [0] * U, None, m._decoder_params(),
+                                        psi=(m.attention.psi.weight, m.attention.psi.bias))
+        # 5. the reference rows carry the CE: ce_weight / (B denom_b), denom_b = count(y[b] != 0) as in the masked CE
+        ce_w = torch.zeros(B, M, device=rows.device, dtype=torch.float32)
+        ce_w[:, K] = self.ce_weight / (B * (hyp_lens.view(B, M)[:, K] + 1).clamp(min=1).to(torch.float32))
+        loss, info = ops.mwer_loss(logits, rows, n_hyps, counts, self.UNITS[self.unit], ce_w.view(B * M))
+        self.last_rows, self.last_hyps, self.last_counts = rows, (chars, n_chars, n_hyps), counts
+        self.last_risk, self.last_info, self.last_logits = info.risk, info, logits
+        return loss, logits
+
+    def __call__(self, x, y, x_lens, hyps=None):
+        """One train step; returns the loss tensor (on the device).  The previous step's verdict is picked up
+        here without a synchronisation, as in ASRTrainStep."""
+        self._note(self.optim.poll())
+        ops.set_wgrad_listener(self.reducer.wgrad_enqueued)
+        if not self.flat.clean:
+            self.optim.zero_grad()
+        self.flat.clean = False
+        self.reducer.begin()
+        with ops.shared_status_row(self.optim.status_row):
+            loss, _ = self.forward_loss(x, y, x_lens, hyps)
+            loss.backward(self._one)
+        scale = self.reducer.finish()
+        self.optim.clip_and_step(self.grad_clip, grad_scale=scale, zero_grad=True)
+        self.flat.clean = True
+        settle_collector()
+        return loss
+
+    _note = ASRTrainStep._note
+    finish = ASRTrainStep.finish
+
+
 class TAETrainStep:
     """One TAETrainer step (the body of TAETrainer.exec, src/trainer.py:652-677) as a reusable object: the
     text autoencoder's forward through the shared attend-and-spell loop (text_autoencoder.py), the loss of

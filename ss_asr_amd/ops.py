@@ -1036,13 +1036,14 @@ EDIT_SCORE_MAX_HYP = 8191      # ssasr_edit_score's limits on a row's tokens, co
 EDIT_SCORE_MAX_REF = 1023
 
 
-def edit_score(hyp, hyp_lens, ref, ref_lens, ref_of=None, *, first_char=2, space):
+def edit_score(hyp, hyp_lens, ref, ref_lens, ref_of=None, *, first_char=2, space, check_ref_of=True):
     """ssasr_edit_score: character and word edit counts of P (hypothesis, reference) pairs in one launch
     (include/ssasr.h).  hyp [P, Hmax] and ref [rows, Rmax] int32 with unit column stride (rows may be padded: the
     row stride is passed), hyp_lens [P] and ref_lens [rows] int32; ref_of [P] int32: the ref row of pair p, None:
     row p.  Ids < first_char are dropped, words split at `space`.  -> int32 [P, 8] on the device: character S, D,
     I, N, then word S, D, I, N.  Shapes past the kernel's limits raise ValueError (postprocess.edit_counts is the
-    host form)."""
+    host form).  check_ref_of False: ref_of's entries are the caller's own arithmetic and are not read back to be
+    range-checked (that check synchronises the device; a train step cannot afford it)."""
     lib = _lib.load()
     _need_gpu(hyp, hyp_lens, ref, ref_lens, ref_of)
     for name, t in (('hyp', hyp), ('ref', ref)):
@@ -1062,7 +1063,7 @@ def edit_score(hyp, hyp_lens, ref, ref_lens, ref_of=None, *, first_char=2, space
     if ref_of is None:
         if rows != P:
             raise ValueError('edit_score: %d hypotheses against %d references need ref_of' % (P, rows))
-    elif ref_of.shape[0] != P or (P and bool(((ref_of < 0) | (ref_of >= rows)).any())):
+    elif ref_of.shape[0] != P or (P and check_ref_of and bool(((ref_of < 0) | (ref_of >= rows)).any())):
         raise ValueError('edit_score: ref_of must name one of the %d reference rows per pair' % rows)
     out = torch.empty(P, 8, device=hyp.device, dtype=torch.int32)
     hyp_ld = hyp.stride(0) if P > 1 else max(hmax, 1)
@@ -1071,6 +1072,152 @@ def edit_score(hyp, hyp_lens, ref, ref_lens, ref_of=None, *, first_char=2, space
                                _p(ref_of), P, hmax, rmax, int(first_char), int(space), _p(out), _stream()),
           'ssasr_edit_score')
     return out
+
+
+# ---------------------------------------------------------------------------
+# MWER training (build-defined; include/ssasr.h, "MWER training")
+# ---------------------------------------------------------------------------
+MWER_MAX_ROWS = 33             # ssasr_mwer_loss_fwd's limit on the rows of a group
+
+
+class MWERInfo:
+    """What ssasr_mwer_loss_fwd left on the device beside the loss: risk [G] float (the expected risk per group),
+    p_hat [R], logp [R] and weight [R] double (views of the workspace: the set's posterior, the rows'
+    log-probabilities and their sequence-level weights), lse [R, U] float."""
+    __slots__ = ('risk', 'p_hat', 'logp', 'weight', 'lse', 'ws')
+
+
+class _MWERLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, rows, n_hyps, counts, unit, ce_w, info):
+        lib = _lib.load()
+        R, U, V = logits.shape
+        G = n_hyps.shape[0]
+        M = R // G if G else 1
+        dev = logits.device
+        need = int(lib.ssasr_mwer_ws_bytes(G, M, U))
+        if G and need <= 0:
+            raise ValueError('mwer_loss: no kernel for %d groups of %d rows, %d steps (1 <= rows <= %d, '
+                             'groups * rows <= 65535)' % (G, M, U, MWER_MAX_ROWS))
+        ws = torch.empty(max(need // 8, 1), device=dev, dtype=torch.float64)
+        risk = torch.empty(G, device=dev, dtype=torch.float32)
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        check(lib.ssasr_mwer_loss_fwd(_p(logits), _p(rows), rows.stride(0), rows.shape[1], _p(n_hyps), _p(counts),
+                                      unit, _p(ce_w), G, M, U, V, _p(ws), need, _p(risk), _p(loss), _stream()),
+              'ssasr_mwer_loss_fwd')
+        info.ws, info.risk = ws, risk
+        info.logp, info.p_hat, info.weight = ws[:R], ws[R:2 * R], ws[2 * R:3 * R]
+        info.lse = ws[3 * R + 2 * G + 8 * R + R * U:].view(torch.float32)[:R * U].view(R, U)
+        ctx.save_for_backward(logits, rows, ws)
+        ctx.geom = (G, M, need)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        lib = _lib.load()
+        logits, rows, ws = ctx.saved_tensors
+        G, M, need = ctx.geom
+        R, U, V = logits.shape
+        dloss = dloss.to(torch.float32).contiguous()
+        dlogits = torch.empty_like(logits)
+        check(lib.ssasr_mwer_loss_bwd(_p(logits), _p(rows), rows.stride(0), rows.shape[1], G, M, U, V, _p(ws), need,
+                                      _p(dloss), _p(dlogits), _stream()), 'ssasr_mwer_loss_bwd')
+        return dlogits, None, None, None, None, None, None
+
+
+def mwer_loss(logits, rows, n_hyps, counts, unit, ce_w=None):
+    """The MWER loss of include/ssasr.h (ssasr_mwer_loss_fwd / _bwd; postprocess.mwer_reference is its float64
+    restatement).  logits [R, U, V] float32 of R = G * M teacher-forced rows, row g * M + k being candidate k of
+    group g; rows int32 [R, >= U + 1], the rows' label matrix (the label of step t is rows[r, t + 1], 0 unlabelled);
+    n_hyps int32 [G]: the first clamp(n_hyps[g], 0, M) rows of a group are its hypothesis set; counts int32 [R, 8]:
+    edit_score's result; unit 'char' | 'word' (or 0 | 1); ce_w float32 [R] or None: absolute weights of the rows'
+    negative log-likelihoods.  -> (loss, MWERInfo): the loss tensor carries the graph, the info is for logging."""
+    _need_gpu(logits, rows, n_hyps, counts, ce_w)
+    unit = {'char': 0, 'word': 1}.get(unit, unit)
+    if unit not in (0, 1):
+        raise ValueError("mwer_loss: unit must be 'char' or 'word', got %r" % (unit,))
+    logits = _f32c(logits)
+    if logits.dim() != 3:
+        raise ValueError('mwer_loss: logits must be [rows, steps, classes]')
+    R, U, V = logits.shape
+    if rows.dtype != torch.int32 or rows.dim() != 2 or rows.stride(1) != 1 or rows.shape[0] != R or rows.shape[1] < U + 1:
+        raise TypeError('mwer_loss: rows must be int32 [%d, >= %d] with unit column stride' % (R, U + 1))
+    for name, t, shape in (('n_hyps', n_hyps, None), ('counts', counts, (R, 8))):
+        if t.dtype != torch.int32 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
+            raise TypeError('mwer_loss: %s must be a contiguous int32 tensor%s' % (name, '' if shape is None else ' of shape %r' % (shape,)))
+    G = n_hyps.shape[0]
+    if n_hyps.dim() != 1 or (G == 0) != (R == 0) or (G and R % G):
+        raise ValueError('mwer_loss: %d rows do not form %d equal groups' % (R, G))
+    if ce_w is not None:
+        ce_w = _f32c(ce_w)
+        if tuple(ce_w.shape) != (R,):
+            raise ValueError('mwer_loss: ce_w must hold one weight per row')
+    info = MWERInfo()
+    return _MWERLoss.apply(logits, rows, n_hyps, counts, unit, ce_w, info), info
+
+
+def mwer_pack(chars, n_chars, n_hyps, y_ref, eos, L=None):
+    """ssasr_mwer_pack: an n-best list (decode_beam's chars [N, K, steps], n_chars [N, K], n_hyps [N], int32) and the
+    batch's label matrix y_ref [N, ref_cols] (int32, <sos> column first, 0-padded) -> (rows int32 [N * (K + 1), L],
+    hyp_lens int32 [N * (K + 1)]): per utterance its K hypothesis rows `0, chars, eos, 0 ...` (all 0 from n_hyps on)
+    and then its reference row; hyp_lens is what edit_score needs for rows[:, 1:] (include/ssasr.h).
+    L: the row length, by default max(steps + 2, ref_cols), its minimum."""
+    lib = _lib.load()
+    _need_gpu(chars, n_chars, n_hyps, y_ref)
+    for name, t in (('chars', chars), ('n_chars', n_chars), ('n_hyps', n_hyps)):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise TypeError('mwer_pack: %s must be a contiguous int32 tensor' % name)
+    if y_ref.dtype != torch.int32 or y_ref.dim() != 2 or (y_ref.shape[1] > 1 and y_ref.stride(1) != 1):
+        raise TypeError('mwer_pack: y_ref must be an int32 matrix with unit column stride')
+    N, K, steps = chars.shape
+    if tuple(n_chars.shape) != (N, K) or tuple(n_hyps.shape) != (N,) or y_ref.shape[0] != N:
+        raise ValueError('mwer_pack: chars [N, K, steps], n_chars [N, K], n_hyps [N] and y_ref [N, cols] disagree')
+    ref_cols = y_ref.shape[1]
+    if L is None:
+        L = max(steps + 2, ref_cols)
+    rows = torch.empty(N * (K + 1), L, device=chars.device, dtype=torch.int32)
+    hyp_lens = torch.empty(N * (K + 1), device=chars.device, dtype=torch.int32)
+    ref_ld = y_ref.stride(0) if N > 1 else max(ref_cols, 1)
+    check(lib.ssasr_mwer_pack(_p(chars), _p(n_chars), _p(n_hyps), _p(y_ref), max(ref_ld, ref_cols), ref_cols, N, K,
+                              steps, int(eos), L, _p(rows), _p(hyp_lens), _stream()), 'ssasr_mwer_pack')
+    return rows, hyp_lens
+
+
+class _RowsRepeat(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t, M):
+        lib = _lib.load()
+        G = t.shape[0]
+        n = t[0].numel() if G else 1
+        out = torch.empty((G * M,) + tuple(t.shape[1:]), device=t.device, dtype=t.dtype)
+        check(lib.ssasr_rows_repeat_fwd(_p(t), G, M, n, _p(out), _stream()), 'ssasr_rows_repeat_fwd')
+        ctx.geom = (G, M, n)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = _lib.load()
+        G, M, n = ctx.geom
+        dout = _f32c(dout)
+        dt = torch.empty((G,) + tuple(dout.shape[1:]), device=dout.device, dtype=torch.float32)
+        check(lib.ssasr_rows_repeat_bwd(_p(dout), G, M, n, _p(dt), _stream()), 'ssasr_rows_repeat_bwd')
+        return dt, None
+
+
+def rows_repeat(t, M):
+    """torch.repeat_interleave(t, M, dim=0) for a float32 or int32 tensor [G, ...] (ssasr_rows_repeat_fwd: a bit
+    copy); the backward of a float32 tensor adds each group's M rows in row order (ssasr_rows_repeat_bwd:
+    deterministic, no atomics)."""
+    _need_gpu(t)
+    if t.dtype not in (torch.float32, torch.int32) or t.dim() < 1:
+        raise TypeError('rows_repeat: a float32 or int32 tensor with a row axis, got %s' % t.dtype)
+    M = int(M)
+    if M < 1:
+        raise ValueError('rows_repeat: M must be >= 1, got %d' % M)
+    t = t if t.is_contiguous() else t.contiguous()
+    if t.dtype == torch.int32:
+        return _RowsRepeat.apply(t.detach(), M)
+    return _RowsRepeat.apply(t, M)
 
 
 # ---------------------------------------------------------------------------

@@ -2,6 +2,8 @@
 accuracy, word-level edit-distance error, attention images, EOS trimming.
 The reference uses the `editdistance` package; a small Levenshtein routine
 replaces it here."""
+import math
+
 import numpy as np
 import torch
 
@@ -71,6 +73,42 @@ def edit_counts(hyp_ids, ref_ids, space, first_char=2):
     hc, hw = score_sequences(hyp_ids, space, first_char)
     rc, rw = score_sequences(ref_ids, space, first_char)
     return list(edit_ops(hc, rc)) + [len(rc)] + list(edit_ops(hw, rw)) + [len(rw)]
+
+
+def mwer_reference(logits, rows, n_hyps, counts, unit, ce_w=None):
+    """BUILD-DEFINED: the MWER loss of ssasr_mwer_loss_fwd (include/ssasr.h) restated in float64 torch, on any
+    device, differentiable by autograd -- what the kernel is defined and tested against.
+    logits [R, U, V] of R = G * M teacher-forced rows (row g * M + k: candidate k of group g); rows [R, >= U + 1]
+    integer labels (the label of step t is rows[r, t + 1], 0 unlabelled); n_hyps [G]: the hypothesis set of group g
+    is its first clamp(n_hyps[g], 0, M) rows; counts [R, 8]: ssasr_edit_score's rows; unit 0 | 'char' or 1 | 'word';
+    ce_w [R] or None: absolute weights of the rows' negative log-likelihoods.
+      logP_r = sum over labelled t of log_softmax(logits[r, t])[label];  p_hat = softmax of logP over the set;
+      risk_g = sum_k p_hat_k (S + D + I)_k;  loss = mean_g risk_g + sum_r ce_w[r] (-logP_r).
+    -> (loss, risk [G], p_hat [R] with 0 outside the sets), all float64."""
+    unit = {'char': 0, 'word': 1}.get(unit, unit)
+    if unit not in (0, 1):
+        raise ValueError("mwer_reference: unit must be 'char' or 'word', got %r" % (unit,))
+    z = logits.to(torch.float64)
+    R, U, V = z.shape
+    G = int(n_hyps.shape[0])
+    M = R // G if G else 1
+    lab = torch.zeros(R, U, dtype=torch.long, device=z.device)
+    have = min(U, rows.shape[1] - 1)
+    lab[:, :have] = rows[:, 1:1 + have].to(torch.long)
+    if bool(((lab < 0) | (lab >= V)).any()):
+        raise ValueError('mwer_reference: a label names no class')
+    logp = (torch.log_softmax(z, -1).gather(2, lab.unsqueeze(2)).squeeze(2) * (lab != 0)).sum(1)
+    err = counts.to(torch.float64)[:, 4 * unit:4 * unit + 3].sum(1).view(G, M)
+    inside = torch.arange(M, device=z.device).unsqueeze(0) < n_hyps.to(torch.long).clamp(0, M).unsqueeze(1)
+    # an empty set is left unmasked (a row of -inf would put NaNs into the graph) and zeroed with the rest below
+    masked = ~inside & inside.any(1, keepdim=True)
+    p_hat = torch.softmax(logp.view(G, M).masked_fill(masked, -math.inf), 1)
+    p_hat = torch.where(inside, p_hat, torch.zeros_like(p_hat))
+    risk = (p_hat * err).sum(1)
+    loss = risk.sum() / max(G, 1)
+    if ce_w is not None:
+        loss = loss - (ce_w.to(torch.float64) * logp).sum()
+    return loss, risk, p_hat.reshape(R)
 
 
 class ErrorStats:

@@ -34,7 +34,7 @@ from .TrackerHandler import TrackerHandler
 from .asr import ASR
 from .charlm import CharLM
 from .LMDataset import load_lm_dataset
-from .preprocess import SOS_TKN
+from .preprocess import EOS_TKN, SOS_TKN
 from .optim import FusedAdadelta
 from .postprocess import ErrorStats, calc_acc, calc_err, draw_att
 
@@ -257,8 +257,47 @@ class ASRTrainer(Solver):
     asr.spec_augment: {freq_masks, freq_width, time_masks, time_width, time_ratio, fill, seed}: SpecAugment
     masks (at most 8 of a kind; widths drawn from 0 .. *_width, time masks no wider than time_ratio of the
     utterance) applied by the resident loader's batch assembly (GpuResidentLoader, ssasr_gather_batch_aug),
-    redrawn every epoch; it needs that loader and raises where it is not in use."""
+    redrawn every epoch; it needs that loader and raises where it is not in use.
+    asr.mwer: {beam_size, ce_weight, unit, max_decoding_steps}: minimum word error rate training
+    (engine.MWERTrainStep) instead of the CE step: the expected number of `unit` (word | char) errors over a beam of
+    2 .. 32 hypotheses searched on the training batch, plus ce_weight (>= 0) times the masked CE.  `train_loss` is
+    then that loss and `mwer_risk`, the mean expected errors per utterance, is logged beside it.  It needs the fused
+    step (Adadelta on the GPU) and is not defined together with asr.label_smoothing.  With a ctc_weight model the CTC
+    branch takes no part in the step."""
     SPEC_AUGMENT_KEYS = ('freq_masks', 'freq_width', 'time_masks', 'time_width', 'time_ratio', 'fill', 'seed')
+    MWER_KEYS = ('beam_size', 'ce_weight', 'unit', 'max_decoding_steps')
+
+    @classmethod
+    def mwer_options(cls, asr_config):
+        """engine.MWERTrainStep's keywords of asr_config's `mwer` mapping, validated; None when it is absent."""
+        import math
+        conf = asr_config.get('mwer')
+        if conf is None:
+            return None
+        if not isinstance(conf, dict):
+            raise ValueError('asr.mwer must be a mapping of {}, got {!r}'.format(cls.MWER_KEYS, conf))
+        unknown = sorted(set(conf) - set(cls.MWER_KEYS))
+        if unknown:
+            raise ValueError('asr.mwer: unknown keys {} (known: {})'.format(unknown, cls.MWER_KEYS))
+        if asr_config.get('label_smoothing'):
+            raise ValueError('asr.label_smoothing and asr.mwer are not defined together: drop one of them')
+
+        def integer(key, v, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+                raise ValueError('asr.mwer.{} must be an integer in {} .. {}, got {!r}'.format(key, lo, hi, v))
+            return v
+
+        if 'beam_size' not in conf:
+            raise ValueError('asr.mwer.beam_size is required (an integer in 2 .. 32)')
+        ce_weight = conf.get('ce_weight', 0.01)
+        if (isinstance(ce_weight, bool) or not isinstance(ce_weight, (int, float)) or not math.isfinite(ce_weight)
+                or ce_weight < 0):
+            raise ValueError('asr.mwer.ce_weight must be a finite number >= 0, got {!r}'.format(ce_weight))
+        unit = conf.get('unit', 'word')
+        if unit not in ('word', 'char'):
+            raise ValueError("asr.mwer.unit must be 'word' or 'char', got {!r}".format(unit))
+        return dict(beam_size=integer('beam_size', conf['beam_size'], 2, 32), ce_weight=float(ce_weight), unit=unit,
+                    max_decoding_steps=integer('max_decoding_steps', conf.get('max_decoding_steps', 200), 1, 8189))
 
     @classmethod
     def regularisers(cls, asr_config):
@@ -303,6 +342,7 @@ class ASRTrainer(Solver):
     def __init__(self, config, paras):
         super().__init__(config, paras, 'asr')
         self.label_smoothing, self.spec_augment = self.regularisers(self.config['asr'])
+        self.mwer = self.mwer_options(self.config['asr'])
 
     def load_data(self):
         """Index files must be sorted so that every batch is in decreasing
@@ -367,11 +407,18 @@ class ASRTrainer(Solver):
         self.train_step = None
         if opt['type'] == 'Adadelta' and self.device.type == 'cuda':
             # the fused step (engine.ASRTrainStep): what bench.py times is what trains
-            from .engine import ASRTrainStep
-            step_cls = JointCTCTrainStep if joint else ASRTrainStep
-            self.train_step = step_cls(self.asr_model, lr=opt['learning_rate'], eps=1e-8, grad_clip=5.0,
-                                       label_smoothing=self.label_smoothing)
+            from .engine import ASRTrainStep, MWERTrainStep
+            if self.mwer is not None:
+                self.train_step = MWERTrainStep(self.asr_model, lr=opt['learning_rate'], eps=1e-8, grad_clip=5.0,
+                                                eos=self.mapper.char_to_ind(EOS_TKN),
+                                                space=self.mapper.char_to_ind(' '), **self.mwer)
+            else:
+                step_cls = JointCTCTrainStep if joint else ASRTrainStep
+                self.train_step = step_cls(self.asr_model, lr=opt['learning_rate'], eps=1e-8, grad_clip=5.0,
+                                           label_smoothing=self.label_smoothing)
             self.flat, self.optim = self.train_step.flat, self.train_step.optim
+        elif self.mwer is not None:
+            raise RuntimeError('asr.mwer runs on the fused step only (Adadelta on the GPU)')
         elif joint:
             raise RuntimeError('the joint CTC+attention loss runs on the fused step only (Adadelta on the GPU)')
         else:
@@ -399,8 +446,14 @@ class ASRTrainer(Solver):
                 if self.train_step is not None:
                     # src/trainer.py:419-438 as one fused step; a persistent launch that timed out
                     # in the previous step raises here (its status words arrive with the optimizer's)
-                    loss = self.train_step(x, y, state_len, ans_len)
-                    prediction = self.train_step.last_logits
+                    if self.mwer is not None:
+                        loss = self.train_step(x, y, state_len)
+                        # the reference rows of the teacher-forced pass are the CE step's logits
+                        prediction = self.train_step.last_logits[self.mwer['beam_size']::self.mwer['beam_size'] + 1]
+                        prediction = prediction[:, :ans_len]
+                    else:
+                        loss = self.train_step(x, y, state_len, ans_len)
+                        prediction = self.train_step.last_logits
                     if self.train_step.skipped_steps > self._nan_reported:
                         self._nan_reported = self.train_step.skipped_steps
                         self.verbose('Error : grad norm is NaN @ step {}'.format(self.tr.step - 1))
@@ -416,6 +469,8 @@ class ASRTrainer(Solver):
                 if self.rank == 0:
                     if self.tr.step % self.logging_step == 0:
                         self.lg.scalar('train_loss', loss.item(), self.tr.step)
+                        if self.mwer is not None:
+                            self.lg.scalar('mwer_risk', self.train_step.last_risk.mean().item(), self.tr.step)
                         self.lg.scalar('train_acc', calc_acc(prediction, label), self.tr.step)
                     if self.tr.step % self.wer_step == 0:
                         self.lg.scalar('train_error',

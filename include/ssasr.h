@@ -29,7 +29,8 @@
  * search -- ssasr_beam_terms, ssasr_decode_beam_ex_ws_bytes, ssasr_decode_beam_ex; SpecAugment in batch assembly and label smoothing in the
  * masked CE -- ssasr_specaug, ssasr_gather_batch_aug, ssasr_specaug_plan, ssasr_ce_loss_ls_fwd, ssasr_ce_loss_ls_bwd; CTC forced
  * alignment -- ssasr_ctc_align_ws_bytes, ssasr_ctc_align; edit-distance scoring -- ssasr_edit_score; MWER training --
- * ssasr_mwer_ws_bytes, ssasr_mwer_loss_fwd, ssasr_mwer_loss_bwd, ssasr_mwer_pack, ssasr_rows_repeat_fwd, ssasr_rows_repeat_bwd.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
+ * ssasr_mwer_ws_bytes, ssasr_mwer_loss_fwd, ssasr_mwer_loss_bwd, ssasr_mwer_pack, ssasr_rows_repeat_fwd, ssasr_rows_repeat_bwd; sampled
+ * decoding -- ssasr_sample, ssasr_decode_sample_ws_bytes, ssasr_decode_sample, ssasr_mwer_loss_fwd_ex.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
  * (nothing older changed).  15: inference -- ssasr_charlm, ssasr_charlm_step, ssasr_infer, ssasr_decode_greedy (nothing
  * older changed).  14 and before: the training entry points below.
  *
@@ -518,6 +519,23 @@ int ssasr_mwer_loss_bwd(const float* logits, const int32_t* y, int64_t y_ld, int
                         int64_t M, int64_t U, int64_t V, const void* ws, int64_t ws_bytes,
                         const float* dloss, float* dlogits, void* stream);
 
+/* ssasr_mwer_loss_fwd with a choice of posterior (added under ABI 16).  posterior 0: the definition above -- the same
+ * kernels, the same bits.  posterior 1, the Monte-Carlo form for a set of SAMPLES drawn from the model's own
+ * distribution (ssasr_decode_sample at temperature 1, no LM): p_k = 1 / |S_g| for k in S_g and 0 outside, whatever
+ * logP is, so Rbar_g is the plain mean risk of the set and the row weight
+ *   w_r = ce_w[r] - (1 / G) (1 / |S_g|) (risk_r - Rbar_g)
+ * is the score-function (REINFORCE) estimator of the gradient of E[risk] with the set's mean risk as the baseline
+ * (Shannon 2017; Prabhavalkar et al. 2018, 3.1).  The baseline INCLUDES the row itself: the estimate is the unbiased
+ * leave-one-out one scaled by (|S| - 1) / |S|, and a set of ONE sample gets no risk gradient at all (its weight is
+ * ce_w alone).  Duplicate samples are legitimate draws and stay in the set.  logP, the workspace layout, risk_out and
+ * loss keep their meaning (loss = (1 / G) sum_g Rbar_g + the CE terms: its VALUE does not depend on logP through the
+ * risk, the gradient is carried by w); ssasr_mwer_loss_bwd is unchanged, it reads w from the workspace.  Any other
+ * posterior is an argument error. */
+int ssasr_mwer_loss_fwd_ex(const float* logits, const int32_t* y, int64_t y_ld, int64_t y_cols,
+                           const int32_t* n_hyps, const int32_t* counts, int unit, const float* ce_w,
+                           int64_t G, int64_t M, int64_t U, int64_t V, void* ws, int64_t ws_bytes,
+                           float* risk_out, float* loss, int posterior, void* stream);
+
 /* The teacher / label matrix of an MWER step from device-resident results: ssasr_decode_beam's chars [N][K][steps],
  * n_chars [N][K] and n_hyps [N], and the batch's label matrix y_ref [N][ref_cols] (row stride ref_ld; <sos> column
  * first, 0-padded).  rows int32 [N * (K + 1)][L], every element written:
@@ -969,6 +987,45 @@ int64_t ssasr_decode_beam_ex_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E
                                       int64_t V, int64_t Hl, int64_t S, int32_t ctc, int32_t coverage);
 int ssasr_decode_beam_ex(const ssasr_beam* d, const ssasr_ctc_prefix* c /* NULL or weight 0: no CTC */,
                          const ssasr_beam_terms* t, void* stream);
+
+/* ---- sampled decoding (added under ABI 16) ---------------------------------------------------------------------
+ * BUILD-DEFINED: the reference draws characters only inside its training loop (scheduled sampling).  The loop of
+ * ssasr_decode_greedy for K independent SAMPLES per utterance drawn from the model's own distribution, ONE launch,
+ * one workgroup per utterance for the whole loop; workgroups exchange nothing, nothing spins, every loop is bounded
+ * by max_steps, enc_len, K or a dimension.  comp and every weight matrix are streamed once per step for all of the
+ * utterance's samples.  d: a ssasr_beam whose K is the number of samples per utterance; sizes, pointers, parameters,
+ * lm, lm_weight and eos mean what they mean to ssasr_decode_beam.
+ * Per sample (n, k): zero states, input <SOS> = 0.  At step s, with row = the score row ssasr_decode_greedy computes
+ * for that state (log_softmax(speller) + lm_weight * log_softmax(lm); the first term alone when lm is NULL) and
+ * u = uniforms[n][k][s]:
+ *   z_v = row_v / tau,  m = max_v z_v,  e_v = expf(z_v - m),  total = sum_v e_v (index order);
+ *   the drawn character is the first v, in index order, whose running sum e_0 + .. + e_v exceeds u * total, and
+ *   V - 1 when none does (the rule of the training loop's sampled steps);
+ *   a drawn eos ends the sample: it is not part of the text, its terms are part of the two sums below; otherwise the
+ *   character's embedding feeds the next step;
+ *   after max_steps steps a live sample is emitted as it stands, n_chars = max_steps.
+ * Outputs, all written completely: chars [N][K][max_steps] in SLOT order (unsorted), zero past n_chars; n_chars [N][K];
+ * hyp_scores [N][K] = the sum of row[drawn] over the executed steps (ssasr_decode_beam's score of that text, so the
+ * two are comparable); n_hyps[n] = K; logq[n][k] = the sum of (z_drawn - m - logf(total)), the log-probability of the
+ * draws under the distribution that was sampled (equal to hyp_scores at tau = 1 without an LM, up to rounding).
+ * Sample (n, k) depends on its utterance's frames, enc_len, tau and its own row of uniforms alone: the same bits for
+ * any N, any padded T.  A finished sample keeps its slot: the step's products run over the slots up to the highest
+ * live one and what a finished slot computes is discarded; a workgroup exits once none of its samples is live.  A
+ * slot's state is kept once (no selection, no re-parenting).
+ * Accepted: what ssasr_decode_beam accepts, with 1 <= K <= 32, uniforms non-NULL and 4-byte aligned, tau finite and
+ * > 0, ws_bytes >= ssasr_decode_sample_ws_bytes(...) (0 for sizes that are not accepted).  Everything else, s == NULL
+ * included, is an argument error before any HIP call.  Not built: top-k / nucleus truncation, a generator inside the
+ * kernel, a CTC term. */
+typedef struct ssasr_sample {
+  const float* uniforms;  /* [N][K][max_steps], each in [0, 1); step s of sample (n, k) reads [n][k][s]          */
+  float temperature;      /* tau > 0, finite                                                                       */
+  float* logq;            /* [N][K] optional: the summed log-probability of the drawn characters under the      */
+                          /* distribution that was sampled (the ending <EOS>'s included)                         */
+} ssasr_sample;
+
+int64_t ssasr_decode_sample_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D, int64_t V,
+                                     int64_t Hl, int64_t S);
+int ssasr_decode_sample(const ssasr_beam* d, const ssasr_sample* s, void* stream);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,11 @@ class BeamTerms(C.Structure):
                 ('n_steps', P)]
 
 
+class Sample(C.Structure):
+    """struct ssasr_sample (include/ssasr.h)."""
+    _fields_ = [('uniforms', P), ('temperature', F32), ('logq', P)]
+
+
 class SpecAug(C.Structure):
     """struct ssasr_specaug (include/ssasr.h)."""
     _fields_ = [('n_freq', C.c_int32), ('max_freq', C.c_int32), ('n_time', C.c_int32), ('max_time', C.c_int32),
@@ -124,6 +129,8 @@ SIGNATURES = {
     'ssasr_decode_beam_ctc': (I32, [C.POINTER(Beam), C.POINTER(CtcPrefix), P]),
     'ssasr_decode_beam_ex_ws_bytes': (I64, [I64] * 9 + [I32, I32]),
     'ssasr_decode_beam_ex': (I32, [C.POINTER(Beam), C.POINTER(CtcPrefix), C.POINTER(BeamTerms), P]),
+    'ssasr_decode_sample_ws_bytes': (I64, [I64] * 9),
+    'ssasr_decode_sample': (I32, [C.POINTER(Beam), C.POINTER(Sample), P]),
     'ssasr_charlm_train_ws_floats': (I64, [I64, I64, I64, I64]),
     'ssasr_charlm_train_fwd': (I32, [C.POINTER(CharLM), P, P, P, P, I64, I64, P, P, P, P, P]),
     'ssasr_charlm_train_bwd': (I32, [C.POINTER(CharLM), P, I64, I64, F32, P, P]),
@@ -139,6 +146,7 @@ SIGNATURES = {
     'ssasr_edit_score': (I32, [P, I64, P, P, I64, P, P, I64, I64, I64, I32, I32, P, P]),
     'ssasr_mwer_ws_bytes': (I64, [I64, I64, I64]),
     'ssasr_mwer_loss_fwd': (I32, [P, P, I64, I64, P, P, I32, P, I64, I64, I64, I64, P, I64, P, P, P]),
+    'ssasr_mwer_loss_fwd_ex': (I32, [P, P, I64, I64, P, P, I32, P, I64, I64, I64, I64, P, I64, P, P, I32, P]),
     'ssasr_mwer_loss_bwd': (I32, [P, P, I64, I64, I64, I64, I64, I64, P, I64, P, P, P]),
     'ssasr_mwer_pack': (I32, [P, P, P, P, I64, I64, I64, I64, I64, I32, I64, P, P, P]),
     'ssasr_rows_repeat_fwd': (I32, [P, I64, I64, I64, P, P]),

@@ -291,6 +291,9 @@ class ASR(nn.Module):
         # what the most recent decode_many / decode_nbest call left to score(): (chars [N, K, steps] int32,
         # n_chars [N, K] int32, n_hyps [N] int32), views of last_decode (K = 1) or last_beam
         self.last_hyps = None
+        # sample's device results: (chars [N, K, steps] int32 in slot order, n_chars [N, K] int32, hyp_scores [N, K],
+        # n_hyps [N] int32, logq [N, K])
+        self.last_samples = None
         self.init_parameters()
 
     def init_parameters(self):
@@ -617,3 +620,36 @@ class ASR(nn.Module):
         chars, n_chars, hyp_scores, n_hyps = [t.cpu().tolist() for t in self.last_beam]
         return [[(''.join(mapper.ind_to_char(c) for c in chars[i][k][:n_chars[i][k]]), hyp_scores[i][k])
                  for k in range(n_hyps[i])] for i in range(len(xs))]
+
+    def sample(self, xs, x_lens, mapper, n_samples, *, temperature=1.0, rnn_lm=None, lm_weight=0.0,
+               max_decoding_steps=200, generator=None, uniforms=None):
+        """BUILD-DEFINED: n_samples (1 .. 32) transcripts per utterance DRAWN from the model's own distribution, for a
+        list of single utterances in ONE launch (ssasr_decode_sample, include/ssasr.h): every step draws a character
+        from softmax(score row / temperature), the score row being log_softmax(speller) + lm_weight *
+        log_softmax(rnn_lm); a drawn <EOS> ends a sample.  Each utterance is encoded alone, as in decode_nbest.  The
+        uniforms [N, n_samples, max_decoding_steps] come from torch.rand on the device (`generator`: a device
+        torch.Generator, for reproducible draws) unless `uniforms` is given.  Returns per utterance the list of
+        (text, score) in SLOT order (unsorted; score as decode_nbest's).  last_samples keeps (chars, n_chars,
+        hyp_scores, n_hyps, logq) on the device; last_hyps is set, so score() scores the samples: its chars / words
+        are slot 0's and its oracle entry is the best of the draws."""
+        n_samples = int(n_samples)
+        if not 1 <= n_samples <= ops.MAX_BEAM:
+            raise ValueError('n_samples must be in 1..%d, got %d' % (ops.MAX_BEAM, n_samples))
+        temperature = float(temperature)
+        if not (math.isfinite(temperature) and temperature > 0.0):
+            raise ValueError('temperature must be finite and > 0, got %r' % (temperature,))
+        with torch.no_grad():
+            packed, enc_lens = self._encode_packed(xs, x_lens)
+            shape = (packed.shape[0], n_samples, int(max_decoding_steps))
+            if uniforms is None:
+                uniforms = torch.rand(shape, device=packed.device, dtype=torch.float32, generator=generator)
+            elif tuple(uniforms.shape) != shape:
+                raise ValueError('sample: uniforms must be %r, got %r' % (shape, tuple(uniforms.shape)))
+            self.last_samples = ops.decode_sample(
+                packed, enc_lens, self._decoder_params(), (self.attention.psi.weight, self.attention.psi.bias),
+                rnn_lm, lm_weight, mapper.char_to_ind(EOS_TKN), max_decoding_steps, n_samples,
+                uniforms.to(device=packed.device, dtype=torch.float32), temperature)
+            self.last_hyps = (self.last_samples[0], self.last_samples[1], self.last_samples[3])
+        chars, n_chars, hyp_scores = [t.cpu().tolist() for t in self.last_samples[:3]]
+        return [[(''.join(mapper.ind_to_char(c) for c in chars[i][k][:n_chars[i][k]]), hyp_scores[i][k])
+                 for k in range(n_samples)] for i in range(len(xs))]

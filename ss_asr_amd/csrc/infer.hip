@@ -1,7 +1,7 @@
 // Inference: the greedy decode loop of ASR.decode (src/asr.py:112-173) with the CharLM term
 // (src/charlm.py:46-57) as ONE launch for N encoded utterances, the same loop as a beam search over up to 32
-// hypotheses per utterance (decode_beam_kernel, below), and one CharLM step for callers that drive the
-// language model themselves.
+// hypotheses per utterance (decode_beam_kernel, below) and as up to 32 samples per utterance drawn from the model's
+// own distribution (decode_sample_kernel), and one CharLM step for callers that drive the language model themselves.
 //
 // One workgroup owns one utterance for its whole loop.  Nothing is exchanged between workgroups:
 // no status words, no spins, no arena.  Every loop is bounded by max_steps / enc_len / a dimension,
@@ -13,12 +13,12 @@
 // on that utterance's frames and enc_len alone, never on N or the padded T': an utterance decoded
 // in a batch gives the bits it gives alone.
 //
-// The three kernels are built from one set of step helpers, each over n hypotheses whose rows lie a stride apart
+// The four kernels are built from one set of step helpers, each over n hypotheses whose rows lie a stride apart
 // (the greedy kernel and the CharLM step pass n = 1): matmat_n / matvec / matmat (weight rows x input vectors, comp =
 // tanh(psi(feat)) included), lstm_update, gru_update, context_partial + context_reduce (att . feat) and score_row
 // (log_softmax(asr) + lm_weight * log_softmax(lm)).  Per kernel: where the state lives, the softmax over the frames
 // (block-wide / a wave per hypothesis: different summation orders) and what follows the score row (the arg-max /
-// the beam's selection, back-pointers and output).
+// the beam's selection, back-pointers and output / the sampler's draw).
 #include <cmath>
 #include "../../include/ssasr.h"
 #include "common.h"
@@ -446,13 +446,15 @@ struct BeamWs {
   int Sz, Tp, G;
 };
 __host__ __device__ inline int64_t up4l(int64_t v) { return (v + 3) & ~(int64_t)3; }
-__host__ __device__ inline BeamWs beam_ws_map(int K, int T, int E, int A, int D, int Hl, int S) {
+// bufs: copies of the K state rows (the beam search re-parents from one buffer into the other, the sampler keeps one);
+// bp: int32 back-pointer words (the sampler writes its characters straight to the output)
+__host__ __device__ inline BeamWs decode_ws_map(int K, int T, int E, int A, int D, int Hl, int bufs, int64_t bp) {
   BeamWs m;
   m.Sz = 4 * D + 2 * Hl;                  // h1 | c1 | h2 | c2 | LM h1 | LM h2 of one hypothesis
   m.Tp = up4(T);
   m.G = context_groups(E);
   int64_t o = 0;
-  m.st = o; o += 2 * (int64_t)K * m.Sz;   // two buffers of K rows
+  m.st = o; o += bufs * (int64_t)K * m.Sz;
   m.xin = o; o += (int64_t)K * (D + E);   // [embedding of the last character | context]
   m.lmx = o; o += (int64_t)K * Hl;
   m.q = o; o += (int64_t)K * A;
@@ -463,9 +465,32 @@ __host__ __device__ inline BeamWs beam_ws_map(int K, int T, int E, int A, int D,
   m.gh = o; o += (int64_t)K * 3 * Hl;
   m.lg = o; o += (int64_t)K * 64;
   m.lmlg = o; o += (int64_t)K * 64;
-  m.bp = o; o += up4l((int64_t)S * K);    // int32 back-pointers [S][K]: parent | char << 8
+  m.bp = o; o += up4l(bp);
   m.total = up4l(o);
   return m;
+}
+// two buffers of K rows; int32 back-pointers [S][K]: parent | char << 8
+__host__ __device__ inline BeamWs beam_ws_map(int K, int T, int E, int A, int D, int Hl, int S) {
+  return decode_ws_map(K, T, E, A, D, Hl, 2, (int64_t)S * K);
+}
+__host__ __device__ inline BeamWs sample_ws_map(int K, int T, int E, int A, int D, int Hl) {
+  return decode_ws_map(K, T, E, A, D, Hl, 1, 0);
+}
+
+// A wave's half of the softmax over one hypothesis' frames: row[t] = exp(row[t] - max) for t < len; returns the
+// sum, in every lane.  The caller divides (the coverage form of the beam search folds its counts into that pass).
+__device__ __forceinline__ float wave_exp_row(float* row, int len) {
+  const int lane = threadIdx.x & 63;
+  float mx = -INFINITY;
+  for (int t = lane; t < len; t += 64) mx = fmaxf(mx, row[t]);
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int t = lane; t < len; t += 64) {
+    const float ex = expf(row[t] - mx);
+    row[t] = ex;
+    sum += ex;
+  }
+  return wave_sum(sum);
 }
 
 struct BeamDev {
@@ -719,16 +744,7 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
     // order: the two stay apart) | LM layer 2 products
     for (int b = wave; b < live; b += kWaves) {
       float* row = en + (int64_t)b * Tp;
-      float mx = -INFINITY;
-      for (int t = lane; t < len; t += 64) mx = fmaxf(mx, row[t]);
-      mx = wave_max(mx);
-      float sum = 0.f;
-      for (int t = lane; t < len; t += 64) {
-        const float ex = expf(row[t] - mx);
-        row[t] = ex;
-        sum += ex;
-      }
-      sum = wave_sum(sum);
+      const float sum = wave_exp_row(row, len);
       if constexpr (TERMS) {
         if (cover) {                                 // cum' = cum + att in place, cov' = frames with cum' > tau
           float* cum = ccur + (int64_t)b * Tp;
@@ -980,6 +996,167 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
   }
 }
 
+// ---- sampled decoding (semantics in include/ssasr.h, ssasr_decode_sample) ------------------------------------------
+// decode_sample_kernel: the loop of decode_greedy_kernel for K independent samples of one utterance in ONE workgroup,
+// with decode_beam_kernel's layout -- a workgroup owns an utterance for the whole loop, exchanges nothing and never
+// spins; comp is computed once; every weight matrix and feat are streamed once per step for all of the utterance's
+// samples; per-sample state and intermediates are in the workspace slice, writer and reader phases a phase_sync()
+// apart.  There is no selection and no re-parenting: a slot's state is kept ONCE and updated in place, its characters
+// go straight to the output row, and LDS holds the slots' flags, last characters and two running sums.
+// Finished slots stay where they are.  The products run over slots 0 .. hi - 1, hi being one past the highest live
+// slot; what a finished slot below hi computes is discarded (its flag is down: it draws nothing, writes nothing and
+// is fed nothing).  matmat_n, context_partial and the updates give a vector the same bits wherever it lies and however
+// many lie beside it, so a sample does not depend on the other slots.  Why not compact: a pass of matmat holds kHyps
+// vectors against the streamed rows, so at K <= kHyps a dead slot costs FMAs in a pass that runs anyway, and moving
+// a live slot's state rows into a hole would cost a copy phase and a slot map for the outputs; trimming to hi sheds
+// the passes that a finished tail would cost at K > kHyps.
+struct SampleDev {
+  InferDev in;                            // in.chars [N][K][S], in.n_chars [N][K]; in.scores / in.att unused
+  int K;
+  float* ws;
+  float* hyp_scores;
+  int32_t* n_hyps;
+  const float* uniforms;                  // [N][K][S]
+  float tau;
+  float* logq;                            // [N][K] or nullptr
+};
+
+__global__ __launch_bounds__(kThreads) void decode_sample_kernel(SampleDev sd) {
+  __shared__ int alive[kMaxBeam], chr[kMaxBeam], nch[kMaxBeam];
+  __shared__ float score[kMaxBeam], logq[kMaxBeam];  // sums over the drawn characters: row[v], log q(v)
+
+  const InferDev& p = sd.in;
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int T = p.T, E = p.E, A = p.A, D = p.D, V = p.V, Hl = p.lm.H, K = sd.K, S = p.max_steps;
+  const BeamWs m = sample_ws_map(K, T, E, A, D, Hl);
+  float* ws = sd.ws + (int64_t)n * m.total;
+  float *st = ws + m.st, *xin = ws + m.xin, *lmx = ws + m.lmx, *q = ws + m.q, *gates = ws + m.gates, *en = ws + m.en,
+        *part = ws + m.part, *gi = ws + m.gi, *gh = ws + m.gh, *lg = ws + m.lg, *lmlg = ws + m.lmlg;
+  float *h1 = st, *c1 = st + D, *h2 = st + 2 * D, *c2 = st + 3 * D, *lmh1 = st + 4 * D, *lmh2 = lmh1 + Hl;
+  const int Sz = m.Sz, Tp = m.Tp, G = m.G, XI = D + E;
+
+  const int len = min(max(p.enc_len[n], 1), T);      // frames this utterance attends over
+  const float* feat = p.feat + (int64_t)n * T * E;
+  float* comp = p.comp + (int64_t)n * T * A;
+  int32_t* chars = p.chars + (int64_t)n * K * S;
+  const float* uni = sd.uniforms + (int64_t)n * K * S;
+
+  // comp = tanh(psi(feat)) once, shared by every sample; K samples: zero states, <SOS> = 0 as the input character
+  matmat(p.w_psi, E, feat, E, E, nullptr, 0, nullptr, 0, 0, p.b_psi, nullptr, A, 1, comp, A, len);
+  for (int i = tid; i < K * Sz; i += kThreads) st[i] = 0.f;
+  for (int i = tid; i < K * D; i += kThreads) xin[(int64_t)(i / D) * XI + i % D] = p.embed[i % D];
+  for (int i = tid; i < K * Hl; i += kThreads) lmx[i] = p.lm.emb[i % Hl];
+  for (int64_t i = tid; i < (int64_t)K * S; i += kThreads) chars[i] = 0;
+  if (tid < K) {
+    alive[tid] = 1;
+    nch[tid] = S;                                    // a sample the cap ends has max_steps characters
+    score[tid] = 0.f;
+    logq[tid] = 0.f;
+  }
+  phase_sync();
+
+  int hi = K;                                        // one past the highest live slot
+  for (int step = 0; step < S && hi > 0; ++step) {
+    // 1: q = tanh(phi(h1)) | LM layer 1 products
+    matmat(p.w_phi, D, h1, Sz, D, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, A, 1, q, A, hi);
+    if (Hl) {
+      matmat(p.lm.w_ih1, Hl, lmx, Hl, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_ih1, nullptr, 3 * Hl, 0, gi, 3 * Hl, hi);
+      matmat(p.lm.w_hh1, Hl, lmh1, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_hh1, nullptr, 3 * Hl, 0, gh, 3 * Hl, hi);
+    }
+    phase_sync();
+    // 2: energies over the utterance's frames | LM layer 1 update
+    gru_update(gi, gh, 3 * Hl, lmh1, Sz, Hl, hi);
+    matmat(comp, A, q, A, A, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, len, 0, en, Tp, hi);
+    phase_sync();
+    // 3: softmax over the frames, a wave per sample | LM layer 2 products
+    for (int b = wave; b < hi; b += kWaves) {
+      float* row = en + (int64_t)b * Tp;
+      const float sum = wave_exp_row(row, len);
+      for (int t = lane; t < len; t += 64) row[t] = row[t] / sum;
+    }
+    if (Hl) {
+      matmat(p.lm.w_ih2, Hl, lmh1, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_ih2, nullptr, 3 * Hl, 0, gi, 3 * Hl, hi);
+      matmat(p.lm.w_hh2, Hl, lmh2, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_hh2, nullptr, 3 * Hl, 0, gh, 3 * Hl, hi);
+    }
+    phase_sync();
+    // 4: context = att . feat | LM layer 2 update
+    context_partial<kHyps>(feat, E, len, G, en, Tp, hi, G == 1 ? xin + D : part, (int64_t)K * E, G == 1 ? XI : E);
+    gru_update(gi, gh, 3 * Hl, lmh2, Sz, Hl, hi);
+    phase_sync();
+    if (G > 1) {
+      context_reduce(part, (int64_t)K * E, E, G, xin + D, XI, E, hi);
+      phase_sync();
+    }
+    // 5: Speller cell 1 on [embedding | context] | LM output layer
+    matmat(p.w_ih1, XI, xin, XI, XI, p.w_hh1, D, h1, Sz, D, p.b_ih1, p.b_hh1, 4 * D, 0, gates, 4 * D, hi);
+    if (Hl) matmat(p.lm.w_out, Hl, lmh2, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_out, nullptr, V, 0, lmlg, 64, hi);
+    phase_sync();
+    lstm_update(gates, 4 * D, h1, c1, Sz, D, hi);
+    phase_sync();
+    // 6: cell 2
+    matmat(p.w_ih2, D, h1, Sz, D, p.w_hh2, D, h2, Sz, D, p.b_ih2, p.b_hh2, 4 * D, 0, gates, 4 * D, hi);
+    phase_sync();
+    lstm_update(gates, 4 * D, h2, c2, Sz, D, hi);
+    phase_sync();
+    // 7: char_trans
+    matmat(p.w_ct, D, h2, Sz, D, nullptr, 0, nullptr, 0, 0, p.b_ct, nullptr, V, 0, lg, 64, hi);
+    phase_sync();
+    // 8: the draw, a wave per live sample: z = row / tau, e = exp(z - max z), the first v whose running sum of e
+    // exceeds u * total (V - 1 when none does); the sums run in index order, the same in every lane
+    for (int b = wave; b < hi; b += kWaves) {
+      if (!alive[b]) continue;
+      const float fin = score_row(lg + b * 64, Hl ? lmlg + b * 64 : nullptr, V, p.lm_weight);
+      const float z = lane < V ? fin / sd.tau : -INFINITY;
+      const float zm = wave_max(z);
+      const float e = lane < V ? expf(z - zm) : 0.f;
+      float total = 0.f;
+      for (int v = 0; v < V; ++v) total += __shfl(e, v, 64);
+      const float target = uni[(int64_t)b * S + step] * total;
+      float run = 0.f;
+      int pick = V - 1;
+      for (int v = 0; v < V; ++v) {
+        run += __shfl(e, v, 64);
+        if (run > target) {
+          pick = v;
+          break;
+        }
+      }
+      const float rv = __shfl(fin, pick, 64), zv = __shfl(z, pick, 64);
+      if (lane == 0) {
+        score[b] += rv;
+        logq[b] += zv - zm - logf(total);
+        if (pick == p.eos) {                         // <EOS> ends the sample and is not part of the text
+          alive[b] = 0;
+          nch[b] = step;
+        } else {
+          chars[(int64_t)b * S + step] = pick;
+          chr[b] = pick;
+        }
+      }
+    }
+    __syncthreads();
+    // 9: the live slots' next inputs are their characters' embeddings
+    int top = 0;
+    for (int b = 0; b < hi; ++b) top = alive[b] ? b + 1 : top;
+    hi = top;
+    for (int i = tid; i < hi * D; i += kThreads) {
+      const int j = i / D, u = i % D;
+      if (alive[j]) xin[(int64_t)j * XI + u] = p.embed[(int64_t)chr[j] * D + u];
+    }
+    for (int i = tid; i < hi * Hl; i += kThreads) {
+      const int j = i / Hl, u = i % Hl;
+      if (alive[j]) lmx[(int64_t)j * Hl + u] = p.lm.emb[(int64_t)chr[j] * Hl + u];
+    }
+    phase_sync();
+  }
+  if (tid < K) {
+    p.n_chars[(int64_t)n * K + tid] = nch[tid];
+    sd.hyp_scores[(int64_t)n * K + tid] = score[tid];
+    if (sd.logq) sd.logq[(int64_t)n * K + tid] = logq[tid];
+  }
+  if (tid == 0) sd.n_hyps[n] = K;
+}
+
 // One CharLM.forward (src/charlm.py:46-57) for B rows, a workgroup per row.
 struct LmStepDev {
   LmDev lm;
@@ -1158,6 +1335,27 @@ extern "C" int ssasr_decode_beam_ex(const ssasr_beam* dp, const ssasr_ctc_prefix
                                     void* stream) {
   if (!tp) return SSASR_EARG;
   return launch_beam(dp, cp, tp, stream);
+}
+
+extern "C" int64_t ssasr_decode_sample_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
+                                                int64_t V, int64_t Hl, int64_t S) {
+  if (!decode_dims_ok(N, K, T, E, A, D, V, Hl, S)) return 0;
+  return N * sample_ws_map((int)K, (int)T, (int)E, (int)A, (int)D, (int)Hl).total * (int64_t)sizeof(float);
+}
+
+extern "C" int ssasr_decode_sample(const ssasr_beam* dp, const ssasr_sample* sp, void* stream) {
+  SampleDev s{};
+  if (!dp || !sp || !infer_dev(*dp, dp->K, s.in)) return SSASR_EARG;
+  const ssasr_beam& d = *dp;
+  if (!sp->uniforms || (reinterpret_cast<uintptr_t>(sp->uniforms) & 3) != 0) return SSASR_EARG;
+  if (!(std::isfinite(sp->temperature) && sp->temperature > 0.f)) return SSASR_EARG;
+  const int64_t need = ssasr_decode_sample_ws_bytes(d.N, d.K, d.T, d.E, d.A, d.D, d.V, s.in.lm.H, d.max_steps);
+  if (!d.ws || !aligned16(d.ws) || !d.hyp_scores || !d.n_hyps || d.ws_bytes < need) return SSASR_EARG;
+  s.K = (int)d.K; s.ws = d.ws; s.hyp_scores = d.hyp_scores; s.n_hyps = d.n_hyps;
+  s.uniforms = sp->uniforms; s.tau = sp->temperature; s.logq = sp->logq;
+  hipLaunchKernelGGL(decode_sample_kernel, dim3((unsigned)d.N), dim3(kThreads), 0, (hipStream_t)stream, s);
+  SSASR_LAUNCH_CHECK();
+  return SSASR_OK;
 }
 
 extern "C" int ssasr_charlm_step(const ssasr_charlm* lm, const int32_t* x, const float* h1, const float* h2,

@@ -9,7 +9,8 @@
 //      and adds (double)z[lab] - lse into the block's share of the row's log-probability.
 //   2. mwer_groups_kernel, ONE block of 256 threads: a wave per group, a lane per candidate (M <= 33 <= 64).  logP_k in
 //      block order, the softmax over the set in double with the maximum subtracted, the expected risk, and each row's
-//      sequence-level weight w_r = ce_w[r] - (1 / G) p_r (risk_r - Rbar_g), which is all the backward needs.  Then the
+//      sequence-level weight w_r = ce_w[r] - (1 / G) p_r (risk_r - Rbar_g), which is all the backward needs
+//      (ssasr_mwer_loss_fwd_ex, posterior 1: p_k = 1 / |S_g| instead of the softmax, the rest unchanged).  Then the
 //      block sums the groups' contributions: thread t takes groups t, t + 256, ... in order, the 256 partial sums are
 //      added in index order by thread 0.  No atomics: the same bits every run.
 // Backward: mwer_bwd_kernel, a wave per (r, t) step: unlabelled steps are stored as zeros without a load.
@@ -106,8 +107,8 @@ __global__ __launch_bounds__(256) void mwer_rows_kernel(const float* logits, con
 }
 
 __global__ __launch_bounds__(256) void mwer_groups_kernel(MwerWs w, const int32_t* n_hyps, const int32_t* counts,
-                                                          const float* ce_w, int G, int M, int unit, float* risk_out,
-                                                          float* loss) {
+                                                          const float* ce_w, int G, int M, int unit, int uniform,
+                                                          float* risk_out, float* loss) {
   __shared__ double s_risk[256], s_ce[256];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const double inv_g = 1.0 / (double)G;
@@ -125,7 +126,8 @@ __global__ __launch_bounds__(256) void mwer_groups_kernel(MwerWs w, const int32_
     const double mx = wave_max_f64(in ? lp : -INFINITY);
     const double e = in ? exp(lp - mx) : 0.0;              // an empty set: every e is 0 and nothing below divides
     const double z = wave_sum_f64(e);
-    const double p = in ? e / z : 0.0;
+    // uniform: the Monte-Carlo form, every member of a set of samples weighs 1 / |S|, whatever logP is
+    const double p = in ? (uniform ? 1.0 / (double)n : e / z) : 0.0;
     const double rbar = wave_sum_f64(in ? p * risk : 0.0);
     const double ce = wave_sum_f64(row ? cw * -lp : 0.0);
     if (row) {
@@ -277,11 +279,12 @@ extern "C" int64_t ssasr_mwer_ws_bytes(int64_t G, int64_t M, int64_t U) {
   return 8 * (3 * R + 2 * G + R * MWER_G + R * U) + 8 * ((R * U + 1) / 2);
 }
 
-extern "C" int ssasr_mwer_loss_fwd(const float* logits, const int32_t* y, int64_t y_ld, int64_t y_cols,
+extern "C" int ssasr_mwer_loss_fwd_ex(const float* logits, const int32_t* y, int64_t y_ld, int64_t y_cols,
                                    const int32_t* n_hyps, const int32_t* counts, int unit, const float* ce_w,
                                    int64_t G, int64_t M, int64_t U, int64_t V, void* ws, int64_t ws_bytes,
-                                   float* risk_out, float* loss, void* stream) {
-  if (!mwer_shape_ok(G, M, U, V) || (unit != 0 && unit != 1) || !loss) return SSASR_EARG;
+                                   float* risk_out, float* loss, int posterior, void* stream) {
+  if (!mwer_shape_ok(G, M, U, V) || (posterior != 0 && posterior != 1) || (unit != 0 && unit != 1) || !loss)
+    return SSASR_EARG;
   hipStream_t st = (hipStream_t)stream;
   if (G == 0) {
     SSASR_HIP(hipMemsetAsync(loss, 0, sizeof(float), st));
@@ -294,9 +297,17 @@ extern "C" int ssasr_mwer_loss_fwd(const float* logits, const int32_t* y, int64_
   hipLaunchKernelGGL(mwer_rows_kernel, dim3((unsigned)(G * M), MWER_G), dim3(256), 0, st, logits, y, y_ld, (int)y_cols,
                      (int)U, (int)V, w.lse, w.lse64, w.part);
   hipLaunchKernelGGL(mwer_groups_kernel, dim3(1), dim3(256), 0, st, w, n_hyps, counts, ce_w, (int)G, (int)M, unit,
-                     risk_out, loss);
+                     posterior, risk_out, loss);
   SSASR_LAUNCH_CHECK();
   return SSASR_OK;
+}
+
+extern "C" int ssasr_mwer_loss_fwd(const float* logits, const int32_t* y, int64_t y_ld, int64_t y_cols,
+                                   const int32_t* n_hyps, const int32_t* counts, int unit, const float* ce_w,
+                                   int64_t G, int64_t M, int64_t U, int64_t V, void* ws, int64_t ws_bytes,
+                                   float* risk_out, float* loss, void* stream) {
+  return ssasr_mwer_loss_fwd_ex(logits, y, y_ld, y_cols, n_hyps, counts, unit, ce_w, G, M, U, V, ws, ws_bytes, risk_out,
+                                loss, 0, stream);
 }
 
 extern "C" int ssasr_mwer_loss_bwd(const float* logits, const int32_t* y, int64_t y_ld, int64_t y_cols, int64_t G,

@@ -122,10 +122,17 @@ class MWERTrainStep:
     UNITS = {'char': 0, 'word': 1}
 
     def __init__(self, model, beam_size, ce_weight=0.01, unit='word', lm=None, lm_weight=0.0, max_decoding_steps=200,
-                 lr=1.0, eps=1e-8, rho=0.9, grad_clip=5.0, eos=None, space=None):
+                 lr=1.0, eps=1e-8, rho=0.9, grad_clip=5.0, eos=None, space=None, sampling=False, seed=None):
         """beam_size 1 .. 32 (K); ce_weight >= 0; unit 'word' | 'char': whose errors are the risk; lm, lm_weight: a
         charlm.CharLM fused into the SEARCH only (the loss is the model's own likelihood); max_decoding_steps: the
-        search's step limit.  eos / space: the Mapper's ids of `>` and ` ` (its fixed alphabet's by default)."""
+        search's step limit.  eos / space: the Mapper's ids of `>` and ` ` (its fixed alphabet's by default).
+        sampling: search() DRAWS the K hypotheses from the model's own distribution (ops.decode_sample at temperature
+        1, no LM) instead of searching for them, and the loss weighs them uniformly (ops.mwer_loss, posterior
+        'uniform': the score-function estimate of the expected risk's gradient, the set's mean risk as the
+        baseline).  The uniforms come from a generator the step owns, seeded with `seed` (None: from torch's global
+        generator's seed): the same seed and the same weights give the same samples.  An LM weight is a ValueError
+        then: the samples would no longer come from the distribution the loss differentiates, and an
+        importance-weighted form is not built."""
         from .asr import EOS_INDEX
         from .preprocess import ALL_CHARS, TOKENS, UNK_TKN
         beam_size = int(beam_size)
@@ -137,6 +144,10 @@ class MWERTrainStep:
             raise ValueError('ce_weight must be >= 0, got %r' % (ce_weight,))
         if int(max_decoding_steps) < 1:
             raise ValueError('max_decoding_steps must be >= 1, got %r' % (max_decoding_steps,))
+        if sampling and float(lm_weight) != 0.0:
+            raise ValueError('sampling draws from the model alone: lm_weight must be 0 with it, got %r' % (lm_weight,))
+        if seed is not None and (isinstance(seed, bool) or int(seed) != seed or seed < 0):
+            raise ValueError('seed must be None or an integer >= 0, got %r' % (seed,))
         if not next(model.parameters()).is_cuda:
             raise RuntimeError('MWERTrainStep needs the model on the GPU (no CPU path)')
         self.model, self.beam_size, self.ce_weight, self.unit = model, beam_size, float(ce_weight), unit
@@ -152,6 +163,11 @@ class MWERTrainStep:
         ops.set_wgrad_listener(self.reducer.wgrad_enqueued)
         self._one = torch.ones((), device=self.flat.data.device)
         self._ref_of = {}
+        self.sampling = bool(sampling)
+        self.generator = None          # sampling: the source of search()'s uniforms
+        if self.sampling:
+            self.generator = torch.Generator(device=self.flat.data.device)
+            self.generator.manual_seed(torch.initial_seed() if seed is None else int(seed))
         self.last_logits = None        # [B * (K + 1), U, V] of the most recent step
         self.last_rows = None          # int32 [B * (K + 1), L]: its teacher / label rows
         self.last_hyps = None          # (chars [B, K, steps], n_chars [B, K], n_hyps [B]) it was given or searched
@@ -162,8 +178,17 @@ class MWERTrainStep:
         self.skipped_steps = 0
 
     def search(self, feat, enc_len_dev):
-        """The n-best list of this batch's own features, without grad: (chars, n_chars, n_hyps) on the device."""
+        """The n-best list of this batch's own features (sampling: K draws per utterance), without grad:
+        (chars, n_chars, n_hyps) on the device."""
         m = self.model
+        if self.sampling:
+            with torch.no_grad():
+                uniforms = torch.rand(feat.shape[0], self.beam_size, self.max_decoding_steps, device=feat.device,
+                                      dtype=torch.float32, generator=self.generator)
+                chars, n_chars, _, n_hyps, _ = ops.decode_sample(
+                    feat.detach(), enc_len_dev, m._decoder_params(), (m.attention.psi.weight, m.attention.psi.bias),
+                    None, 0.0, self.eos, self.max_decoding_steps, self.beam_size, uniforms)
+            return chars, n_chars, n_hyps
         with torch.no_grad():
             chars, n_chars, _, n_hyps = ops.decode_beam(
                 feat.detach(), enc_len_dev, m._decoder_params(), (m.attention.psi.weight, m.attention.psi.bias),
@@ -204,7 +229,8 @@ class MWERTrainStep:
         # 5. the reference rows carry the CE: ce_weight / (B denom_b), denom_b = count(y[b] != 0) as in the masked CE
         ce_w = torch.zeros(B, M, device=rows.device, dtype=torch.float32)
         ce_w[:, K] = self.ce_weight / (B * (hyp_lens.view(B, M)[:, K] + 1).clamp(min=1).to(torch.float32))
-        loss, info = ops.mwer_loss(logits, rows, n_hyps, counts, self.UNITS[self.unit], ce_w.view(B * M))
+        loss, info = ops.mwer_loss(logits, rows, n_hyps, counts, self.UNITS[self.unit], ce_w.view(B * M),
+                                   posterior='uniform' if self.sampling else 'renorm')
         self.last_rows, self.last_hyps, self.last_counts = rows, (chars, n_chars, n_hyps), counts
         self.last_risk, self.last_info, self.last_logits = info.risk, info, logits
         return loss, logits

@@ -1089,7 +1089,7 @@ class MWERInfo:
 
 class _MWERLoss(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, rows, n_hyps, counts, unit, ce_w, info):
+    def forward(ctx, logits, rows, n_hyps, counts, unit, ce_w, info, posterior=0):
         lib = _lib.load()
         R, U, V = logits.shape
         G = n_hyps.shape[0]
@@ -1102,9 +1102,14 @@ class _MWERLoss(torch.autograd.Function):
         ws = torch.empty(max(need // 8, 1), device=dev, dtype=torch.float64)
         risk = torch.empty(G, device=dev, dtype=torch.float32)
         loss = torch.empty((), device=dev, dtype=torch.float32)
-        check(lib.ssasr_mwer_loss_fwd(_p(logits), _p(rows), rows.stride(0), rows.shape[1], _p(n_hyps), _p(counts),
-                                      unit, _p(ce_w), G, M, U, V, _p(ws), need, _p(risk), _p(loss), _stream()),
-              'ssasr_mwer_loss_fwd')
+        if posterior:
+            check(lib.ssasr_mwer_loss_fwd_ex(_p(logits), _p(rows), rows.stride(0), rows.shape[1], _p(n_hyps),
+                                             _p(counts), unit, _p(ce_w), G, M, U, V, _p(ws), need, _p(risk), _p(loss),
+                                             posterior, _stream()), 'ssasr_mwer_loss_fwd_ex')
+        else:
+            check(lib.ssasr_mwer_loss_fwd(_p(logits), _p(rows), rows.stride(0), rows.shape[1], _p(n_hyps), _p(counts),
+                                          unit, _p(ce_w), G, M, U, V, _p(ws), need, _p(risk), _p(loss), _stream()),
+                  'ssasr_mwer_loss_fwd')
         info.ws, info.risk = ws, risk
         info.logp, info.p_hat, info.weight = ws[:R], ws[R:2 * R], ws[2 * R:3 * R]
         info.lse = ws[3 * R + 2 * G + 8 * R + R * U:].view(torch.float32)[:R * U].view(R, U)
@@ -1122,17 +1127,25 @@ class _MWERLoss(torch.autograd.Function):
         dlogits = torch.empty_like(logits)
         check(lib.ssasr_mwer_loss_bwd(_p(logits), _p(rows), rows.stride(0), rows.shape[1], G, M, U, V, _p(ws), need,
                                       _p(dloss), _p(dlogits), _stream()), 'ssasr_mwer_loss_bwd')
-        return dlogits, None, None, None, None, None, None
+        return dlogits, None, None, None, None, None, None, None
 
 
-def mwer_loss(logits, rows, n_hyps, counts, unit, ce_w=None):
+MWER_POSTERIORS = {'renorm': 0, 'uniform': 1}
+
+
+def mwer_loss(logits, rows, n_hyps, counts, unit, ce_w=None, posterior='renorm'):
     """The MWER loss of include/ssasr.h (ssasr_mwer_loss_fwd / _bwd; postprocess.mwer_reference is its float64
     restatement).  logits [R, U, V] float32 of R = G * M teacher-forced rows, row g * M + k being candidate k of
     group g; rows int32 [R, >= U + 1], the rows' label matrix (the label of step t is rows[r, t + 1], 0 unlabelled);
     n_hyps int32 [G]: the first clamp(n_hyps[g], 0, M) rows of a group are its hypothesis set; counts int32 [R, 8]:
     edit_score's result; unit 'char' | 'word' (or 0 | 1); ce_w float32 [R] or None: absolute weights of the rows'
-    negative log-likelihoods.  -> (loss, MWERInfo): the loss tensor carries the graph, the info is for logging."""
+    negative log-likelihoods.  posterior 'renorm': the set's posterior is the softmax of the rows' log-probabilities
+    (an n-best list); 'uniform': every member weighs 1 / |set| (samples drawn from the model, ssasr_mwer_loss_fwd_ex's
+    Monte-Carlo form: the loss VALUE is the mean risk plus the CE terms, the gradient is the score-function estimate).
+    -> (loss, MWERInfo): the loss tensor carries the graph, the info is for logging."""
     _need_gpu(logits, rows, n_hyps, counts, ce_w)
+    if posterior not in MWER_POSTERIORS:
+        raise ValueError("mwer_loss: posterior must be 'renorm' or 'uniform', got %r" % (posterior,))
     unit = {'char': 0, 'word': 1}.get(unit, unit)
     if unit not in (0, 1):
         raise ValueError("mwer_loss: unit must be 'char' or 'word', got %r" % (unit,))
@@ -1153,7 +1166,7 @@ def mwer_loss(logits, rows, n_hyps, counts, unit, ce_w=None):
         if tuple(ce_w.shape) != (R,):
             raise ValueError('mwer_loss: ce_w must hold one weight per row')
     info = MWERInfo()
-    return _MWERLoss.apply(logits, rows, n_hyps, counts, unit, ce_w, info), info
+    return _MWERLoss.apply(logits, rows, n_hyps, counts, unit, ce_w, info, MWER_POSTERIORS[posterior]), info
 
 
 def mwer_pack(chars, n_chars, n_hyps, y_ref, eos, L=None):
@@ -1441,6 +1454,35 @@ def decode_beam(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_
     d, outs, keep = beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws)
     check(_lib.load().ssasr_decode_beam(C.byref(d), _stream()), 'ssasr_decode_beam')
     return outs
+
+
+def decode_sample(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, n_samples, uniforms, temperature=1.0):
+    """ssasr_decode_sample over feat [N, T, E] (each utterance encoded alone) and enc_len int32 [N]: 1 <= n_samples
+    <= 32 samples per utterance drawn from softmax(score row / temperature), sample (n, k) taking step s's uniform
+    from uniforms[n, k, s] (float32 [N, n_samples, max_steps] in [0, 1), on the device).
+    -> (chars [N, K, max_steps] int32 in slot order, n_chars [N, K] int32, hyp_scores [N, K] (the beam search's score
+    of that text), n_hyps [N] int32 (= K), logq [N, K]: the draws' log-probability under the sampled distribution).
+    params, psi, lm: as for decode_greedy."""
+    lib = _lib.load()
+    K, S = int(n_samples), int(max_steps)
+    N, T, E = feat.shape
+    A, D = params['w_phi'].shape
+    hl = lm.hidden_size if lm is not None else 0
+    need = int(lib.ssasr_decode_sample_ws_bytes(N, K, T, E, A, D, params['w_ct'].shape[0], hl, S))
+    if need <= 0:
+        raise RuntimeError('ssasr_decode_sample: invalid argument (%d samples, sizes N %d T %d E %d A %d D %d V %d '
+                           'H %d steps %d)' % (K, N, T, E, A, D, params['w_ct'].shape[0], hl, S))
+    _need_gpu(feat, uniforms)
+    if uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (N, K, S):
+        raise ValueError('decode_sample: uniforms must be float32 [%d, %d, %d], got %s %r'
+                         % (N, K, S, uniforms.dtype, tuple(uniforms.shape)))
+    uniforms = uniforms.contiguous()
+    ws = torch.empty(need // 4, device=feat.device, dtype=torch.float32)
+    d, outs, keep = beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, S, K, ws)
+    logq = torch.empty(N, K, device=feat.device, dtype=torch.float32)
+    s = _lib.Sample(uniforms.data_ptr(), float(temperature), logq.data_ptr())
+    check(lib.ssasr_decode_sample(C.byref(d), C.byref(s), _stream()), 'ssasr_decode_sample')
+    return outs + (logq,)
 
 
 CTC_BLANK = 0      # class 0, as in training (ctc.BLANK)

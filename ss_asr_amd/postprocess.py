@@ -75,7 +75,7 @@ def edit_counts(hyp_ids, ref_ids, space, first_char=2):
     return list(edit_ops(hc, rc)) + [len(rc)] + list(edit_ops(hw, rw)) + [len(rw)]
 
 
-def mwer_reference(logits, rows, n_hyps, counts, unit, ce_w=None):
+def mwer_reference(logits, rows, n_hyps, counts, unit, ce_w=None, *, posterior='renorm'):
     """BUILD-DEFINED: the MWER loss of ssasr_mwer_loss_fwd (include/ssasr.h) restated in float64 torch, on any
     device, differentiable by autograd -- what the kernel is defined and tested against.
     logits [R, U, V] of R = G * M teacher-forced rows (row g * M + k: candidate k of group g); rows [R, >= U + 1]
@@ -84,7 +84,14 @@ def mwer_reference(logits, rows, n_hyps, counts, unit, ce_w=None):
     ce_w [R] or None: absolute weights of the rows' negative log-likelihoods.
       logP_r = sum over labelled t of log_softmax(logits[r, t])[label];  p_hat = softmax of logP over the set;
       risk_g = sum_k p_hat_k (S + D + I)_k;  loss = mean_g risk_g + sum_r ce_w[r] (-logP_r).
+    posterior 'uniform' (ssasr_mwer_loss_fwd_ex's Monte-Carlo form, for sets of samples drawn from the model):
+    p_hat_k = 1 / |S_g| inside the set, whatever logP is; risk_g is then the set's mean risk and does not depend on
+    the logits, so the risk term enters the graph as the score-function surrogate sum_r c_r logP_r with the detached
+    c_r = (1 / G) (1 / |S_g|) (risk_r - risk_g), its own value subtracted again: the loss VALUE is as above, its
+    gradient is the estimator's (the baseline risk_g includes the row itself; a set of one gets no risk gradient).
     -> (loss, risk [G], p_hat [R] with 0 outside the sets), all float64."""
+    if posterior not in ('renorm', 'uniform'):
+        raise ValueError("mwer_reference: posterior must be 'renorm' or 'uniform', got %r" % (posterior,))
     unit = {'char': 0, 'word': 1}.get(unit, unit)
     if unit not in (0, 1):
         raise ValueError("mwer_reference: unit must be 'char' or 'word', got %r" % (unit,))
@@ -104,8 +111,13 @@ def mwer_reference(logits, rows, n_hyps, counts, unit, ce_w=None):
     masked = ~inside & inside.any(1, keepdim=True)
     p_hat = torch.softmax(logp.view(G, M).masked_fill(masked, -math.inf), 1)
     p_hat = torch.where(inside, p_hat, torch.zeros_like(p_hat))
+    if posterior == 'uniform':
+        p_hat = inside.to(torch.float64) / inside.sum(1, keepdim=True).clamp(min=1)
     risk = (p_hat * err).sum(1)
     loss = risk.sum() / max(G, 1)
+    if posterior == 'uniform':
+        surrogate = ((p_hat * (err - risk.unsqueeze(1))).reshape(R) * logp).sum() / max(G, 1)
+        loss = loss + surrogate - surrogate.detach()
     if ce_w is not None:
         loss = loss - (ce_w.to(torch.float64) * logp).sum()
     return loss, risk, p_hat.reshape(R)

@@ -258,14 +258,15 @@ class ASRTrainer(Solver):
     masks (at most 8 of a kind; widths drawn from 0 .. *_width, time masks no wider than time_ratio of the
     utterance) applied by the resident loader's batch assembly (GpuResidentLoader, ssasr_gather_batch_aug),
     redrawn every epoch; it needs that loader and raises where it is not in use.
-    asr.mwer: {beam_size, ce_weight, unit, max_decoding_steps}: minimum word error rate training
+    asr.mwer: {beam_size, ce_weight, unit, max_decoding_steps, sampling, seed}: minimum word error rate training
     (engine.MWERTrainStep) instead of the CE step: the expected number of `unit` (word | char) errors over a beam of
     2 .. 32 hypotheses searched on the training batch, plus ce_weight (>= 0) times the masked CE.  `train_loss` is
     then that loss and `mwer_risk`, the mean expected errors per utterance, is logged beside it.  It needs the fused
     step (Adadelta on the GPU) and is not defined together with asr.label_smoothing.  With a ctc_weight model the CTC
-    branch takes no part in the step."""
+    branch takes no part in the step.  sampling: true draws the beam_size hypotheses from the model's own distribution
+    instead of searching for them (seed: an integer >= 0 for the step's generator)."""
     SPEC_AUGMENT_KEYS = ('freq_masks', 'freq_width', 'time_masks', 'time_width', 'time_ratio', 'fill', 'seed')
-    MWER_KEYS = ('beam_size', 'ce_weight', 'unit', 'max_decoding_steps')
+    MWER_KEYS = ('beam_size', 'ce_weight', 'unit', 'max_decoding_steps', 'sampling', 'seed')
 
     @classmethod
     def mwer_options(cls, asr_config):
@@ -296,8 +297,16 @@ class ASRTrainer(Solver):
         unit = conf.get('unit', 'word')
         if unit not in ('word', 'char'):
             raise ValueError("asr.mwer.unit must be 'word' or 'char', got {!r}".format(unit))
-        return dict(beam_size=integer('beam_size', conf['beam_size'], 2, 32), ce_weight=float(ce_weight), unit=unit,
-                    max_decoding_steps=integer('max_decoding_steps', conf.get('max_decoding_steps', 200), 1, 8189))
+        out = dict(beam_size=integer('beam_size', conf['beam_size'], 2, 32), ce_weight=float(ce_weight), unit=unit,
+                   max_decoding_steps=integer('max_decoding_steps', conf.get('max_decoding_steps', 200), 1, 8189))
+        # the sampled form's keys are passed on only when the config names them
+        if 'sampling' in conf:
+            if not isinstance(conf['sampling'], bool):
+                raise ValueError('asr.mwer.sampling must be true or false, got {!r}'.format(conf['sampling']))
+            out['sampling'] = conf['sampling']
+        if 'seed' in conf:
+            out['seed'] = integer('seed', conf['seed'], 0, 2 ** 63 - 1)
+        return out
 
     @classmethod
     def regularisers(cls, asr_config):

@@ -30,7 +30,8 @@
  * masked CE -- ssasr_specaug, ssasr_gather_batch_aug, ssasr_specaug_plan, ssasr_ce_loss_ls_fwd, ssasr_ce_loss_ls_bwd; CTC forced
  * alignment -- ssasr_ctc_align_ws_bytes, ssasr_ctc_align; edit-distance scoring -- ssasr_edit_score; MWER training --
  * ssasr_mwer_ws_bytes, ssasr_mwer_loss_fwd, ssasr_mwer_loss_bwd, ssasr_mwer_pack, ssasr_rows_repeat_fwd, ssasr_rows_repeat_bwd; sampled
- * decoding -- ssasr_sample, ssasr_decode_sample_ws_bytes, ssasr_decode_sample, ssasr_mwer_loss_fwd_ex.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
+ * decoding -- ssasr_sample, ssasr_decode_sample_ws_bytes, ssasr_decode_sample, ssasr_mwer_loss_fwd_ex; minimum-Bayes-risk
+ * selection -- ssasr_mbr_select.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
  * (nothing older changed).  15: inference -- ssasr_charlm, ssasr_charlm_step, ssasr_infer, ssasr_decode_greedy (nothing
  * older changed).  14 and before: the training entry points below.
  *
@@ -480,6 +481,39 @@ int ssasr_edit_score(const int32_t* hyp, int64_t hyp_ld, const int32_t* hyp_lens
                      const int32_t* ref, int64_t ref_ld, const int32_t* ref_lens,
                      const int32_t* ref_of, int64_t P, int64_t Hmax, int64_t Rmax,
                      int32_t first_char, int32_t space, int32_t* out, void* stream);
+
+/* ---- Minimum-Bayes-risk selection (added under ABI 16) -----------------------------------------------------------
+ * BUILD-DEFINED: the reference has no n-best list to choose from.  Of the K hypotheses that a decode left for each of
+ * N utterances (ssasr_decode_beam's or ssasr_decode_sample's chars, n_chars, n_hyps and hyp_scores), the one with the
+ * lowest EXPECTED error count under the list's own posterior (Goel & Byrne 2000; Prabhavalkar et al. 2018, 3), in
+ * ONE launch, one workgroup per utterance: the pairwise distances, the posterior, the risks and the choice.
+ *   Sequences: hypothesis (n, k) is chars[(n * K + k) * hyp_ld + 0 .. clamp(n_chars[n][k], 0, Hmax)).  Its tokens and
+ *   words are exactly ssasr_edit_score's: ids < first_char are dropped, words are the maximal runs of tokens !=
+ *   space.  The set S_n is the rows k < clamp(n_hyps[n], 0, K).
+ *   Distances: for j, k in S_n, pair[n][k][j][0] is the character S + D + I of hypothesis k against hypothesis j as
+ *   the reference and pair[n][k][j][1] the same over words -- the first component of ssasr_edit_score's lexicographic
+ *   minimum (S + D + I, S).  It is symmetric with a zero diagonal; each unordered pair's DP runs once and is written
+ *   twice.  Entries with j or k outside S_n are -1.
+ *   Posterior: posterior 1: p_j = 1 / |S_n|.  posterior 0: with x_j = (double)scale * (double)scores[n][j],
+ *   p_j = exp(x_j - LSE_i x_i) over the finite x of the set, in double, LSE = m + log(sum_i exp(x_i - m)) with the
+ *   maximum m subtracted first; a non-finite x_j gets p_j = 0; if no x of the set is finite the posterior is the
+ *   uniform one.  scores may be NULL when posterior == 1.
+ *   Risk and choice: risk[n][k] = sum_{j in S_n} p_j * pair[n][k][j][unit] (unit 0: characters, 1: words), products
+ *   and sums in double, each rounded on its own (no fused multiply-add), in the order j = 0 .. K - 1, rounded once to
+ *   float; rows outside S_n get +inf.  best[n] is the lowest k in S_n whose double risk is minimal, -1 for an empty
+ *   set.  Every element of best, risk and pair is written; no atomics; nothing depends on scheduling.
+ * Accepted: 0 <= N <= 65535 (N == 0 launches nothing), 1 <= K <= 32, 0 <= Hmax <= 1023 (both sides of a pair are DP
+ * columns), K * Hmax <= 8192 (an utterance's kept tokens: 32 KB of LDS; its word tables stay under 25 KB), hyp_ld >=
+ * Hmax, unit and posterior in {0, 1}, a finite scale >= 0, non-NULL n_chars, n_hyps, best, risk, pair, chars (unless
+ * Hmax == 0) and scores (unless posterior == 1).  Argument errors return before any HIP call.
+ * The block has 64 * max(ceil((Hmax + 1) / 64), min(K (K - 1) / 2, 16)) threads (at least 64): a wave per hypothesis
+ * compacts it and finds its words once, a thread per word numbers it over all of the utterance's words, groups of
+ * ceil((L + 1) / 64) waves (L: the utterance's longest kept sequence) take the pairs round-robin, and a lane per
+ * candidate forms posterior, risk and argmin. */
+int ssasr_mbr_select(const int32_t* chars, int64_t hyp_ld, const int32_t* n_chars, const int32_t* n_hyps,
+                     const float* scores, int64_t N, int64_t K, int64_t Hmax, int32_t first_char, int32_t space,
+                     int unit, int posterior, float scale, int32_t* best, float* risk, int32_t* pair,
+                     void* stream);
 
 /* ---- MWER training (added under ABI 16) ------------------------------------------------------------------------
  * BUILD-DEFINED: the reference trains on the masked CE alone.  Minimum word error rate training (Prabhavalkar et al.

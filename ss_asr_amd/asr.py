@@ -43,6 +43,11 @@ Alignment = collections.namedtuple('Alignment', ('score', 'chars'))
 # (ties: fewest character errors, then lowest k), the best entry itself for a greedy decode.
 Score = collections.namedtuple('Score', ('chars', 'words', 'oracle'))
 
+# ASR.mbr's result for one utterance (BUILD-DEFINED).  k: the slot with the lowest expected error count under the
+# list's own posterior (-1 for an empty list); text: its transcript; risk: that expectation; risks: the tuple of
+# expectations over the list's entries.
+MBR = collections.namedtuple('MBR', ('k', 'text', 'risk', 'risks'))
+
 
 def input_span(first, last, n_frames, frame_shift=None):
     """Encoder frames first .. last (inclusive) -> the input frames [lo, hi) they cover: encoder frame j covers
@@ -291,6 +296,11 @@ class ASR(nn.Module):
         # what the most recent decode_many / decode_nbest call left to score(): (chars [N, K, steps] int32,
         # n_chars [N, K] int32, n_hyps [N] int32), views of last_decode (K = 1) or last_beam
         self.last_hyps = None
+        # the scores [N, K] float32 that belong to last_hyps, and whether last_hyps are draws (sample) -- what mbr()
+        # forms its posterior from; mbr's device results (best [N] int32, risk [N, K], pair [N, K, K, 2] int32)
+        self.last_hyp_scores = None
+        self.last_hyps_sampled = False
+        self.last_mbr = None
         # sample's device results: (chars [N, K, steps] int32 in slot order, n_chars [N, K] int32, hyp_scores [N, K],
         # n_hyps [N] int32, logq [N, K])
         self.last_samples = None
@@ -539,12 +549,67 @@ class ASR(nn.Module):
             hyp, lens = chars.cpu().tolist(), n_chars.cpu().tolist()
             out = [[postprocess.edit_counts(hyp[i][k][:max(lens[i][k], 0)], rows[i], space, first_char)
                     for k in range(K)] for i in range(N)]
+        self.last_score_rows = out          # [N][K][8]: every hypothesis' counts, for callers that choose another slot
         scores = []
         for i in range(N):
             cand = out[i][:max(min(n_hyps_host[i], K), 1)]
             k = min(range(len(cand)), key=lambda k: (sum(cand[k][4:7]), sum(cand[k][0:3]), k))
             scores.append(Score(tuple(cand[0][:4]), tuple(cand[0][4:]), (k, tuple(cand[k][:4]), tuple(cand[k][4:]))))
         return scores
+
+    def mbr(self, mapper, *, unit='word', posterior=None, scale=1.0):
+        """BUILD-DEFINED: minimum-Bayes-risk selection among the hypotheses that the last decode_many / decode_nbest /
+        sample call left on the device (last_hyps, last_hyp_scores): per utterance the entry with the lowest expected
+        number of errors (unit 'word' | 'char') against the other entries, weighted by the list's own posterior.  ONE
+        launch forms the pairwise distances, the posterior, the risks and the choice (ssasr_mbr_select,
+        include/ssasr.h).  posterior 'softmax': p_j = softmax(scale * score_j) over the list; 'uniform': every entry
+        weighs the same, which is right for draws from the model; None: 'uniform' after sample(), 'softmax' otherwise.
+        Returns one MBR(k, text, risk, risks) per utterance; last_mbr keeps (best [N], risk [N, K], pair [N, K, K, 2])
+        on the device.  A group past the kernel's limits (more than 1,023 columns, or more than 8,192 over an
+        utterance's K rows) is selected by postprocess.mbr_reference on the host, last_mbr then holding its results.
+        A call before any decode is a ValueError."""
+        if self.last_hyps is None or self.last_hyp_scores is None:
+            raise ValueError('mbr: nothing decoded yet (decode_many / decode_nbest / sample leave the hypotheses)')
+        if posterior is None:
+            posterior = 'uniform' if self.last_hyps_sampled else 'softmax'
+        if posterior not in ops.MBR_POSTERIORS:
+            raise ValueError("mbr: posterior must be 'softmax', 'uniform' or None, got %r" % (posterior,))
+        if unit not in ops.MBR_UNITS:
+            raise ValueError("mbr: unit must be 'char' or 'word', got %r" % (unit,))
+        chars, n_chars, n_hyps = self.last_hyps
+        N, K, steps = chars.shape
+        space, first_char = int(mapper.char_to_ind(' ')), TOKENS.index(UNK_TKN)
+        rows, lens = chars.cpu().tolist(), n_chars.cpu().tolist()
+        hmax = min(steps, max([max(max(r), 0) for r in lens] + [0]))
+        if ops.mbr_fits(K, hmax) and N <= 65535:
+            self.last_mbr = ops.mbr_select(chars[:, :, :hmax], n_chars, n_hyps, self.last_hyp_scores,
+                                           first_char=first_char, space=space, unit=unit, posterior=posterior,
+                                           scale=scale)
+            best, risk = self.last_mbr[0].cpu().tolist(), self.last_mbr[1].cpu().tolist()
+        else:
+            hyps = [[rows[i][k][:max(lens[i][k], 0)] for k in range(K)] for i in range(N)]
+            best, risk, pair = postprocess.mbr_reference(hyps, n_hyps.cpu().tolist(), self.last_hyp_scores.cpu().tolist(),
+                                                         space, first_char, unit, posterior, scale)
+            dev = chars.device
+            self.last_mbr = (torch.tensor(best, dtype=torch.int32, device=dev).reshape(N),
+                             torch.tensor(risk, dtype=torch.float32, device=dev).reshape(N, K),
+                             torch.tensor(pair, dtype=torch.int32, device=dev).reshape(N, K, K, 2))
+        out = []
+        for i, nh in enumerate(n_hyps.cpu().tolist()):
+            k = best[i]
+            text = ''.join(mapper.ind_to_char(c) for c in rows[i][k][:max(lens[i][k], 0)]) if k >= 0 else ''
+            out.append(MBR(k, text, risk[i][k] if k >= 0 else math.inf, tuple(risk[i][:min(max(nh, 0), K)])))
+        return out
+
+    def decode_mbr(self, xs, x_lens, rnn_lm, mapper, lm_weight, beam_size, max_decoding_steps=200, *, unit='word',
+                   scale=1.0, **nbest_args):
+        """decode_nbest (its keywords pass through), then mbr(unit=unit, scale=scale) over each n-best list with the
+        softmax of the hypothesis scores as the posterior: returns the N chosen strings, the entries with the lowest
+        expected error count, not the highest-scoring ones.  last_beam / last_hyps stay in the beam's order, so
+        score() afterwards still scores slot 0, the MAP entry; last_mbr[0] names the chosen slots."""
+        self.decode_nbest(xs, x_lens, rnn_lm, mapper, lm_weight, beam_size, max_decoding_steps=max_decoding_steps,
+                          **nbest_args)
+        return [m.text for m in self.mbr(mapper, unit=unit, posterior='softmax', scale=scale)]
 
     def decode_many(self, xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1,
                     ctc_weight=0.0, length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None):
@@ -573,6 +638,13 @@ class ASR(nn.Module):
                 mapper.char_to_ind(EOS_TKN), max_decoding_steps)
             self.last_hyps = (self.last_decode[0].unsqueeze(1), self.last_decode[1].unsqueeze(1),
                               torch.ones_like(self.last_decode[1]))
+            # the transcript's score as decode_nbest reports it: the chosen entries of the executed steps, <EOS>'s too
+            chars, n_chars, scores, _ = self.last_decode
+            taken = torch.gather(scores, 2, chars.long().unsqueeze(2)).squeeze(2)
+            executed = torch.clamp(n_chars + 1, max=max_decoding_steps).unsqueeze(1)
+            mask = torch.arange(chars.shape[1], device=chars.device).unsqueeze(0) < executed
+            self.last_hyp_scores = (taken * mask).sum(1, keepdim=True)
+            self.last_hyps_sampled = False
         chars, n_chars = self.last_decode[0].cpu().tolist(), self.last_decode[1].cpu().tolist()
         return [''.join(mapper.ind_to_char(c) for c in row[:n]) for row, n in zip(chars, n_chars)]
 
@@ -617,6 +689,7 @@ class ASR(nn.Module):
             else:
                 self.last_beam = ops.decode_beam(*args) if ctc is None else ops.decode_beam_ctc(*args, ctc)
             self.last_hyps = (self.last_beam[0], self.last_beam[1], self.last_beam[3])
+            self.last_hyp_scores, self.last_hyps_sampled = self.last_beam[2], False
         chars, n_chars, hyp_scores, n_hyps = [t.cpu().tolist() for t in self.last_beam]
         return [[(''.join(mapper.ind_to_char(c) for c in chars[i][k][:n_chars[i][k]]), hyp_scores[i][k])
                  for k in range(n_hyps[i])] for i in range(len(xs))]
@@ -650,6 +723,7 @@ class ASR(nn.Module):
                 rnn_lm, lm_weight, mapper.char_to_ind(EOS_TKN), max_decoding_steps, n_samples,
                 uniforms.to(device=packed.device, dtype=torch.float32), temperature)
             self.last_hyps = (self.last_samples[0], self.last_samples[1], self.last_samples[3])
-        chars, n_chars, hyp_scores = [t.cpu().tolist() for t in self.last_samples[:3]]
+            self.last_hyp_scores, self.last_hyps_sampled = self.last_samples[2], True
+        chars, n_chars, hyp_scores =[t.cpu().tolist() for t in self.last_samples[:3]]
         return [[(''.join(mapper.ind_to_char(c) for c in chars[i][k][:n_chars[i][k]]), hyp_scores[i][k])
                  for k in range(n_samples)] for i in range(len(xs))]

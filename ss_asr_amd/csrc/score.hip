@@ -14,18 +14,20 @@
 //      an equal word -- lengths, then tokens; exact, no hashing; one thread per word.
 //   3. the DP, once over the tokens and once over the word ids, by one templated routine: an anti-diagonal sweep,
 //      thread j owning reference column j.  At step d it computes cell (d - j, j) from its own value of step d - 1
-//      and thread j - 1's values of steps d - 1 and d - 2.  The neighbour's value comes by a one-lane DPP shift
-//      of the whole wave (no LDS round trip); across a wave boundary it comes through a two-slot LDS exchange and
-//      one __syncthreads() per step.  A pair whose columns fit one wave runs the sweep in wave 0 with no barrier.
+//      and thread j - 1's values of steps d - 1 and d - 2 (edit_dp.h, shared with mbr.hip).  The neighbour's value
+//      comes by a one-lane DPP shift of the whole wave (no LDS round trip); across a wave boundary it comes through
+//      a two-slot LDS exchange and one __syncthreads() per step.  A pair whose columns fit one wave runs the sweep
+//      in wave 0 with no barrier.
 // Every thread reaches every barrier: all loop bounds are the pair's lengths, which are uniform over the block.
 #include "common.h"
+#include "edit_dp.h"
 #include "../../include/ssasr.h"
 
 namespace {
 
 constexpr int SCORE_MAX_R = 1023;     // reference tokens per row, before dropping: R + 1 columns <= 1024 threads
 constexpr int SCORE_MAX_H = 8191;     // hypothesis tokens per row, before dropping
-constexpr int SCORE_MAX_WAVES = 16;
+constexpr int SCORE_MAX_WAVES = editdp::MAX_WAVES;
 
 struct ScoreArgs {
   const int32_t* hyp;
@@ -100,49 +102,14 @@ __device__ int score_words(const int32_t* tok, int off, int n, int space, int wb
   return __builtin_amdgcn_readfirstlane(nw);
 }
 
-// lane l's value <- lane l - 1's, over the whole wave; lane 0 gets 0 (DPP wave_shr:1)
-__device__ __forceinline__ uint32_t lane_shr1(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false);
-}
-
-// The packed cell (H, R) of hyp[0 .. H) against ref[0 .. R), valid in thread R (R + 1 <= blockDim.x).
+// The packed cell (H, R) of hyp[0 .. H) against ref[0 .. R), valid in thread R (R + 1 <= blockDim.x): editdp::sweep
+// over the block's columns, with the barrier when they span more than one wave, else in wave 0 alone.
 template <typename T>
 __device__ uint32_t score_dp(const T* ref, int R, const T* hyp, int H, uint32_t (*xch)[SCORE_MAX_WAVES]) {
-  const int j = threadIdx.x, lane = j & 63, wave = j >> 6;
-  const bool multi = R >= 64;                 // uniform: the pair's columns span more than one wave
-  uint32_t mine = 0;                          // step 0: cell (0, 0) = 0 in thread 0
-  if (multi || wave == 0) {
-    uint32_t left1 = 0, left2 = 0;
-    const T rt = ref[j >= 1 && j <= R ? j - 1 : 0];
-    const int hlast = H > 0 ? H - 1 : 0;
-    if (multi) {
-      if (lane == 63) xch[0][wave] = mine;
-      __syncthreads();
-    }
-    T hn = hyp[min(max(-j, 0), hlast)];       // hyp[i - 1] of step 1
-    const int steps = H + R;
-    for (int d = 1; d <= steps; ++d) {
-      uint32_t in = lane_shr1(mine);
-      if (multi && lane == 0 && wave > 0) in = xch[(d - 1) & 1][wave - 1];
-      left2 = left1;
-      left1 = in;
-      const T hc = hn;
-      const int i = d - j;
-      hn = hyp[min(max(i, 0), hlast)];        // the next step's token, loaded a step ahead
-      if (j <= R && i >= 0 && i <= H) {
-        uint32_t v;
-        if (j == 0) v = (uint32_t)i << 16;
-        else if (i == 0) v = (uint32_t)j << 16;
-        else v = min(min(left2 + (hc != rt ? 0x10001u : 0u), mine + 0x10000u), left1 + 0x10000u);
-        mine = v;
-      }
-      if (multi) {
-        if (lane == 63) xch[d & 1][wave] = mine;
-        __syncthreads();
-      }
-    }
-  }
-  return mine;
+  const int j = threadIdx.x, wave = j >> 6;
+  if (R >= 64) return editdp::sweep<T, true>(ref, R, hyp, H, j, H + R, xch, wave, wave > 0);    // uniform
+  if (wave == 0) return editdp::sweep<T, false>(ref, R, hyp, H, j, H + R, xch, 0, false);
+  return 0;
 }
 
 // S, D, I, N from the last cell

@@ -5,6 +5,7 @@ libssasr_hip.so.  There is no CPU implementation: calling these with CPU
 tensors, or without the shared object, raises.
 """
 import ctypes as C
+import math
 import os
 import weakref
 
@@ -1072,6 +1073,70 @@ def edit_score(hyp, hyp_lens, ref, ref_lens, ref_of=None, *, first_char=2, space
                                _p(ref_of), P, hmax, rmax, int(first_char), int(space), _p(out), _stream()),
           'ssasr_edit_score')
     return out
+
+
+MBR_MAX_HYPS = 32              # ssasr_mbr_select's limits: hypotheses per utterance, tokens per row before dropping,
+MBR_MAX_LEN = 1023             # and the two multiplied
+MBR_MAX_TOKENS = 8192
+MBR_UNITS = {'char': 0, 'word': 1}
+MBR_POSTERIORS = {'softmax': 0, 'uniform': 1}
+
+
+def mbr_fits(K, hmax):
+    """Whether ssasr_mbr_select takes K hypotheses per utterance of at most hmax tokens each."""
+    return 1 <= K <= MBR_MAX_HYPS and 0 <= hmax <= MBR_MAX_LEN and K * hmax <= MBR_MAX_TOKENS
+
+
+def mbr_select(chars, n_chars, n_hyps, scores, *, first_char=2, space, unit='word', posterior='softmax', scale=1.0):
+    """ssasr_mbr_select: minimum-Bayes-risk selection over each utterance's hypotheses in one launch
+    (include/ssasr.h; postprocess.mbr_reference is its float64 restatement).  chars [N, K, Hmax] int32 with unit
+    column stride and rows in (n, k) order (the row stride is passed), n_chars [N, K] and n_hyps [N] int32, scores
+    [N, K] float32 (None with posterior 'uniform'); unit 'char' | 'word' (or 0 | 1), posterior 'softmax' | 'uniform'
+    (or 0 | 1), scale finite and >= 0.  -> (best int32 [N], risk float32 [N, K], pair int32 [N, K, K, 2]) on the
+    device.  Shapes past the kernel's limits (mbr_fits) raise ValueError."""
+    lib = _lib.load()
+    _need_gpu(chars, n_chars, n_hyps, scores)
+    unit = MBR_UNITS.get(unit, unit)
+    if unit not in (0, 1):
+        raise ValueError("mbr_select: unit must be 'char' or 'word', got %r" % (unit,))
+    posterior = MBR_POSTERIORS.get(posterior, posterior)
+    if posterior not in (0, 1):
+        raise ValueError("mbr_select: posterior must be 'softmax' or 'uniform', got %r" % (posterior,))
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale >= 0.0):
+        raise ValueError('mbr_select: scale must be finite and >= 0, got %r' % (scale,))
+    if chars.dtype != torch.int32 or chars.dim() != 3:
+        raise TypeError('mbr_select: chars must be an int32 tensor [N, K, Hmax]')
+    N, K, hmax = chars.shape
+    hyp_ld = chars.stride(1) if N * K > 1 else max(hmax, 1)
+    if ((hmax > 1 and chars.stride(2) != 1) or (N * K > 1 and hyp_ld < hmax) or
+            (N > 1 and K > 0 and chars.stride(0) != K * hyp_ld)):
+        raise TypeError('mbr_select: chars must have unit column stride and equally spaced, disjoint rows')
+    for name, t, shape in (('n_chars', n_chars, (N, K)), ('n_hyps', n_hyps, (N,))):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise TypeError('mbr_select: %s must be a contiguous int32 tensor' % name)
+        if tuple(t.shape) != shape:
+            raise ValueError('mbr_select: %s must be %r, got %r' % (name, shape, tuple(t.shape)))
+    if posterior == 0:
+        if scores is None:
+            raise ValueError("mbr_select: posterior 'softmax' needs the scores")
+        if scores.dtype != torch.float32 or not scores.is_contiguous():
+            raise TypeError('mbr_select: scores must be a contiguous float32 tensor')
+        if tuple(scores.shape) != (N, K):
+            raise ValueError('mbr_select: scores must be %r, got %r' % ((N, K), tuple(scores.shape)))
+    else:
+        scores = None
+    if N > 65535 or not mbr_fits(K, hmax):
+        raise ValueError('mbr_select: %d utterances of %d hypotheses of %d columns exceed the kernel\'s 65535, %d, %d '
+                         '(and %d tokens per utterance)' % (N, K, hmax, MBR_MAX_HYPS, MBR_MAX_LEN, MBR_MAX_TOKENS))
+    dev = chars.device
+    best = torch.empty(N, device=dev, dtype=torch.int32)
+    risk = torch.empty(N, K, device=dev, dtype=torch.float32)
+    pair = torch.empty(N, K, K, 2, device=dev, dtype=torch.int32)
+    check(lib.ssasr_mbr_select(_p(chars), max(hyp_ld, hmax), _p(n_chars), _p(n_hyps), _p(scores), N, K, hmax,
+                               int(first_char), int(space), unit, posterior, scale, _p(best), _p(risk), _p(pair),
+                               _stream()), 'ssasr_mbr_select')
+    return best, risk, pair
 
 
 # ---------------------------------------------------------------------------

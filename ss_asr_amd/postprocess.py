@@ -123,6 +123,72 @@ def mwer_reference(logits, rows, n_hyps, counts, unit, ce_w=None, *, posterior='
     return loss, risk, p_hat.reshape(R)
 
 
+def edit_total(a, b):
+    """S + D + I of edit_ops(a, b), the plain edit distance.  A common prefix and a common suffix are cut first: the
+    distance (not the split into S, D, I) is unchanged by that, and the entries of an n-best list share most of
+    their length."""
+    lo, n = 0, min(len(a), len(b))
+    while lo < n and a[lo] == b[lo]:
+        lo += 1
+    hi = 0
+    while hi < n - lo and a[len(a) - 1 - hi] == b[len(b) - 1 - hi]:
+        hi += 1
+    return sum(edit_ops(a[lo:len(a) - hi], b[lo:len(b) - hi]))
+
+
+def mbr_reference(hyps, n_hyps, scores, space, first_char=2, unit='word', posterior='softmax', scale=1.0):
+    """BUILD-DEFINED: minimum-Bayes-risk selection, ssasr_mbr_select (include/ssasr.h) restated in pure Python /
+    float64 on top of edit_ops and score_sequences -- what the kernel is defined and tested against, and ASR.mbr's
+    path for groups past the kernel's limits.
+    hyps[n][k]: the token ids of hypothesis k of utterance n, already cut to its length (every utterance has the same
+    number K of rows); n_hyps[n]: the set S_n is the rows k < clamp(n_hyps[n], 0, K); scores[n][k] (None with
+    posterior 'uniform'); unit 'char' | 'word' (or 0 | 1); posterior 'softmax' | 'uniform' (or 0 | 1).
+      pair[n][k][j] = [character, word] S + D + I of hypothesis k against hypothesis j, -1 outside the set;
+      p_j = exp(x_j - LSE x) over the finite x_j = scale * score_j (0 for a non-finite one; uniform if none is
+      finite), or 1 / |S_n|;  risk[n][k] = sum_j p_j pair[n][k][j][unit] in the order j = 0 .. K - 1, inf outside the
+      set;  best[n] = the lowest k of minimal risk, -1 for an empty set.
+    -> (best [N], risk [N][K], pair [N][K][K][2]) as lists."""
+    unit = {'char': 0, 'word': 1}.get(unit, unit)
+    if unit not in (0, 1):
+        raise ValueError("mbr_reference: unit must be 'char' or 'word', got %r" % (unit,))
+    posterior = {'softmax': 0, 'uniform': 1}.get(posterior, posterior)
+    if posterior not in (0, 1):
+        raise ValueError("mbr_reference: posterior must be 'softmax' or 'uniform', got %r" % (posterior,))
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale >= 0.0):
+        raise ValueError('mbr_reference: scale must be finite and >= 0, got %r' % (scale,))
+    best, risks, pairs = [], [], []
+    for n, rows in enumerate(hyps):
+        K = len(rows)
+        nh = min(max(int(n_hyps[n]), 0), K)
+        seqs = [score_sequences(rows[k], space, first_char) for k in range(nh)]
+        pair = [[[-1, -1] for _ in range(K)] for _ in range(K)]
+        for k in range(nh):
+            pair[k][k] = [0, 0]
+            for j in range(k):
+                pair[k][j] = pair[j][k] = [edit_total(seqs[k][u], seqs[j][u]) for u in (0, 1)]
+        p = [1.0 / nh] * nh if nh else []
+        if posterior == 0 and nh:
+            with np.errstate(all='ignore'):     # inf * 0 is the non-finite entry the definition names
+                # the entry takes scale and scores as floats; the product is formed in double
+                x = [float(np.float64(np.float32(scale)) * np.float64(np.float32(scores[n][k]))) for k in range(nh)]
+            finite = [v for v in x if math.isfinite(v)]
+            if finite:
+                m = max(finite)
+                lse = m + math.log(sum(math.exp(v - m) for v in x if math.isfinite(v)))
+                p = [math.exp(v - lse) if math.isfinite(v) else 0.0 for v in x]
+        risk = [math.inf] * K
+        for k in range(nh):
+            acc = 0.0
+            for j in range(nh):
+                acc = acc + p[j] * float(pair[k][j][unit])
+            risk[k] = acc
+        best.append(min(range(nh), key=lambda k: (risk[k], k)) if nh else -1)
+        risks.append(risk)
+        pairs.append(pair)
+    return best, risks, pairs
+
+
 class ErrorStats:
     """Corpus-level error rates: sums (S, D, I, N) rows of characters and of words; cer / wer =
     sum(S + D + I) / sum(N), nan when N == 0.  (calc_err below stays the reference's mean of per-utterance ratios.)"""

@@ -602,7 +602,15 @@ class ASRTester(Solver):
     asr.Score per utterance in index order and `last_error_rates` the corpus-level {'cer', 'wer', 'oracle_cer',
     'oracle_wer', 'chars': (S, D, I, N), 'words': (S, D, I, N)} (postprocess.ErrorStats: summed errors over summed
     reference lengths; oracle_*: of each n-best list's entry with the fewest word errors), printed as one verbose
-    line."""
+    line.
+    asr.decode_mbr: {unit: word, scale: 1.0} (absent: off; unit 'word' | 'char', scale finite and >= 0, both
+    optional; needs decode_beam_size >= 2, else set_model raises): every decoded group's written transcript is the
+    minimum-Bayes-risk choice of its n-best list (ASR.mbr, ssasr_mbr_select: the entry with the lowest expected error
+    count under the softmax of scale * the hypothesis scores) instead of its first entry; `decode_file` gains
+    `_mbr<unit>` and `last_mbr_choices` holds the chosen slot per utterance in index order.  With asr.decode_score on,
+    `last_scores` keeps scoring slot 0 and `last_error_rates` gains 'mbr_cer' / 'mbr_wer', the corpus-level rates of
+    the chosen slots (read from the scorer's per-hypothesis rows, no second launch); an align then aligns the chosen
+    transcripts."""
     decode_group = 32
     TERM_KEYS = ('decode_length_bonus', 'decode_coverage_weight', 'decode_coverage_threshold', 'decode_end_margin')
 
@@ -634,6 +642,28 @@ class ASRTester(Solver):
             kw['end_margin'] = vals['decode_end_margin']
             suffix += '_end{:}'.format(vals['decode_end_margin'])
         return kw, suffix
+
+    @staticmethod
+    def mbr_args(asr_config):
+        """ASR.mbr's keywords from asr.decode_mbr, validated; None when the key is absent (or false)."""
+        import math
+        conf = asr_config.get('decode_mbr')
+        if conf is None or conf is False:
+            return None
+        if conf is True:
+            conf = {}
+        if not isinstance(conf, dict) or set(conf) - {'unit', 'scale'}:
+            raise ValueError('asr.decode_mbr must be a mapping with the keys unit and scale, got {!r}'.format(conf))
+        unit, scale = conf.get('unit', 'word'), conf.get('scale', 1.0)
+        if unit not in ('word', 'char'):
+            raise ValueError("asr.decode_mbr.unit must be 'word' or 'char', got {!r}".format(unit))
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale) or scale < 0:
+            raise ValueError('asr.decode_mbr.scale must be a finite number >= 0, got {!r}'.format(scale))
+        beam = asr_config.get('decode_beam_size')
+        if isinstance(beam, bool) or not isinstance(beam, int) or beam < 2:
+            raise ValueError('asr.decode_mbr chooses among an n-best list: asr.decode_beam_size must be >= 2, '
+                             'got {!r}'.format(beam))
+        return {'unit': unit, 'scale': float(scale)}
 
     def __init__(self, config, paras):
         super().__init__(config, paras, 'asr')
@@ -681,6 +711,9 @@ class ASRTester(Solver):
         self.decode_file += suffix
         if self.decode_align:
             self.decode_file += '_align'
+        self.decode_mbr = self.mbr_args(self.config['asr'])
+        if self.decode_mbr is not None:
+            self.decode_file += '_mbr{}'.format(self.decode_mbr['unit'])
 
     def exec(self, lm_weight=None):
         """-> the decoded strings, one per utterance of the test index, in index order."""
@@ -703,14 +736,24 @@ class ASRTester(Solver):
             self.last_alignments = []
         if self.decode_score:
             self.last_scores = []
+        mbr_stats = ErrorStats()
+        if self.decode_mbr is not None:
+            self.last_mbr_choices = []
 
         def flush():
             if xs:
                 texts = self.asr_model.decode_many(xs, x_lens, self.lm, self.mapper, lm_weight,
                                                    beam_size=beam, ctc_weight=ctc_weight, **terms)
+                if self.decode_mbr is not None:  # the n-best lists are still on the device: one launch for the group
+                    chosen = self.asr_model.mbr(self.mapper, posterior='softmax', **self.decode_mbr)
+                    texts = [m.text for m in chosen]
+                    self.last_mbr_choices.extend(m.k for m in chosen)
                 results.extend(texts)
                 if self.decode_score:            # the hypotheses are still on the device: one launch for the group
                     self.last_scores.extend(self.asr_model.score(ys, self.mapper))
+                    if self.decode_mbr is not None:
+                        for rows, m in zip(self.asr_model.last_score_rows, chosen):
+                            mbr_stats.add(rows[max(m.k, 0)][:4], rows[max(m.k, 0)][4:])
                 if self.decode_align:            # on the group's encoder outputs: no second encode
                     self.last_alignments.extend(self.asr_model.align(
                         xs, x_lens, texts, self.mapper, encoded=self.asr_model.last_encoded_packed))
@@ -733,6 +776,10 @@ class ASRTester(Solver):
                 oracle.add(sc.oracle[1], sc.oracle[2])
             self.last_error_rates = {'cer': best.cer, 'wer': best.wer, 'oracle_cer': oracle.cer,
                                      'oracle_wer': oracle.wer, 'chars': tuple(best.chars), 'words': tuple(best.words)}
+            if self.decode_mbr is not None:
+                self.last_error_rates.update(mbr_cer=mbr_stats.cer, mbr_wer=mbr_stats.wer)
+                self.verbose('MBR choice ({}s, scale {}): CER {:.4f} WER {:.4f}'.format(
+                    self.decode_mbr['unit'], self.decode_mbr['scale'], mbr_stats.cer, mbr_stats.wer))
             self.verbose('CER {:.4f} WER {:.4f} (oracle CER {:.4f} WER {:.4f}); characters S/D/I/N {}/{}/{}/{}, '
                          'words S/D/I/N {}/{}/{}/{}'.format(best.cer, best.wer, oracle.cer, oracle.wer,
                                                             *(best.chars + best.words)))

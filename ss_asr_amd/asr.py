@@ -622,38 +622,38 @@ class ASR(nn.Module):
         hyp_scores [N, K], n_hyps [N]) on the device in last_beam; last_decode is left as it was.
         ctc_weight > 0, or a length bonus, a coverage term or end detection on: as beam_size > 1, for any beam_size
         in 1..32 (decode_nbest)."""
-        terms = self._beam_terms(length_bonus, coverage_weight, coverage_threshold, end_margin)
-        if beam_size != 1 or self._ctc_head(ctc_weight) is not None or terms is not None:
-            return [nbest[0][0] for nbest in self.decode_nbest(xs, x_lens, rnn_lm, mapper, lm_weight, beam_size,
-                                                               max_decoding_steps=max_decoding_steps,
-                                                               ctc_weight=ctc_weight, length_bonus=length_bonus,
-                                                               coverage_weight=coverage_weight,
-                                                               coverage_threshold=coverage_threshold,
-                                                               end_margin=end_margin)]
-        with torch.no_grad():
-            packed, enc_lens = self._encode_packed(xs, x_lens)
-            self.last_decode = ops.decode_greedy(
-                packed, enc_lens, self._decoder_params(),
-                (self.attention.psi.weight, self.attention.psi.bias), rnn_lm, lm_weight,
-                mapper.char_to_ind(EOS_TKN), max_decoding_steps)
-            self.last_hyps = (self.last_decode[0].unsqueeze(1), self.last_decode[1].unsqueeze(1),
-                              torch.ones_like(self.last_decode[1]))
-            # the transcript's score as decode_nbest reports it: the chosen entries of the executed steps, <EOS>'s too
-            chars, n_chars, scores, _ = self.last_decode
-            taken = torch.gather(scores, 2, chars.long().unsqueeze(2)).squeeze(2)
-            executed = torch.clamp(n_chars + 1, max=max_decoding_steps).unsqueeze(1)
-            mask = torch.arange(chars.shape[1], device=chars.device).unsqueeze(0) < executed
-            self.last_hyp_scores = (taken * mask).sum(1, keepdim=True)
-            self.last_hyps_sampled = False
-        chars, n_chars = self.last_decode[0].cpu().tolist(), self.last_decode[1].cpu().tolist()
-        return [''.join(mapper.ind_to_char(c) for c in row[:n]) for row, n in zip(chars, n_chars)]
+        nbest = self.decode_nbest(xs, x_lens, rnn_lm, mapper, lm_weight, beam_size,
+                                  max_decoding_steps=max_decoding_steps, ctc_weight=ctc_weight,
+                                  length_bonus=length_bonus, coverage_weight=coverage_weight,
+                                  coverage_threshold=coverage_threshold, end_margin=end_margin)
+        return [hyps[0][0] for hyps in nbest]
+
+    def _decode_args(self, packed, enc_lens, lm, lm_weight, mapper_or_eos, max_steps):
+        """What every decode entry of ops takes first: the encoded group, the decoder's and psi's parameters, the
+        language model and its weight, <EOS> (an index, or the mapper that knows it) and the step cap."""
+        eos = mapper_or_eos if isinstance(mapper_or_eos, int) else mapper_or_eos.char_to_ind(EOS_TKN)
+        return (packed, enc_lens, self._decoder_params(), (self.attention.psi.weight, self.attention.psi.bias), lm,
+                lm_weight, eos, max_steps)
+
+    def _keep_hyps(self, chars, n_chars, n_hyps, scores, sampled):
+        """What score() and mbr() read: the last call's hypotheses [N, K, steps], [N, K], [N] and scores [N, K]."""
+        self.last_hyps = (chars, n_chars, n_hyps)
+        self.last_hyp_scores, self.last_hyps_sampled = scores, sampled
+
+    @staticmethod
+    def _texts(chars, n_chars, n_hyps, scores, mapper):
+        """Per utterance the list of (text, score) of its first n_hyps[i] (a tensor [N], or one count for all) slots."""
+        chars, n_chars, scores = [t.cpu().tolist() for t in (chars, n_chars, scores)]
+        n_hyps = [n_hyps] * len(chars) if isinstance(n_hyps, int) else n_hyps.cpu().tolist()
+        return [[(''.join(mapper.ind_to_char(c) for c in chars[i][k][:n_chars[i][k]]), scores[i][k])
+                 for k in range(n_hyps[i])] for i in range(len(chars))]
 
     def decode_nbest(self, xs, x_lens, rnn_lm, mapper, lm_weight, beam_size, max_decoding_steps=200, *,
                      ctc_weight=0.0, length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None):
         """Beam search over a list of single utterances in ONE launch: per utterance the list of (text, score),
         best first, score = the sum of the chosen characters' log_softmax(speller) + lm_weight *
         log_softmax(rnn_lm) entries (<EOS>'s included when it ended the hypothesis; no length normalisation).
-        beam_size 1 is greedy decoding (decode_many, last_decode); beam_size 2 .. 32 sets last_beam.
+        beam_size 1 is greedy decoding (ssasr_decode_greedy, last_decode); beam_size 2 .. 32 sets last_beam.
         ctc_weight in (0, 1] (a model with a ctc_head): joint CTC / attention decoding, ssasr_decode_beam_ctc for
         any beam_size in 1..32 (width 1 is the beam kernel at K = 1); a character's score entry is then
         (1 - ctc_weight) * log_softmax(speller) + ctc_weight * (the CTC prefix score's increase) + lm_weight *
@@ -671,28 +671,28 @@ class ASR(nn.Module):
             raise ValueError('beam_size must be in 1..%d, got %d' % (ops.MAX_BEAM, beam_size))
         ctc = self._ctc_head(ctc_weight)
         terms = self._beam_terms(length_bonus, coverage_weight, coverage_threshold, end_margin)
-        if beam_size == 1 and ctc is None and terms is None:
-            texts = self.decode_many(xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=max_decoding_steps)
-            chars, n_chars, scores, _ = self.last_decode
-            steps = torch.clamp(n_chars + 1, max=max_decoding_steps)            # executed steps: <EOS>'s too
-            taken = torch.gather(scores, 2, chars.long().unsqueeze(2)).squeeze(2)
-            mask = torch.arange(chars.shape[1], device=chars.device).unsqueeze(0) < steps.unsqueeze(1)
-            totals = (taken * mask).sum(1).cpu().tolist()
-            return [[(t, s)] for t, s in zip(texts, totals)]
         with torch.no_grad():
             packed, enc_lens = self._encode_packed(xs, x_lens)
-            args = (packed, enc_lens, self._decoder_params(), (self.attention.psi.weight, self.attention.psi.bias),
-                    rnn_lm, lm_weight, mapper.char_to_ind(EOS_TKN), max_decoding_steps, beam_size)
-            if terms is not None:
-                out = ops.decode_beam_ex(*args, ctc, **terms)
-                self.last_beam, self.last_beam_steps = out[:4], out[4]
+            args = self._decode_args(packed, enc_lens, rnn_lm, lm_weight, mapper, max_decoding_steps)
+            if beam_size == 1 and ctc is None and terms is None:
+                self.last_decode = ops.decode_greedy(*args)
+                chars, n_chars, scores, _ = self.last_decode
+                # the transcript's score: the chosen entries of the executed steps, <EOS>'s too
+                taken = torch.gather(scores, 2, chars.long().unsqueeze(2)).squeeze(2)
+                executed = torch.clamp(n_chars + 1, max=max_decoding_steps).unsqueeze(1)
+                mask = torch.arange(chars.shape[1], device=chars.device).unsqueeze(0) < executed
+                hyps = (chars.unsqueeze(1), n_chars.unsqueeze(1), torch.ones_like(n_chars),
+                        (taken * mask).sum(1, keepdim=True))
             else:
-                self.last_beam = ops.decode_beam(*args) if ctc is None else ops.decode_beam_ctc(*args, ctc)
-            self.last_hyps = (self.last_beam[0], self.last_beam[1], self.last_beam[3])
-            self.last_hyp_scores, self.last_hyps_sampled = self.last_beam[2], False
-        chars, n_chars, hyp_scores, n_hyps = [t.cpu().tolist() for t in self.last_beam]
-        return [[(''.join(mapper.ind_to_char(c) for c in chars[i][k][:n_chars[i][k]]), hyp_scores[i][k])
-                 for k in range(n_hyps[i])] for i in range(len(xs))]
+                if terms is not None:
+                    out = ops.decode_beam_ex(*args, beam_size, ctc, **terms)
+                    self.last_beam, self.last_beam_steps = out[:4], out[4]
+                else:
+                    self.last_beam = (ops.decode_beam(*args, beam_size) if ctc is None else
+                                      ops.decode_beam_ctc(*args, beam_size, ctc))
+                hyps = (self.last_beam[0], self.last_beam[1], self.last_beam[3], self.last_beam[2])
+            self._keep_hyps(*hyps, sampled=False)
+        return self._texts(*hyps, mapper)
 
     def sample(self, xs, x_lens, mapper, n_samples, *, temperature=1.0, rnn_lm=None, lm_weight=0.0,
                max_decoding_steps=200, generator=None, uniforms=None):
@@ -719,11 +719,8 @@ class ASR(nn.Module):
             elif tuple(uniforms.shape) != shape:
                 raise ValueError('sample: uniforms must be %r, got %r' % (shape, tuple(uniforms.shape)))
             self.last_samples = ops.decode_sample(
-                packed, enc_lens, self._decoder_params(), (self.attention.psi.weight, self.attention.psi.bias),
-                rnn_lm, lm_weight, mapper.char_to_ind(EOS_TKN), max_decoding_steps, n_samples,
+                *self._decode_args(packed, enc_lens, rnn_lm, lm_weight, mapper, max_decoding_steps), n_samples,
                 uniforms.to(device=packed.device, dtype=torch.float32), temperature)
-            self.last_hyps = (self.last_samples[0], self.last_samples[1], self.last_samples[3])
-            self.last_hyp_scores, self.last_hyps_sampled = self.last_samples[2], True
-        chars, n_chars, hyp_scores =[t.cpu().tolist() for t in self.last_samples[:3]]
-        return [[(''.join(mapper.ind_to_char(c) for c in chars[i][k][:n_chars[i][k]]), hyp_scores[i][k])
-                 for k in range(n_samples)] for i in range(len(xs))]
+            chars, n_chars, hyp_scores, n_hyps, _ = self.last_samples
+            self._keep_hyps(chars, n_chars, n_hyps, hyp_scores, sampled=True)
+        return self._texts(chars, n_chars, n_samples, hyp_scores, mapper)

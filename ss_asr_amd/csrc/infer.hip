@@ -16,9 +16,12 @@
 // The four kernels are built from one set of step helpers, each over n hypotheses whose rows lie a stride apart
 // (the greedy kernel and the CharLM step pass n = 1): matmat_n / matvec / matmat (weight rows x input vectors, comp =
 // tanh(psi(feat)) included), lstm_update, gru_update, context_partial + context_reduce (att . feat) and score_row
-// (log_softmax(asr) + lm_weight * log_softmax(lm)).  Per kernel: where the state lives, the softmax over the frames
-// (block-wide / a wave per hypothesis: different summation orders) and what follows the score row (the arg-max /
-// the beam's selection, back-pointers and output / the sampler's draw).
+// (log_softmax(asr) + lm_weight * log_softmax(lm)).  The two K-hypothesis kernels also share the SEQUENCE that calls
+// them: decode_prologue (comp, zero states, <SOS>) and speller_step (phases 1 to 7, barriers included) over a StepWs;
+// what follows the score rows is theirs (the beam's selection, back-pointers and output / the sampler's draw).
+// decode_greedy_kernel and charlm_step_kernel keep bodies of their own: state in LDS behind __syncthreads() alone, a
+// block-wide softmax over the frames (another summation order than a wave per hypothesis) and a comp prologue shaped
+// to stay out of scratch memory.
 #include <cmath>
 #include "../../include/ssasr.h"
 #include "common.h"
@@ -492,6 +495,87 @@ __device__ __forceinline__ float wave_exp_row(float* row, int len) {
   }
   return wave_sum(sum);
 }
+__device__ __forceinline__ void normalise_row(float* row, float sum, int len) {
+  for (int t = (threadIdx.x & 63); t < len; t += 64) row[t] = row[t] / sum;
+}
+
+// one utterance's blocks of a BeamWs slice that a step reads and writes, K slots each, and the strides between slots
+struct StepWs {
+  float *xin, *lmx, *q, *gates, *en, *part, *gi, *gh, *lg, *lmlg;
+  int K, Sz, Tp, G, XI;
+};
+__device__ __forceinline__ StepWs step_ws(const BeamWs& m, float* ws, int K, int XI) {
+  return StepWs{ws + m.xin, ws + m.lmx, ws + m.q, ws + m.gates, ws + m.en, ws + m.part, ws + m.gi, ws + m.gh,
+                ws + m.lg, ws + m.lmlg, K, m.Sz, m.Tp, m.G, XI};
+}
+
+// Before the loop: comp = tanh(psi(feat)) for this utterance's frames, once, shared by every slot (W_psi against the
+// frames as vectors); slots 0 .. n - 1 of st: zero states, <SOS> = 0 as the input character.  No barrier.
+__device__ __forceinline__ void decode_prologue(const InferDev& p, const StepWs& w, const float* feat, float* comp,
+                                                int len, float* st, int n) {
+  const int tid = threadIdx.x, D = p.D, Hl = p.lm.H;
+  matmat(p.w_psi, p.E, feat, p.E, p.E, nullptr, 0, nullptr, 0, 0, p.b_psi, nullptr, p.A, 1, comp, p.A, len);
+  for (int i = tid; i < n * w.Sz; i += kThreads) st[i] = 0.f;
+  for (int i = tid; i < n * D; i += kThreads) w.xin[(int64_t)(i / D) * w.XI + i % D] = p.embed[i % D];
+  for (int i = tid; i < n * Hl; i += kThreads) w.lmx[i] = p.lm.emb[i % Hl];
+}
+
+// Phases 1 to 7 of one step for slots 0 .. n - 1 of the state rows st (w.Sz floats apart), up to and including the
+// phase_sync() after char_trans: w.lg / w.lmlg hold the slots' logit rows.  att_row(b, row, sum) is called by the wave
+// that owns slot b once row holds exp(energy - max) and sum their sum: it leaves the attention weights in row
+// (normalise_row; the beam search's coverage form counts in the same pass).
+template <class AttRow>
+__device__ __forceinline__ void speller_step(const InferDev& p, const StepWs& w, const float* feat, const float* comp,
+                                             int len, float* st, int n, AttRow att_row) {
+  const int wave = threadIdx.x >> 6;
+  const int E = p.E, A = p.A, D = p.D, V = p.V, Hl = p.lm.H, K = w.K, Sz = w.Sz, Tp = w.Tp, G = w.G, XI = w.XI;
+  float *h1 = st, *c1 = st + D, *h2 = st + 2 * D, *c2 = st + 3 * D, *lmh1 = st + 4 * D, *lmh2 = lmh1 + Hl;
+  float *xin = w.xin, *lmx = w.lmx, *q = w.q, *gates = w.gates, *en = w.en, *part = w.part, *gi = w.gi, *gh = w.gh;
+  // 1: q = tanh(phi(h1)) | LM layer 1 products
+  matmat(p.w_phi, D, h1, Sz, D, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, A, 1, q, A, n);
+  if (Hl) {
+    matmat(p.lm.w_ih1, Hl, lmx, Hl, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_ih1, nullptr, 3 * Hl, 0, gi, 3 * Hl, n);
+    matmat(p.lm.w_hh1, Hl, lmh1, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_hh1, nullptr, 3 * Hl, 0, gh, 3 * Hl, n);
+  }
+  phase_sync();
+  // 2: energies over the utterance's frames | LM layer 1 update
+  gru_update(gi, gh, 3 * Hl, lmh1, Sz, Hl, n);
+  matmat(comp, A, q, A, A, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, len, 0, en, Tp, n);
+  phase_sync();
+  // 3: softmax over the frames, a wave per slot (decode_greedy_kernel's is block-wide) | LM layer 2 products
+  for (int b = wave; b < n; b += kWaves) {
+    float* row = en + (int64_t)b * Tp;
+    const float sum = wave_exp_row(row, len);
+    att_row(b, row, sum);
+  }
+  if (Hl) {
+    matmat(p.lm.w_ih2, Hl, lmh1, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_ih2, nullptr, 3 * Hl, 0, gi, 3 * Hl, n);
+    matmat(p.lm.w_hh2, Hl, lmh2, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_hh2, nullptr, 3 * Hl, 0, gh, 3 * Hl, n);
+  }
+  phase_sync();
+  // 4: context = att . feat, partial sums in the workspace at [g][K][E] | LM layer 2 update
+  context_partial<kHyps>(feat, E, len, G, en, Tp, n, G == 1 ? xin + D : part, (int64_t)K * E, G == 1 ? XI : E);
+  gru_update(gi, gh, 3 * Hl, lmh2, Sz, Hl, n);
+  phase_sync();
+  if (G > 1) {
+    context_reduce(part, (int64_t)K * E, E, G, xin + D, XI, E, n);
+    phase_sync();
+  }
+  // 5: Speller cell 1 on [embedding | context] | LM output layer
+  matmat(p.w_ih1, XI, xin, XI, XI, p.w_hh1, D, h1, Sz, D, p.b_ih1, p.b_hh1, 4 * D, 0, gates, 4 * D, n);
+  if (Hl) matmat(p.lm.w_out, Hl, lmh2, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_out, nullptr, V, 0, w.lmlg, 64, n);
+  phase_sync();
+  lstm_update(gates, 4 * D, h1, c1, Sz, D, n);
+  phase_sync();
+  // 6: cell 2
+  matmat(p.w_ih2, D, h1, Sz, D, p.w_hh2, D, h2, Sz, D, p.b_ih2, p.b_hh2, 4 * D, 0, gates, 4 * D, n);
+  phase_sync();
+  lstm_update(gates, 4 * D, h2, c2, Sz, D, n);
+  phase_sync();
+  // 7: char_trans
+  matmat(p.w_ct, D, h2, Sz, D, nullptr, 0, nullptr, 0, 0, p.b_ct, nullptr, V, 0, w.lg, 64, n);
+  phase_sync();
+}
 
 struct BeamDev {
   InferDev in;                            // in.chars [N][K][S], in.n_chars [N][K]; in.scores / in.att unused
@@ -544,6 +628,12 @@ struct TermsDev {
 
 // floats of one utterance's coverage block: cum, 2 buffers x K rows of up4(T)
 __host__ __device__ inline int64_t cov_ws_floats(const BeamWs& m, int K) { return 2 * (int64_t)K * m.Tp; }
+
+// floats of one utterance's slice of the beam search's workspace: the plain or the CTC form's blocks, then the coverage
+// block.  The kernel's slice stride and the three size queries.
+__host__ __device__ inline int64_t beam_slice_floats(const BeamWs& m, int K, int T, bool ctc, bool cover) {
+  return (ctc ? ctc_ws_map(m, K, T).total : m.total) + (cover ? cov_ws_floats(m, K) : 0);
+}
 
 constexpr int kCtcAhead = 4;              // frames whose loads a lattice loop issues before it needs the first
 
@@ -659,13 +749,10 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
   const BeamWs m = beam_ws_map(K, T, E, A, D, Hl, S);
   const CtcWs cm = ctc_ws_map(m, K, T);
   const bool cover = TERMS && td.eta != 0.f;
-  int64_t slice = CTC ? cm.total : m.total;
-  if constexpr (TERMS) slice += cover ? cov_ws_floats(m, K) : 0;
-  float* ws = bd.ws + (int64_t)n * slice;
-  float *xin = ws + m.xin, *lmx = ws + m.lmx, *q = ws + m.q, *gates = ws + m.gates, *en = ws + m.en,
-        *part = ws + m.part, *gi = ws + m.gi, *gh = ws + m.gh, *lg = ws + m.lg, *lmlg = ws + m.lmlg;
+  float* ws = bd.ws + (int64_t)n * beam_slice_floats(m, K, T, CTC, cover);
+  const StepWs w = step_ws(m, ws, K, D + E);
   int32_t* bp = reinterpret_cast<int32_t*>(ws + m.bp);
-  const int Sz = m.Sz, Tp = m.Tp, G = m.G, XI = D + E;
+  const int Sz = w.Sz, Tp = w.Tp, XI = w.XI;
 
   const int len = min(max(p.enc_len[n], 1), T);      // frames this utterance attends over
   const float* feat = p.feat + (int64_t)n * T * E;
@@ -674,15 +761,10 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
   int32_t* n_chars = p.n_chars + (int64_t)n * K;
   float* hyp_scores = bd.hyp_scores + (int64_t)n * K;
 
-  // comp = tanh(psi(feat)) for this utterance's frames, once, shared by every hypothesis: W_psi against the
-  // frames as vectors
-  matmat(p.w_psi, E, feat, E, E, nullptr, 0, nullptr, 0, 0, p.b_psi, nullptr, A, 1, comp, A, len);
-  // one live hypothesis: zero states, score 0, <SOS> = 0 as the input character
+  // comp, and one live hypothesis: zero states, score 0, <SOS> = 0 as the input character
   float* cur = ws + m.st;
   float* nxt = cur + (int64_t)K * Sz;
-  for (int i = tid; i < Sz; i += kThreads) cur[i] = 0.f;
-  copy_row(xin, p.embed, D);
-  if (Hl) copy_row(lmx, p.lm.emb, Hl);
+  decode_prologue(p, w, feat, comp, len, cur, 1);
   if (tid == 0) score[0][0] = 0.f;
   // CTC: lp = log_softmax(ctc_head(feat)) of this utterance's frames, the head against the frames as vectors, then a
   // wave per row; the empty prefix: gamma_n = -inf, gamma_b[t] = lp[0][blank] + .. + lp[t][blank], psi = 0
@@ -726,27 +808,13 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
 
   int live = 1, nfin = 0, step = 0;
   for (; step < S && live > 0; ++step) {
-    float *h1 = cur, *c1 = cur + D, *h2 = cur + 2 * D, *c2 = cur + 3 * D, *lmh1 = cur + 4 * D, *lmh2 = lmh1 + Hl;
     const float* sc = score[step & 1];
     float* sc_new = score[(step + 1) & 1];
-    // 1: q = tanh(phi(h1)) | LM layer 1 products
-    matmat(p.w_phi, D, h1, Sz, D, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, A, 1, q, A, live);
-    if (Hl) {
-      matmat(p.lm.w_ih1, Hl, lmx, Hl, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_ih1, nullptr, 3 * Hl, 0, gi, 3 * Hl, live);
-      matmat(p.lm.w_hh1, Hl, lmh1, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_hh1, nullptr, 3 * Hl, 0, gh, 3 * Hl, live);
-    }
-    phase_sync();
-    // 2: energies over the utterance's frames | LM layer 1 update
-    gru_update(gi, gh, 3 * Hl, lmh1, Sz, Hl, live);
-    matmat(comp, A, q, A, A, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, len, 0, en, Tp, live);
-    phase_sync();
-    // 3: softmax over the frames, a wave per hypothesis (decode_greedy_kernel's is block-wide and sums in another
-    // order: the two stay apart) | LM layer 2 products
-    for (int b = wave; b < live; b += kWaves) {
-      float* row = en + (int64_t)b * Tp;
-      const float sum = wave_exp_row(row, len);
+    // 1 to 7: the step's logit rows of the live hypotheses.  Coverage: the attention row is normalised, added to the
+    // parent's cum in place and counted in one pass: cov' = frames with cum' > tau
+    speller_step(p, w, feat, comp, len, cur, live, [&](int b, float* row, float sum) {
       if constexpr (TERMS) {
-        if (cover) {                                 // cum' = cum + att in place, cov' = frames with cum' > tau
+        if (cover) {
           float* cum = ccur + (int64_t)b * Tp;
           float cnt = 0.f;                           // an integer <= 16,384: exact, whatever the order
           for (int t = lane; t < len; t += 64) {
@@ -761,38 +829,12 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
             cov_new[b] = cn;
             cov_inc[b] = td.eta * (float)(cn - cov[step & 1][b]);
           }
-          continue;
+          return;
         }
       }
-      for (int t = lane; t < len; t += 64) row[t] = row[t] / sum;
-    }
-    if (Hl) {
-      matmat(p.lm.w_ih2, Hl, lmh1, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_ih2, nullptr, 3 * Hl, 0, gi, 3 * Hl, live);
-      matmat(p.lm.w_hh2, Hl, lmh2, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_hh2, nullptr, 3 * Hl, 0, gh, 3 * Hl, live);
-    }
-    phase_sync();
-    // 4: context = att . feat, partial sums in the workspace at [g][K][E] | LM layer 2 update
-    context_partial<kHyps>(feat, E, len, G, en, Tp, live, G == 1 ? xin + D : part, (int64_t)K * E, G == 1 ? XI : E);
-    gru_update(gi, gh, 3 * Hl, lmh2, Sz, Hl, live);
-    phase_sync();
-    if (G > 1) {
-      context_reduce(part, (int64_t)K * E, E, G, xin + D, XI, E, live);
-      phase_sync();
-    }
-    // 5: Speller cell 1 on [embedding | context] | LM output layer
-    matmat(p.w_ih1, XI, xin, XI, XI, p.w_hh1, D, h1, Sz, D, p.b_ih1, p.b_hh1, 4 * D, 0, gates, 4 * D, live);
-    if (Hl) matmat(p.lm.w_out, Hl, lmh2, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_out, nullptr, V, 0, lmlg, 64, live);
-    phase_sync();
-    lstm_update(gates, 4 * D, h1, c1, Sz, D, live);
-    phase_sync();
-    // 6: cell 2
-    matmat(p.w_ih2, D, h1, Sz, D, p.w_hh2, D, h2, Sz, D, p.b_ih2, p.b_hh2, 4 * D, 0, gates, 4 * D, live);
-    phase_sync();
-    lstm_update(gates, 4 * D, h2, c2, Sz, D, live);
-    phase_sync();
-    // 7: char_trans
-    matmat(p.w_ct, D, h2, Sz, D, nullptr, 0, nullptr, 0, 0, p.b_ct, nullptr, V, 0, lg, 64, live);
-    phase_sync();
+      normalise_row(row, sum, len);
+    });
+    const float *lg = w.lg, *lmlg = w.lmlg;
     // 8: candidates score_b + log_softmax(asr) + lm_weight * log_softmax(lm), a wave per hypothesis
     if constexpr (CTC) {
       // lane v owns candidate (b, v) and runs the frame loop over its parent's lattice rows
@@ -923,11 +965,11 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
     }
     for (int i = tid; i < nl * D; i += kThreads) {
       const int j = i / D, u = i % D;
-      xin[(int64_t)j * XI + u] = p.embed[(int64_t)chr[j] * D + u];
+      w.xin[(int64_t)j * XI + u] = p.embed[(int64_t)chr[j] * D + u];
     }
     for (int i = tid; i < nl * Hl; i += kThreads) {
       const int j = i / Hl, u = i % Hl;
-      lmx[(int64_t)j * Hl + u] = p.lm.emb[(int64_t)chr[j] * Hl + u];
+      w.lmx[(int64_t)j * Hl + u] = p.lm.emb[(int64_t)chr[j] * Hl + u];
     }
     if constexpr (TERMS) {                           // and its coverage row is its parent's cum'
       if (cover) {
@@ -1011,11 +1053,7 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
 // a live slot's state rows into a hole would cost a copy phase and a slot map for the outputs; trimming to hi sheds
 // the passes that a finished tail would cost at K > kHyps.
 struct SampleDev {
-  InferDev in;                            // in.chars [N][K][S], in.n_chars [N][K]; in.scores / in.att unused
-  int K;
-  float* ws;
-  float* hyp_scores;
-  int32_t* n_hyps;
+  BeamDev b;
   const float* uniforms;                  // [N][K][S]
   float tau;
   float* logq;                            // [N][K] or nullptr
@@ -1025,15 +1063,14 @@ __global__ __launch_bounds__(kThreads) void decode_sample_kernel(SampleDev sd) {
   __shared__ int alive[kMaxBeam], chr[kMaxBeam], nch[kMaxBeam];
   __shared__ float score[kMaxBeam], logq[kMaxBeam];  // sums over the drawn characters: row[v], log q(v)
 
-  const InferDev& p = sd.in;
+  const InferDev& p = sd.b.in;
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int T = p.T, E = p.E, A = p.A, D = p.D, V = p.V, Hl = p.lm.H, K = sd.K, S = p.max_steps;
+  const int T = p.T, E = p.E, A = p.A, D = p.D, V = p.V, Hl = p.lm.H, K = sd.b.K, S = p.max_steps;
   const BeamWs m = sample_ws_map(K, T, E, A, D, Hl);
-  float* ws = sd.ws + (int64_t)n * m.total;
-  float *st = ws + m.st, *xin = ws + m.xin, *lmx = ws + m.lmx, *q = ws + m.q, *gates = ws + m.gates, *en = ws + m.en,
-        *part = ws + m.part, *gi = ws + m.gi, *gh = ws + m.gh, *lg = ws + m.lg, *lmlg = ws + m.lmlg;
-  float *h1 = st, *c1 = st + D, *h2 = st + 2 * D, *c2 = st + 3 * D, *lmh1 = st + 4 * D, *lmh2 = lmh1 + Hl;
-  const int Sz = m.Sz, Tp = m.Tp, G = m.G, XI = D + E;
+  float* ws = sd.b.ws + (int64_t)n * m.total;
+  const StepWs w = step_ws(m, ws, K, D + E);
+  float *st = ws + m.st, *lg = w.lg, *lmlg = w.lmlg;
+  const int XI = w.XI;
 
   const int len = min(max(p.enc_len[n], 1), T);      // frames this utterance attends over
   const float* feat = p.feat + (int64_t)n * T * E;
@@ -1041,11 +1078,8 @@ __global__ __launch_bounds__(kThreads) void decode_sample_kernel(SampleDev sd) {
   int32_t* chars = p.chars + (int64_t)n * K * S;
   const float* uni = sd.uniforms + (int64_t)n * K * S;
 
-  // comp = tanh(psi(feat)) once, shared by every sample; K samples: zero states, <SOS> = 0 as the input character
-  matmat(p.w_psi, E, feat, E, E, nullptr, 0, nullptr, 0, 0, p.b_psi, nullptr, A, 1, comp, A, len);
-  for (int i = tid; i < K * Sz; i += kThreads) st[i] = 0.f;
-  for (int i = tid; i < K * D; i += kThreads) xin[(int64_t)(i / D) * XI + i % D] = p.embed[i % D];
-  for (int i = tid; i < K * Hl; i += kThreads) lmx[i] = p.lm.emb[i % Hl];
+  // comp, and K samples: zero states, <SOS> = 0 as the input character
+  decode_prologue(p, w, feat, comp, len, st, K);
   for (int64_t i = tid; i < (int64_t)K * S; i += kThreads) chars[i] = 0;
   if (tid < K) {
     alive[tid] = 1;
@@ -1057,50 +1091,8 @@ __global__ __launch_bounds__(kThreads) void decode_sample_kernel(SampleDev sd) {
 
   int hi = K;                                        // one past the highest live slot
   for (int step = 0; step < S && hi > 0; ++step) {
-    // 1: q = tanh(phi(h1)) | LM layer 1 products
-    matmat(p.w_phi, D, h1, Sz, D, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, A, 1, q, A, hi);
-    if (Hl) {
-      matmat(p.lm.w_ih1, Hl, lmx, Hl, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_ih1, nullptr, 3 * Hl, 0, gi, 3 * Hl, hi);
-      matmat(p.lm.w_hh1, Hl, lmh1, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_hh1, nullptr, 3 * Hl, 0, gh, 3 * Hl, hi);
-    }
-    phase_sync();
-    // 2: energies over the utterance's frames | LM layer 1 update
-    gru_update(gi, gh, 3 * Hl, lmh1, Sz, Hl, hi);
-    matmat(comp, A, q, A, A, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, len, 0, en, Tp, hi);
-    phase_sync();
-    // 3: softmax over the frames, a wave per sample | LM layer 2 products
-    for (int b = wave; b < hi; b += kWaves) {
-      float* row = en + (int64_t)b * Tp;
-      const float sum = wave_exp_row(row, len);
-      for (int t = lane; t < len; t += 64) row[t] = row[t] / sum;
-    }
-    if (Hl) {
-      matmat(p.lm.w_ih2, Hl, lmh1, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_ih2, nullptr, 3 * Hl, 0, gi, 3 * Hl, hi);
-      matmat(p.lm.w_hh2, Hl, lmh2, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_hh2, nullptr, 3 * Hl, 0, gh, 3 * Hl, hi);
-    }
-    phase_sync();
-    // 4: context = att . feat | LM layer 2 update
-    context_partial<kHyps>(feat, E, len, G, en, Tp, hi, G == 1 ? xin + D : part, (int64_t)K * E, G == 1 ? XI : E);
-    gru_update(gi, gh, 3 * Hl, lmh2, Sz, Hl, hi);
-    phase_sync();
-    if (G > 1) {
-      context_reduce(part, (int64_t)K * E, E, G, xin + D, XI, E, hi);
-      phase_sync();
-    }
-    // 5: Speller cell 1 on [embedding | context] | LM output layer
-    matmat(p.w_ih1, XI, xin, XI, XI, p.w_hh1, D, h1, Sz, D, p.b_ih1, p.b_hh1, 4 * D, 0, gates, 4 * D, hi);
-    if (Hl) matmat(p.lm.w_out, Hl, lmh2, Sz, Hl, nullptr, 0, nullptr, 0, 0, p.lm.b_out, nullptr, V, 0, lmlg, 64, hi);
-    phase_sync();
-    lstm_update(gates, 4 * D, h1, c1, Sz, D, hi);
-    phase_sync();
-    // 6: cell 2
-    matmat(p.w_ih2, D, h1, Sz, D, p.w_hh2, D, h2, Sz, D, p.b_ih2, p.b_hh2, 4 * D, 0, gates, 4 * D, hi);
-    phase_sync();
-    lstm_update(gates, 4 * D, h2, c2, Sz, D, hi);
-    phase_sync();
-    // 7: char_trans
-    matmat(p.w_ct, D, h2, Sz, D, nullptr, 0, nullptr, 0, 0, p.b_ct, nullptr, V, 0, lg, 64, hi);
-    phase_sync();
+    // 1 to 7: the logit rows of slots 0 .. hi - 1
+    speller_step(p, w, feat, comp, len, st, hi, [&](int, float* row, float sum) { normalise_row(row, sum, len); });
     // 8: the draw, a wave per live sample: z = row / tau, e = exp(z - max z), the first v whose running sum of e
     // exceeds u * total (V - 1 when none does); the sums run in index order, the same in every lane
     for (int b = wave; b < hi; b += kWaves) {
@@ -1141,20 +1133,20 @@ __global__ __launch_bounds__(kThreads) void decode_sample_kernel(SampleDev sd) {
     hi = top;
     for (int i = tid; i < hi * D; i += kThreads) {
       const int j = i / D, u = i % D;
-      if (alive[j]) xin[(int64_t)j * XI + u] = p.embed[(int64_t)chr[j] * D + u];
+      if (alive[j]) w.xin[(int64_t)j * XI + u] = p.embed[(int64_t)chr[j] * D + u];
     }
     for (int i = tid; i < hi * Hl; i += kThreads) {
       const int j = i / Hl, u = i % Hl;
-      if (alive[j]) lmx[(int64_t)j * Hl + u] = p.lm.emb[(int64_t)chr[j] * Hl + u];
+      if (alive[j]) w.lmx[(int64_t)j * Hl + u] = p.lm.emb[(int64_t)chr[j] * Hl + u];
     }
     phase_sync();
   }
   if (tid < K) {
     p.n_chars[(int64_t)n * K + tid] = nch[tid];
-    sd.hyp_scores[(int64_t)n * K + tid] = score[tid];
+    sd.b.hyp_scores[(int64_t)n * K + tid] = score[tid];
     if (sd.logq) sd.logq[(int64_t)n * K + tid] = logq[tid];
   }
-  if (tid == 0) sd.n_hyps[n] = K;
+  if (tid == 0) sd.b.n_hyps[n] = K;
 }
 
 // One CharLM.forward (src/charlm.py:46-57) for B rows, a workgroup per row.
@@ -1257,32 +1249,42 @@ extern "C" int ssasr_decode_greedy(const ssasr_infer* dp, void* stream) {
 
 extern "C" int64_t ssasr_decode_beam_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
                                               int64_t V, int64_t Hl, int64_t S) {
-  if (!decode_dims_ok(N, K, T, E, A, D, V, Hl, S)) return 0;
-  return N * beam_ws_map((int)K, (int)T, (int)E, (int)A, (int)D, (int)Hl, (int)S).total * (int64_t)sizeof(float);
+  return ssasr_decode_beam_ex_ws_bytes(N, K, T, E, A, D, V, Hl, S, 0, 0);
 }
 
 extern "C" int64_t ssasr_decode_beam_ctc_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
                                                   int64_t V, int64_t Hl, int64_t S) {
-  if (!decode_dims_ok(N, K, T, E, A, D, V, Hl, S)) return 0;
-  const BeamWs m = beam_ws_map((int)K, (int)T, (int)E, (int)A, (int)D, (int)Hl, (int)S);
-  return N * ctc_ws_map(m, (int)K, (int)T).total * (int64_t)sizeof(float);
+  return ssasr_decode_beam_ex_ws_bytes(N, K, T, E, A, D, V, Hl, S, 1, 0);
 }
 
 extern "C" int64_t ssasr_decode_beam_ex_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
                                                  int64_t V, int64_t Hl, int64_t S, int32_t ctc, int32_t coverage) {
   if (!decode_dims_ok(N, K, T, E, A, D, V, Hl, S)) return 0;
   const BeamWs m = beam_ws_map((int)K, (int)T, (int)E, (int)A, (int)D, (int)Hl, (int)S);
-  const int64_t slice = (ctc ? ctc_ws_map(m, (int)K, (int)T).total : m.total) + (coverage ? cov_ws_floats(m, (int)K) : 0);
-  return N * slice * (int64_t)sizeof(float);
+  return N * beam_slice_floats(m, (int)K, (int)T, ctc != 0, coverage != 0) * (int64_t)sizeof(float);
+}
+
+extern "C" int64_t ssasr_decode_sample_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
+                                                int64_t V, int64_t Hl, int64_t S) {
+  if (!decode_dims_ok(N, K, T, E, A, D, V, Hl, S)) return 0;
+  return N * sample_ws_map((int)K, (int)T, (int)E, (int)A, (int)D, (int)Hl).total * (int64_t)sizeof(float);
 }
 
 namespace {
 
+// What the K-hypothesis entries check alike and fill alike: the description (infer_dev), the workspace (there, on 16
+// bytes, at least need(Hl) bytes: the entry's own size query) and the two per-hypothesis outputs.
+template <class Need>
+bool beam_dev(const ssasr_beam* dp, Need need, BeamDev& b) {
+  if (!dp || !infer_dev(*dp, dp->K, b.in)) return false;
+  const ssasr_beam& d = *dp;
+  if (!d.ws || !aligned16(d.ws) || !d.hyp_scores || !d.n_hyps || d.ws_bytes < need(d, b.in.lm.H)) return false;
+  b.K = (int)d.K; b.ws = d.ws; b.hyp_scores = d.hyp_scores; b.n_hyps = d.n_hyps;
+  return true;
+}
+
 // ssasr_decode_beam (cp == nullptr), ssasr_decode_beam_ctc and ssasr_decode_beam_ex (tp != nullptr)
 int launch_beam(const ssasr_beam* dp, const ssasr_ctc_prefix* cp, const ssasr_beam_terms* tp, void* stream) {
-  BeamDev b{};
-  if (!dp || !infer_dev(*dp, dp->K, b.in)) return SSASR_EARG;
-  const ssasr_beam& d = *dp;
   TermsDev t{0.f, 0.f, 0.f, -1.f, nullptr};
   if (tp) {
     if (!std::isfinite(tp->length_bonus) || !std::isfinite(tp->coverage_weight) || tp->end_margin != tp->end_margin)
@@ -1293,10 +1295,12 @@ int launch_beam(const ssasr_beam* dp, const ssasr_ctc_prefix* cp, const ssasr_be
                  tp->end_margin >= 0.f ? tp->end_margin : -1.f, tp->n_steps};
   }
   const bool terms = t.beta != 0.f || t.eta != 0.f || t.delta >= 0.f;
-  const int64_t need = ssasr_decode_beam_ex_ws_bytes(d.N, d.K, d.T, d.E, d.A, d.D, d.V, b.in.lm.H, d.max_steps,
-                                                     cp ? 1 : 0, t.eta != 0.f ? 1 : 0);
-  if (!d.ws || !aligned16(d.ws) || !d.hyp_scores || !d.n_hyps || d.ws_bytes < need) return SSASR_EARG;
-  b.K = (int)d.K; b.ws = d.ws; b.hyp_scores = d.hyp_scores; b.n_hyps = d.n_hyps;
+  BeamDev b{};
+  const auto need = [&](const ssasr_beam& d, int Hl) {
+    return ssasr_decode_beam_ex_ws_bytes(d.N, d.K, d.T, d.E, d.A, d.D, d.V, Hl, d.max_steps, cp ? 1 : 0, t.eta != 0.f);
+  };
+  if (!beam_dev(dp, need, b)) return SSASR_EARG;
+  const ssasr_beam& d = *dp;
   CtcDev c{};
   if (cp) {
     if (!(cp->ctc_weight >= 0.f && cp->ctc_weight <= 1.f) || cp->blank < 0 || cp->blank >= d.V || cp->blank == d.eos)
@@ -1337,23 +1341,16 @@ extern "C" int ssasr_decode_beam_ex(const ssasr_beam* dp, const ssasr_ctc_prefix
   return launch_beam(dp, cp, tp, stream);
 }
 
-extern "C" int64_t ssasr_decode_sample_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
-                                                int64_t V, int64_t Hl, int64_t S) {
-  if (!decode_dims_ok(N, K, T, E, A, D, V, Hl, S)) return 0;
-  return N * sample_ws_map((int)K, (int)T, (int)E, (int)A, (int)D, (int)Hl).total * (int64_t)sizeof(float);
-}
-
 extern "C" int ssasr_decode_sample(const ssasr_beam* dp, const ssasr_sample* sp, void* stream) {
   SampleDev s{};
-  if (!dp || !sp || !infer_dev(*dp, dp->K, s.in)) return SSASR_EARG;
-  const ssasr_beam& d = *dp;
-  if (!sp->uniforms || (reinterpret_cast<uintptr_t>(sp->uniforms) & 3) != 0) return SSASR_EARG;
+  if (!sp || !sp->uniforms || (reinterpret_cast<uintptr_t>(sp->uniforms) & 3) != 0) return SSASR_EARG;
   if (!(std::isfinite(sp->temperature) && sp->temperature > 0.f)) return SSASR_EARG;
-  const int64_t need = ssasr_decode_sample_ws_bytes(d.N, d.K, d.T, d.E, d.A, d.D, d.V, s.in.lm.H, d.max_steps);
-  if (!d.ws || !aligned16(d.ws) || !d.hyp_scores || !d.n_hyps || d.ws_bytes < need) return SSASR_EARG;
-  s.K = (int)d.K; s.ws = d.ws; s.hyp_scores = d.hyp_scores; s.n_hyps = d.n_hyps;
+  const auto need = [](const ssasr_beam& d, int Hl) {
+    return ssasr_decode_sample_ws_bytes(d.N, d.K, d.T, d.E, d.A, d.D, d.V, Hl, d.max_steps);
+  };
+  if (!beam_dev(dp, need, s.b)) return SSASR_EARG;
   s.uniforms = sp->uniforms; s.tau = sp->temperature; s.logq = sp->logq;
-  hipLaunchKernelGGL(decode_sample_kernel, dim3((unsigned)d.N), dim3(kThreads), 0, (hipStream_t)stream, s);
+  hipLaunchKernelGGL(decode_sample_kernel, dim3((unsigned)dp->N), dim3(kThreads), 0, (hipStream_t)stream, s);
   SSASR_LAUNCH_CHECK();
   return SSASR_OK;
 }

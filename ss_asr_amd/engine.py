@@ -180,19 +180,16 @@ class MWERTrainStep:
     def search(self, feat, enc_len_dev):
         """The n-best list of this batch's own features (sampling: K draws per utterance), without grad:
         (chars, n_chars, n_hyps) on the device."""
-        m = self.model
-        if self.sampling:
-            with torch.no_grad():
+        with torch.no_grad():
+            if self.sampling:
+                args = self.model._decode_args(feat.detach(), enc_len_dev, None, 0.0, self.eos, self.max_decoding_steps)
                 uniforms = torch.rand(feat.shape[0], self.beam_size, self.max_decoding_steps, device=feat.device,
                                       dtype=torch.float32, generator=self.generator)
-                chars, n_chars, _, n_hyps, _ = ops.decode_sample(
-                    feat.detach(), enc_len_dev, m._decoder_params(), (m.attention.psi.weight, m.attention.psi.bias),
-                    None, 0.0, self.eos, self.max_decoding_steps, self.beam_size, uniforms)
-            return chars, n_chars, n_hyps
-        with torch.no_grad():
-            chars, n_chars, _, n_hyps = ops.decode_beam(
-                feat.detach(), enc_len_dev, m._decoder_params(), (m.attention.psi.weight, m.attention.psi.bias),
-                self.lm, self.lm_weight, self.eos, self.max_decoding_steps, self.beam_size)
+                chars, n_chars, _, n_hyps, _ = ops.decode_sample(*args, self.beam_size, uniforms)
+            else:
+                args = self.model._decode_args(feat.detach(), enc_len_dev, self.lm, self.lm_weight, self.eos,
+                                               self.max_decoding_steps)
+                chars, n_chars, _, n_hyps = ops.decode_beam(*args, self.beam_size)
         return chars, n_chars, n_hyps
 
     def _reference_rows(self, B, M, dev):

@@ -1478,25 +1478,25 @@ MAX_BEAM = 32
 
 
 def beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws=None, ctc=False,
-                coverage=None):
+                coverage=False, size_query=None):
     """(struct ssasr_beam, its outputs (chars, n_chars, hyp_scores, n_hyps), the tensors it points into) for
-    decode_beam's arguments; the outputs are allocated, not yet written.  ctc: the workspace is sized for
-    ssasr_decode_beam_ctc.  coverage True / False: it is sized by ssasr_decode_beam_ex_ws_bytes, with / without the
-    coverage block."""
+    decode_beam's arguments; the outputs are allocated, not yet written.  The workspace is sized by
+    ssasr_decode_beam_ex_ws_bytes for the CTC form (ctc) and the coverage block (coverage), or by size_query, another
+    entry's query over the same nine sizes (ssasr_decode_sample_ws_bytes).  Sizes no entry takes are refused before
+    anything else is looked at."""
     lib = _lib.load()
-    d, keep = _decode_struct(_lib.Beam, feat, enc_len, params, psi, lm, lm_weight, eos, max_steps)
-    N, K, S = d.N, int(beam_size), d.max_steps
-    dev = keep[0].device
-    hl = lm.hidden_size if lm is not None else 0
-    if coverage is None:
-        query = lib.ssasr_decode_beam_ctc_ws_bytes if ctc else lib.ssasr_decode_beam_ws_bytes
-        need = int(query(N, K, d.T, d.E, d.A, d.D, d.V, hl, S))
+    (N, T, E), (A, D), V = feat.shape, params['w_phi'].shape, params['w_ct'].shape[0]
+    K, S, hl = int(beam_size), int(max_steps), lm.hidden_size if lm is not None else 0
+    sizes = (N, K, T, E, A, D, V, hl, S)
+    if size_query is None:
+        entry, need = 'ssasr_decode_beam', lib.ssasr_decode_beam_ex_ws_bytes(*sizes, int(bool(ctc)), int(bool(coverage)))
     else:
-        need = int(lib.ssasr_decode_beam_ex_ws_bytes(N, K, d.T, d.E, d.A, d.D, d.V, hl, S, int(bool(ctc)),
-                                                     int(bool(coverage))))
+        entry, need = size_query.__name__[:-len('_ws_bytes')], size_query(*sizes)
     if need <= 0:
-        raise RuntimeError('ssasr_decode_beam: invalid argument (beam size %d, sizes N %d T %d E %d A %d D %d V %d '
-                           'H %d steps %d)' % (K, N, d.T, d.E, d.A, d.D, d.V, hl, S))
+        raise RuntimeError('%s: invalid argument (beam size %d, sizes N %d T %d E %d A %d D %d V %d H %d steps %d)'
+                           % (entry, K, N, T, E, A, D, V, hl, S))
+    d, keep = _decode_struct(_lib.Beam, feat, enc_len, params, psi, lm, lm_weight, eos, S)
+    dev = keep[0].device
     if ws is None:
         ws = torch.empty(need // 4, device=dev, dtype=torch.float32)
     _need_gpu(ws)
@@ -1529,22 +1529,14 @@ def decode_sample(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, n_s
     of that text), n_hyps [N] int32 (= K), logq [N, K]: the draws' log-probability under the sampled distribution).
     params, psi, lm: as for decode_greedy."""
     lib = _lib.load()
-    K, S = int(n_samples), int(max_steps)
-    N, T, E = feat.shape
-    A, D = params['w_phi'].shape
-    hl = lm.hidden_size if lm is not None else 0
-    need = int(lib.ssasr_decode_sample_ws_bytes(N, K, T, E, A, D, params['w_ct'].shape[0], hl, S))
-    if need <= 0:
-        raise RuntimeError('ssasr_decode_sample: invalid argument (%d samples, sizes N %d T %d E %d A %d D %d V %d '
-                           'H %d steps %d)' % (K, N, T, E, A, D, params['w_ct'].shape[0], hl, S))
-    _need_gpu(feat, uniforms)
-    if uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (N, K, S):
-        raise ValueError('decode_sample: uniforms must be float32 [%d, %d, %d], got %s %r'
-                         % (N, K, S, uniforms.dtype, tuple(uniforms.shape)))
+    d, outs, keep = beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, n_samples,
+                                size_query=lib.ssasr_decode_sample_ws_bytes)
+    _need_gpu(uniforms)
+    if uniforms.dtype != torch.float32 or tuple(uniforms.shape) != tuple(outs[0].shape):
+        raise ValueError('decode_sample: uniforms must be float32 %r, got %s %r'
+                         % (list(outs[0].shape), uniforms.dtype, tuple(uniforms.shape)))
     uniforms = uniforms.contiguous()
-    ws = torch.empty(need // 4, device=feat.device, dtype=torch.float32)
-    d, outs, keep = beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, S, K, ws)
-    logq = torch.empty(N, K, device=feat.device, dtype=torch.float32)
+    logq = torch.empty_like(outs[2])
     s = _lib.Sample(uniforms.data_ptr(), float(temperature), logq.data_ptr())
     check(lib.ssasr_decode_sample(C.byref(d), C.byref(s), _stream()), 'ssasr_decode_sample')
     return outs + (logq,)

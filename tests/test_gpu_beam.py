@@ -1,7 +1,6 @@
 """Beam-search decoding on the GPU: ASR.decode / decode_many / decode_nbest with beam_size (ssasr_decode_beam) and
-trainer.ASRTester with asr.decode_beam_size, against a float64 CPU beam search written HERE from the semantics of
-include/ssasr.h (beam_reference: las_oracle's OracleASR parts and the float64 GRU of test_gpu_decode; it shares
-nothing with the library's host code).
+trainer.ASRTester with asr.decode_beam_size, against the float64 CPU beam search of tests/decode_checker.py, written
+from the semantics of include/ssasr.h (it shares nothing with the library's host code).
 
 Tolerances.  A step's score row is held to SCORE_ATOL = 5e-5 (test_gpu_decode); a hypothesis' score is a sum of at
 most `steps` such entries, hence 5e-5 * steps.  The checker records, per step, the gap between the last kept and
@@ -17,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-import las_oracle as lo
+import decode_checker as dc
 import test_gpu_decode as tgd
 from conftest import GOLDEN
 from test_host_cpu import make_corpus
@@ -39,63 +38,11 @@ FULL_CASE = 'decode_full_s6'
 PAIR_CASES = [(n, f, k) for n in SMALL for f in (40, 24) for k in (0, 1)] + [(FULL_CASE, 160, 0), (FULL_CASE, 160, 1)]
 
 
-def beam_reference(fx, frames, lm_weight, K, S):
-    """The beam search of include/ssasr.h in float64 on the CPU.  -> (hyps, min_gap): hyps = [(chars, score,
-    step it ended at, capped)] in output order."""
-    from ss_asr_amd.charlm import CharLM
-    dims = tuple(int(v) for v in fx['dims'])
-    V = dims[0]
-    torch.manual_seed(0)
-    asr = lo.seeded_weights(lo.OracleASR(*dims, 1.0), int(fx['asr_weights_seed'])).double().eval()
-    lm = lo.seeded_generic_weights(CharLM(V, int(fx['lm_hidden'])), int(fx['lm_weights_seed']))
-    sd = {k: v.detach().double() for k, v in lm.state_dict().items()}
-    gru = [[sd['layer_%d.%s' % (l, n)] for n in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh')] for l in (1, 2)]
-    x = torch.from_numpy(fx['x'][:, :frames]).double()
-    with torch.no_grad():
-        feat, enc_len = asr.encoder(x, [x.shape[1]])
-        comp = torch.tanh(asr.attention.psi(feat))[0, :enc_len[0]]
-        feat = feat[0, :enc_len[0]]
-        D, Hl = dims[2], int(fx['lm_hidden'])
-        z = torch.zeros(1, D, dtype=torch.float64)
-        zl = torch.zeros(1, Hl, dtype=torch.float64)
-        live = [dict(score=0.0, prefix=[], last=0, h1=z, c1=z, h2=z, c2=z, l1=zl, l2=zl)]
-        done, gaps = [], []
-        for step in range(S):
-            if not live:
-                break
-            width = K - len(done)
-            cands, nxt = [], []
-            for b, h in enumerate(live):
-                q = torch.tanh(asr.attention.phi(h['h1']))
-                alpha = torch.softmax(comp @ q[0], 0)
-                ctx = (alpha @ feat).unsqueeze(0)
-                inp = torch.cat([asr.embed.weight[h['last']].unsqueeze(0), ctx], -1)
-                h1, c1 = asr.decoder.layer_1(inp, (h['h1'], h['c1']))
-                h2, c2 = asr.decoder.layer_2(h1, (h['h2'], h['c2']))
-                row = torch.log_softmax(asr.char_trans(h2)[0], 0)
-                l1 = tgd.gru_cell64(sd['emb.weight'][h['last']].unsqueeze(0), h['l1'], *gru[0])
-                l2 = tgd.gru_cell64(l1, h['l2'], *gru[1])
-                row = row + lm_weight * torch.log_softmax((l2 @ sd['out.weight'].t() + sd['out.bias'])[0], 0)
-                nxt.append(dict(h1=h1, c1=c1, h2=h2, c2=c2, l1=l1, l2=l2))
-                cands += [(h['score'] + float(row[v]), b * V + v) for v in range(V)]
-            order = sorted(cands, key=lambda c: (-c[0], c[1]))
-            kept = order[:width]
-            if len(order) > width:
-                gaps.append(kept[-1][0] - order[width][0])
-            gaps += [a[0] - b[0] for a, b in zip(kept, kept[1:])]
-            new = []
-            for score, flat in kept:
-                b, v = divmod(flat, V)
-                if v == EOS:
-                    done.append((list(live[b]['prefix']), score, step, False))
-                else:
-                    new.append(dict(nxt[b], score=score, prefix=live[b]['prefix'] + [v], last=v))
-            live = new
-        done += [(h['prefix'], h['score'], S, True) for h in live]
-    order = sorted(range(len(done)), key=lambda i: (-done[i][1], i))
-    hyps = [done[i] for i in order]
-    gaps += [a[1] - b[1] for a, b in zip(hyps, hyps[1:])]
-    return hyps, float(min(gaps))
+def beam_reference(m, lm_weight, K, S):
+    """The plain beam search over the float64 model m.  -> (hyps, min_gap): hyps = [(chars, score, step it ended at,
+    capped)] in output order."""
+    r = dc.beam_search(m, K, S, lm_weight)
+    return [h[:4] for h in r['hyps']], r['gap']
 
 
 _refs = {}
@@ -104,8 +51,7 @@ _refs = {}
 def reference(golden, name, frames, k, K):
     key = (name, frames, k, K)
     if key not in _refs:
-        fx = golden(name)
-        _refs[key] = beam_reference(fx, frames, float(fx['lm_weights'][k]), K, STEPS)
+        _refs[key] = beam_reference(dc.model(golden, name, frames), float(golden(name)['lm_weights'][k]), K, STEPS)
     return _refs[key]
 
 

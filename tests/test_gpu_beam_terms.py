@@ -1,8 +1,7 @@
 """The beam search's length bonus, coverage term and end detection on the GPU (ssasr_decode_beam_ex; ASR.decode /
 decode_many / decode_nbest with length_bonus, coverage_weight, coverage_threshold, end_margin; ASRTester with the
-asr.decode_* keys) against a float64 CPU beam search written HERE from the semantics of include/ssasr.h
-(terms_beam: test_gpu_beam.beam_reference's loop with the CTC scorer restated as test_gpu_ctc_decode.py does, plus
-the three terms).  It shares nothing with the library's host code.
+asr.decode_* keys) against the float64 CPU beam search of tests/decode_checker.py with its three terms (and, at
+lambda > 0, its CTC term) on.  It shares nothing with the library's host code.
 
 Gaps.  A (case, K, lambda, terms) tuple is compared only when the checker's smallest gap is >= MIN_GAP = 1e-3: kept /
 dropped, kept / kept, emitted / emitted, and the stop rule's |max live - (best finished - delta)| at every step it is
@@ -22,7 +21,7 @@ import numpy as np
 import pytest
 import torch
 
-import test_ctc_decode_cpu as tcc
+import decode_checker as dc
 import test_gpu_beam as tgb
 import test_gpu_ctc_decode as tgc
 import test_gpu_decode as tgd
@@ -39,7 +38,6 @@ Mapper = tgd.Mapper
 EOS, STEPS = 1, 24
 BEAMS = (2, 3, 5)
 LAMBDAS = (0.0, 0.3)
-NEG = -math.inf
 LONG_CASE = 'decode_long_s6'
 # (beta, eta, tau, delta), delta None: no end detection: the length bonus alone, the coverage term alone, and all
 # three.  Found by sweeping the checker on the CPU.  With these seeded weights the attention is near-uniform (1 / T'
@@ -51,123 +49,15 @@ LONG_CASE = 'decode_long_s6'
 GRID = ((0.6, 0.0, 0.5, None), (0.0, 1.5, 0.36, None), (0.1, 1.5, 0.36, 0.0))
 
 
-class Ref(tgc.Ref):
-    """tgc.Ref whose step also hands out the attention row (float64 numpy [T'])."""
-
-    def step(self, h):
-        asr, sd = self.asr, self.sd
-        with torch.no_grad():
-            q = torch.tanh(asr.attention.phi(h['h1']))
-            alpha = torch.softmax(self.comp @ q[0], 0)
-            ctx = (alpha @ self.feat).unsqueeze(0)
-            inp = torch.cat([asr.embed.weight[h['last']].unsqueeze(0), ctx], -1)
-            h1, c1 = asr.decoder.layer_1(inp, (h['h1'], h['c1']))
-            h2, c2 = asr.decoder.layer_2(h1, (h['h2'], h['c2']))
-            row = torch.log_softmax(asr.char_trans(h2)[0], 0)
-            l1 = tgd.gru_cell64(sd['emb.weight'][h['last']].unsqueeze(0), h['l1'], *self.gru[0])
-            l2 = tgd.gru_cell64(l1, h['l2'], *self.gru[1])
-            lm_row = torch.log_softmax((l2 @ sd['out.weight'].t() + sd['out.bias'])[0], 0)
-        return row.numpy(), lm_row.numpy(), dict(h1=h1, c1=c1, h2=h2, c2=c2, l1=l1, l2=l2, alpha=alpha.numpy())
-
-    def entries(self, h, lam, lm_weight):
-        """-> (today's score entries of h's candidates [V] (-inf: never chosen), psi [V] or None, advanced states)."""
-        if lam > 0:
-            return self.rows(h, lam, lm_weight)
-        row, lm_row, nxt = self.step(h)
-        return row + lm_weight * lm_row, None, nxt
-
-
-def terms_beam(ref, K, S, lam, lm_weight, beta, eta, tau, delta):
-    """The beam search of include/ssasr.h with its terms, float64.  -> dict(hyps = [(chars, score, step it ended at,
-    capped, cov of the prefix)] in output order, gap, tau_gap, n_steps, fired: the stop rule ended the loop (with
-    something live, by definition), early: it did so before the cap's last step)."""
-    V = ref.V
-    start = ref.start()
-    start.update(cum=np.zeros(ref.T), cov=0)
-    live, done, gaps, tau_gap, n_steps, fired = [start], [], [], math.inf, 0, False
-    for step in range(S):
-        if not live:
-            break
-        n_steps = step + 1
-        cands, nxt, psis = [], [], []
-        for b, h in enumerate(live):
-            entry, psi, n = ref.entries(h, lam, lm_weight)
-            inc = 0.0
-            if eta != 0:
-                n['cum'] = h['cum'] + n['alpha']
-                n['cov'] = int((n['cum'] > tau).sum())
-                tau_gap = min(tau_gap, float(np.abs(n['cum'] - tau).min()))
-                inc = eta * (n['cov'] - h['cov'])
-            else:
-                n['cum'], n['cov'] = h['cum'], 0
-            nxt.append(n)
-            psis.append(psi)
-            cands += [(h['score'] + float(entry[v]) + (beta if v != EOS else 0.0) + inc, b * V + v)
-                      for v in range(V) if entry[v] > NEG]
-        width = min(K - len(done), len(cands))
-        order = sorted(cands, key=lambda c: (-c[0], c[1]))
-        kept = order[:width]
-        if len(order) > width:
-            gaps.append(kept[-1][0] - order[width][0])
-        gaps += [a[0] - b[0] for a, b in zip(kept, kept[1:])]
-        new = []
-        for score, flat in kept:
-            b, v = divmod(flat, V)
-            if v == EOS:
-                done.append((list(live[b]['prefix']), score, step, False, nxt[b]['cov']))
-            else:
-                child = dict(nxt[b], score=score, prefix=live[b]['prefix'] + [v], last=v)
-                if lam > 0:
-                    child['ctc'] = tcc.extend(ref.lp, live[b]['ctc'], v, psis[b][v])
-                new.append(child)
-        live = new
-        if delta is not None and done and live:
-            ml, mf = max(h['score'] for h in live), max(d[1] for d in done)
-            gaps.append(abs(ml - (mf - delta)))
-            if ml < mf - delta:
-                fired, live = True, []
-                break
-    done += [(h['prefix'], h['score'], S, True, h['cov']) for h in live]
-    order = sorted(range(len(done)), key=lambda i: (-done[i][1], i))
-    hyps = [done[i] for i in order]
-    gaps += [a[1] - b[1] for a, b in zip(hyps, hyps[1:])]
-    return dict(hyps=hyps, gap=float(min(gaps)) if gaps else math.inf, tau_gap=tau_gap, n_steps=n_steps, fired=fired,
-                early=fired and n_steps < S)
-
-
-def forced(ref, text, ended, lam, lm_weight, tau):
-    """(today's score of exactly `text` (ended: by <EOS>), cov(text) at tau counting <EOS>'s step when ended, the
-    smallest |cum' - tau| on the way), teacher-forced through the float64 model."""
-    h, total, cum, tau_gap = ref.start(), 0.0, np.zeros(ref.T), math.inf
-    for v in list(text) + ([EOS] if ended else []):
-        entry, psi, nxt = ref.entries(h, lam, lm_weight)
-        total += float(entry[v])
-        cum = cum + nxt['alpha']
-        tau_gap = min(tau_gap, float(np.abs(cum - tau).min()))
-        if v != EOS:
-            ctc = tcc.extend(ref.lp, h['ctc'], v, psi[v]) if lam > 0 else h['ctc']
-            h = dict(nxt, score=total, prefix=h['prefix'] + [v], last=v, ctc=ctc)
-    return total, int((cum > tau).sum()), tau_gap
-
-
-def bound(steps, lam):
-    return tgc.bound(steps, lam)
-
-
+forced, ref_of, bound = dc.forced, dc.model, tgc.bound
 _refs, _beams = {}, {}
-
-
-def ref_of(golden, name, frames):
-    if (name, frames) not in _refs:
-        _refs[(name, frames)] = Ref(golden(name), frames)
-    return _refs[(name, frames)]
 
 
 def reference(golden, name, frames, k, K, lam, terms, S=STEPS):
     key = (name, frames, k, K, lam, terms, S)
     if key not in _beams:
         w = float(golden(name)['lm_weights'][k])
-        _beams[key] = terms_beam(ref_of(golden, name, frames), K, S, lam, w, *terms)
+        _beams[key] = dc.beam_search(ref_of(golden, name, frames), K, S, w, lam, *terms)
     return _beams[key]
 
 
@@ -330,7 +220,7 @@ def test_the_coverage_term_of_every_emitted_hypothesis_is_eta_times_its_count(go
     asr, lm = tgc.models(fx)
     key = (name, 'long', K)
     if key not in _refs:
-        _refs[key] = Ref(dict(fx, x=xs) if K == 32 else fx, 1100)
+        _refs[key] = dc.Model(dict(fx, x=xs) if K == 32 else fx, 1100)
     ref = _refs[key]
     assert ref.T == 137
     tau = 2.5 / 137                                   # near-uniform attention: crossed at about the third step

@@ -1,8 +1,7 @@
 """Joint CTC / attention decoding on the GPU (ssasr_decode_beam_ctc; ASR.decode / decode_many / decode_nbest with
-ctc_weight; ASRTester with asr.decode_ctc_weight) against a float64 CPU beam search written HERE from the semantics
-of include/ssasr.h: test_gpu_beam.beam_reference's loop restated with the CTC prefix scorer that
-test_ctc_decode_cpu.py pins by brute force and against torch's ctc_loss.  It shares nothing with the library's
-host code.  The head's weights come from a seed (HEAD_SEED, las_oracle.seeded_generic_weights on an nn.Linear).
+ctc_weight; ASRTester with asr.decode_ctc_weight) against the float64 CPU beam search of tests/decode_checker.py with
+its CTC term on: the prefix scorer is the one that test_ctc_decode_cpu.py pins by brute force and against torch's
+ctc_loss.  The head's weights come from a seed (HEAD_SEED, las_oracle.seeded_generic_weights on an nn.Linear).
 
 Tolerance of a hypothesis' score: 5e-5 * steps for the attention and LM rows (SCORE_ATOL, unchanged) plus
 lambda * C for the CTC part: the CTC terms of a hypothesis telescope to lambda * psi(final prefix), one term.
@@ -22,9 +21,9 @@ import types
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
+import decode_checker as dc
 import las_oracle as lo
 import test_ctc_decode_cpu as tcc
 import test_gpu_beam as tgb
@@ -41,7 +40,7 @@ Mapper = tgd.Mapper
 EOS, BLANK, STEPS = 1, 0, 24
 BEAMS = (2, 3, 5)
 LAMBDAS = (0.3, 1.0)
-HEAD_SEED = 1
+HEAD_SEED = dc.HEAD_SEED
 # test_gpu_beam's shapes (T' = 5, 3 and 20), and T' = 1 (9 frames) beside them.  With these near-uniform seeded heads no hypothesis of the
 # 40- / 24- / 160-frame cases is ended by frames running out under any head seed 0..15 (checked with the checker on
 # the CPU: the <EOS> candidates of the shorter prefixes fill the beam before a prefix as long as the utterance is
@@ -54,109 +53,12 @@ CTC_C = 8 * CTC_NOISE
 NEG = -math.inf
 
 
-class Ref:
-    """The float64 model of one (fixture, frames): encoder output, comp, the head's lp (float64, and float32 from
-    a float32 product for the noise figure), and one decoder + LM step."""
-
-    def __init__(self, fx, frames, head_seed=HEAD_SEED):
-        from ss_asr_amd.charlm import CharLM
-        dims = tuple(int(v) for v in fx['dims'])
-        self.V, self.D, self.Hl = dims[0], dims[2], int(fx['lm_hidden'])
-        torch.manual_seed(0)
-        self.asr = lo.seeded_weights(lo.OracleASR(*dims, 1.0), int(fx['asr_weights_seed'])).double().eval()
-        lm = lo.seeded_generic_weights(CharLM(self.V, self.Hl), int(fx['lm_weights_seed']))
-        self.sd = {k: v.detach().double() for k, v in lm.state_dict().items()}
-        self.gru = [[self.sd['layer_%d.%s' % (l, n)] for n in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh')]
-                    for l in (1, 2)]
-        x = torch.from_numpy(fx['x'][:, :frames]).double()
-        with torch.no_grad():
-            feat, enc_len = self.asr.encoder(x, [x.shape[1]])
-            self.feat = feat[0, :enc_len[0]]
-            self.comp = torch.tanh(self.asr.attention.psi(feat))[0, :enc_len[0]]
-            head = lo.seeded_generic_weights(nn.Linear(self.feat.shape[1], self.V), head_seed)
-            self.lp = torch.log_softmax(self.feat @ head.weight.double().t() + head.bias.double(), -1).numpy()
-            self.lp32 = torch.log_softmax(self.feat.float() @ head.weight.t() + head.bias, -1).numpy()
-        self.T = self.lp.shape[0]
-
-    def start(self):
-        z, zl = torch.zeros(1, self.D, dtype=torch.float64), torch.zeros(1, self.Hl, dtype=torch.float64)
-        return dict(score=0.0, prefix=[], last=0, h1=z, c1=z, h2=z, c2=z, l1=zl, l2=zl, ctc=tcc.empty_prefix(self.lp))
-
-    def step(self, h):
-        """-> (log_softmax(speller) [V], log_softmax(lm) [V], the advanced states)."""
-        asr, sd = self.asr, self.sd
-        with torch.no_grad():
-            q = torch.tanh(asr.attention.phi(h['h1']))
-            alpha = torch.softmax(self.comp @ q[0], 0)
-            ctx = (alpha @ self.feat).unsqueeze(0)
-            inp = torch.cat([asr.embed.weight[h['last']].unsqueeze(0), ctx], -1)
-            h1, c1 = asr.decoder.layer_1(inp, (h['h1'], h['c1']))
-            h2, c2 = asr.decoder.layer_2(h1, (h['h2'], h['c2']))
-            row = torch.log_softmax(asr.char_trans(h2)[0], 0)
-            l1 = tgd.gru_cell64(sd['emb.weight'][h['last']].unsqueeze(0), h['l1'], *self.gru[0])
-            l2 = tgd.gru_cell64(l1, h['l2'], *self.gru[1])
-            lm_row = torch.log_softmax((l2 @ sd['out.weight'].t() + sd['out.bias'])[0], 0)
-        return row.numpy(), lm_row.numpy(), dict(h1=h1, c1=c1, h2=h2, c2=c2, l1=l1, l2=l2)
-
-    def rows(self, h, lam, lm_weight):
-        """-> (the candidates' score entries [V], psi of the candidates [V], the advanced states)."""
-        row, lm_row, nxt = self.step(h)
-        psi = tcc.candidate_psi(self.lp, h['ctc'], EOS)
-        with np.errstate(invalid='ignore'):
-            entry = (1.0 - lam) * row + lam * (psi - h['ctc'].psi)
-        if lm_weight is not None:
-            entry = entry + lm_weight * lm_row
-        return entry, psi, nxt
-
-
 def joint_beam(ref, K, S, lam, lm_weight):
-    """The beam search of include/ssasr.h with the CTC prefix score, float64.  -> (hyps, min_gap, ran_out): hyps =
+    """The beam search with the CTC prefix score over the float64 model ref.  -> (hyps, min_gap, ran_out): hyps =
     [(chars, score, step it ended at, capped)] in output order; ran_out: a hypothesis was ended by <EOS> at a step
     where all its other candidates were at -inf."""
-    V = ref.V
-    live, done, gaps, ran_out = [ref.start()], [], [], False
-    for step in range(S):
-        if not live:
-            break
-        cands, nxt, psis, stuck = [], [], [], []
-        for b, h in enumerate(live):
-            entry, psi, n = ref.rows(h, lam, lm_weight)
-            nxt.append(n)
-            psis.append(psi)
-            stuck.append(all(entry[v] == NEG for v in range(V) if v != EOS))
-            cands += [(h['score'] + float(entry[v]), b * V + v) for v in range(V) if entry[v] > NEG]
-        width = min(K - len(done), len(cands))
-        order = sorted(cands, key=lambda c: (-c[0], c[1]))
-        kept = order[:width]
-        if len(order) > width:
-            gaps.append(kept[-1][0] - order[width][0])
-        gaps += [a[0] - b[0] for a, b in zip(kept, kept[1:])]
-        new = []
-        for score, flat in kept:
-            b, v = divmod(flat, V)
-            if v == EOS:
-                done.append((list(live[b]['prefix']), score, step, False))
-                ran_out |= stuck[b]
-            else:
-                new.append(dict(nxt[b], score=score, prefix=live[b]['prefix'] + [v], last=v,
-                                ctc=tcc.extend(ref.lp, live[b]['ctc'], v, psis[b][v])))
-        live = new
-    done += [(h['prefix'], h['score'], S, True) for h in live]
-    order = sorted(range(len(done)), key=lambda i: (-done[i][1], i))
-    hyps = [done[i] for i in order]
-    gaps += [a[1] - b[1] for a, b in zip(hyps, hyps[1:])]
-    return hyps, float(min(gaps)) if gaps else math.inf, ran_out
-
-
-def forced_score(ref, text, ended, lam, lm_weight):
-    """The joint score of exactly `text` (ended: by <EOS>), teacher-forced through the float64 model."""
-    h, total = ref.start(), 0.0
-    for v in list(text) + ([EOS] if ended else []):
-        entry, psi, nxt = ref.rows(h, lam, lm_weight)
-        total += float(entry[v])
-        if v != EOS:
-            h = dict(nxt, score=total, prefix=h['prefix'] + [v], last=v, ctc=tcc.extend(ref.lp, h['ctc'], v, psi[v]))
-    return total
+    r = dc.beam_search(ref, K, S, lm_weight, lam)
+    return [h[:4] for h in r['hyps']], r['gap'], r['ran_out']
 
 
 def final_psi(lp, text, ended):
@@ -179,13 +81,8 @@ def bound(steps, lam):
     return SCORE_ATOL * steps + lam * CTC_C
 
 
-_refs, _beams, _joint = {}, {}, {}
-
-
-def ref_of(golden, name, frames):
-    if (name, frames) not in _refs:
-        _refs[(name, frames)] = Ref(golden(name), frames)
-    return _refs[(name, frames)]
+_beams, _joint = {}, {}
+ref_of = dc.model
 
 
 def reference(golden, name, frames, k, K, lam):
@@ -302,7 +199,7 @@ def test_every_emitted_score_is_the_joint_score_of_its_text_at_twelve_hypotheses
     for i in range(nh):
         n = int(n_chars[0, i])
         text, ended = [int(c) for c in chars[0, i, :n]], n < STEPS
-        want = forced_score(ref, text, ended, lam, w)
+        want = dc.forced(ref, text, ended, lam, w)[0]
         err = abs(float(scores[0, i]) - want)
         print('hypothesis %d: %d characters, %s, score %.6f, joint score of the text %.6f, error %.2e'
               % (i, n, 'ended' if ended else 'capped', float(scores[0, i]), want, err))

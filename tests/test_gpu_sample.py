@@ -1,6 +1,6 @@
 """Sampled decoding on the GPU: ssasr_decode_sample (ops.decode_sample, ASR.sample) against test_sample_cpu's float64
-checker walking a float64 model written HERE (las_oracle's OracleASR parts and the float64 GRU of test_gpu_decode; it
-shares nothing with the library's host code), ssasr_mwer_loss_fwd_ex against postprocess.mwer_reference, and
+checker walking the float64 model of tests/decode_checker.py, K rows a step (it shares nothing with the library's host
+code), ssasr_mwer_loss_fwd_ex against postprocess.mwer_reference, and
 engine.MWERTrainStep(sampling=True) against OracleASR in float64 driven the same way.
 
 Tolerances.  A step's score row is held to SCORE_ATOL = 5e-5 (test_gpu_decode); a sample's score is a sum of at most
@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+import decode_checker as dc
 import las_oracle as lo
 import test_gpu_beam as tgb
 import test_gpu_decode as tgd
@@ -41,59 +42,7 @@ TAUS = (0.5, 1.0, 2.0)
 SHAPES = sorted({(n, f) for n, f, _ in tgb.PAIR_CASES}) + [(n, 9) for n in tgb.SMALL]
 
 
-class Model64:
-    """The float64 model of one (fixture, frames): one decoder + LM step for K samples at once (the rows of a batch
-    do not interact: every product is row by row)."""
-
-    def __init__(self, fx, frames):
-        from ss_asr_amd.charlm import CharLM
-        dims = tuple(int(v) for v in fx['dims'])
-        self.V, self.D, self.Hl = dims[0], dims[2], int(fx['lm_hidden'])
-        torch.manual_seed(0)
-        self.asr = lo.seeded_weights(lo.OracleASR(*dims, 1.0), int(fx['asr_weights_seed'])).double().eval()
-        lm = lo.seeded_generic_weights(CharLM(self.V, self.Hl), int(fx['lm_weights_seed']))
-        self.sd = {k: v.detach().double() for k, v in lm.state_dict().items()}
-        self.gru = [[self.sd['layer_%d.%s' % (l, n)] for n in ('weight_ih', 'weight_hh', 'bias_ih', 'bias_hh')]
-                    for l in (1, 2)]
-        x = torch.from_numpy(fx['x'][:, :frames]).double()
-        with torch.no_grad():
-            feat, enc_len = self.asr.encoder(x, [x.shape[1]])
-            self.comp = torch.tanh(self.asr.attention.psi(feat))[0, :enc_len[0]]
-            self.feat = feat[0, :enc_len[0]]
-
-    def start(self, K):
-        z, zl = torch.zeros(K, self.D, dtype=torch.float64), torch.zeros(K, self.Hl, dtype=torch.float64)
-        return dict(h1=z, c1=z, h2=z, c2=z, l1=zl, l2=zl)
-
-    def step_fn(self, lm_weight):
-        """sample_walk's step_fn; lm_weight None: no language model."""
-        asr, sd = self.asr, self.sd
-
-        def step(st, last):
-            with torch.no_grad():
-                last = torch.tensor(last, dtype=torch.long)
-                q = torch.tanh(asr.attention.phi(st['h1']))
-                alpha = torch.softmax(q @ self.comp.t(), 1)
-                inp = torch.cat([asr.embed.weight[last], alpha @ self.feat], 1)
-                h1, c1 = asr.decoder.layer_1(inp, (st['h1'], st['c1']))
-                h2, c2 = asr.decoder.layer_2(h1, (st['h2'], st['c2']))
-                row = torch.log_softmax(asr.char_trans(h2), 1)
-                l1, l2 = st['l1'], st['l2']
-                if lm_weight is not None:
-                    l1 = tgd.gru_cell64(sd['emb.weight'][last], l1, *self.gru[0])
-                    l2 = tgd.gru_cell64(l1, l2, *self.gru[1])
-                    row = row + lm_weight * torch.log_softmax(l2 @ sd['out.weight'].t() + sd['out.bias'], 1)
-            return row.tolist(), dict(h1=h1, c1=c1, h2=h2, c2=c2, l1=l1, l2=l2)
-        return step
-
-
-_models64 = {}
-
-
-def model64(golden, name, frames):
-    if (name, frames) not in _models64:
-        _models64[(name, frames)] = Model64(golden(name), frames)
-    return _models64[(name, frames)]
+model64 = dc.model
 
 
 def walk(m64, lm_weight, K, tau, choose_u):

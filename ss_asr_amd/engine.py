@@ -33,26 +33,94 @@ def settle_collector(again=False):
     gc.freeze()
 
 
-class ASRTrainStep:
+class TrainStep:
+    """What every step object does around its loss, once.  A step is
+
+        self._open()                                   the previous step's verdict, the listener, clean gradients
+        with ops.shared_status_row(<optimizer>.status_row):
+            <loss>.backward(self._one)                 every persistent launch reports into that optimizer's row
+        scale = <all-reduce>
+        self._update(scale)                            clip + NaN guard + update, buffers clean again
+
+    and the subclass writes that out with its own loss and all-reduce in the middle.  Its __init__ calls
+    `_models_on_gpu`, builds its optimizers and calls `_set_up`."""
+
+    # the process-wide weight-gradient listener (ops.set_wgrad_listener) at the opening of a step: True claims it for
+    # `self._listener` -- None keeps another step object's reducer from seeing this pass's gradients; False leaves it
+    # alone (the CharLM's step enqueues no weight gradient on the side stream)
+    claims_listener = True
+    _listener = None
+
+    def _models_on_gpu(self, what, *models):
+        for m in models:
+            if not next(m.parameters()).is_cuda:
+                raise RuntimeError('%s needs %s on the GPU (no CPU path)' % (type(self).__name__, what))
+
+    def _set_up(self, flats, verdicts, grad_clip):
+        """flats: the FlatParameters the step zeroes at its opening and its last update leaves clean.  verdicts:
+        ((attribute, optimizer), ...) in polling order; the last one's optimizer is the one `_update` steps, and its
+        attribute must be 'last_done'."""
+        self._flats, self._verdicts, self.grad_clip = tuple(flats), tuple(verdicts), grad_clip
+        self._one = torch.ones((), device=self._flats[0].data.device)
+        for name, _ in self._verdicts:
+            setattr(self, name, None)  # (grad_norm, skipped) of that optimizer's last step whose words have arrived
+        self.skipped_steps = 0         # updates (of any of the optimizers) skipped because the gradient norm was NaN
+
+    def _note(self, wait=False):
+        """Picks up the verdict of the previous step (gradient norm, NaN skip, and whether one of its persistent
+        launches timed out) from each optimizer whose words have reached the host; a time-out raises."""
+        for name, optim in self._verdicts:
+            done = optim.poll(wait)
+            if done is not None:
+                setattr(self, name, done)
+                self.skipped_steps += int(done[1])
+
+    def finish(self):
+        """Waits for the last step's words of every optimizer: returns the last one's (grad_norm, skipped); raises on
+        a time-out.  Whoever writes a checkpoint calls this first."""
+        self._note(wait=True)
+        return self.last_done
+
+    def _open(self):
+        self._note()                  # no synchronisation
+        if self.claims_listener:
+            # (several step objects may alternate in one process: the ASR and joint steps, the trainers of the Seed loop)
+            ops.set_wgrad_listener(self._listener)
+        for flat in self._flats:
+            if not flat.clean:        # (True right after a step whose update kernel zeroed the gradients)
+                flat.zero_grad()
+            flat.clean = False
+
+    def _update(self, scale):
+        """The step's last update.  Its kernel zeroes the gradients it read (zero_grad=True), and the pass touched no
+        other gradient of `_flats`: only here are they marked clean."""
+        self._verdicts[-1][1].clip_and_step(self.grad_clip, grad_scale=scale, zero_grad=True)
+        for flat in self._flats:
+            flat.clean = True
+        settle_collector()
+
+
+class ASRTrainStep(TrainStep):
     def __init__(self, model, lr=1.0, eps=1e-8, rho=0.9, grad_clip=5.0, label_smoothing=0.0):
         """label_smoothing in [0, 1) (build-defined): the smoothed CE of ops.masked_ce_loss; 0 is the reference's loss."""
         if not 0.0 <= float(label_smoothing) < 1.0:
             raise ValueError('label_smoothing must lie in [0, 1), got %r' % (label_smoothing,))
         self.label_smoothing = float(label_smoothing)
-        if not next(model.parameters()).is_cuda:
-            raise RuntimeError('ASRTrainStep needs the model on the GPU (no CPU path)')
+        self._set_up_asr(model, lr, eps, rho, grad_clip)
+
+    def _set_up_asr(self, model, lr, eps, rho, grad_clip):
+        """Adadelta over the whole model and the two-bucket reducer: what every step of the ASR family trains with."""
+        self._models_on_gpu('the model', model)
         self.model = model
         self.flat = FlatParameters.of(model)       # (a TAETrainStep over the same model may have made it already)
         sdist.broadcast_flat(self.flat.data)
         self.optim = FusedAdadelta(self.flat, lr=lr, rho=rho, eps=eps)
-        self.grad_clip = grad_clip
         # gradient all-reduce in two buckets, the large one overlapped with the last layer's BPTT
         self.reducer = sdist.GradReducer(self.flat, list(model.encoder.blstm_1.parameters()))
-        ops.set_wgrad_listener(self.reducer.wgrad_enqueued)
-        self._one = torch.ones((), device=self.flat.data.device)
+        self._listener = self.reducer.wgrad_enqueued
+        ops.set_wgrad_listener(self._listener)
+        self._set_up([self.flat], [('last_done', self.optim)], grad_clip)
         self.last_logits = None        # [B, U, V] of the most recent step (for the trainer's logging)
-        self.last_done = None          # (grad_norm, skipped) of the last step whose words have arrived
-        self.skipped_steps = 0         # steps whose update was skipped because the gradient norm was NaN
 
     def forward_loss(self, x, y, x_lens, ans_len):
         _, logits, att = self.model(x, ans_len, teacher=y, state_len=x_lens)
@@ -60,51 +128,29 @@ class ASRTrainStep:
 
     def __call__(self, x, y, x_lens, ans_len):
         """x [B,T,F] float32, y [B,L] int64 (both on the GPU), x_lens host list
-        (descending), ans_len = max label length - 1.  Returns the loss tensor
-        (on the device; reading it synchronises).
-
-        The verdict of the PREVIOUS step (gradient norm, NaN skip, and whether one of its
-        persistent launches timed out) is picked up here when its words have reached the host
-        -- no synchronisation; a timeout raises."""
-        self._note(self.optim.poll())
-        # the weight-gradient listener is process-wide: claim it for THIS step object (several step
-        # objects may alternate in one process -- the ASR and joint steps, the trainers of the Seed loop)
-        ops.set_wgrad_listener(self.reducer.wgrad_enqueued)
-        if not self.flat.clean:           # (True right after a step whose update kernel zeroed the gradients)
-            self.optim.zero_grad()
-        self.flat.clean = False
+        (descending), ans_len = max label length - 1 (handed on to forward_loss, whose first two results are the
+        loss and the logits).  Returns the loss tensor (on the device; reading it synchronises)."""
+        self._open()
         self.reducer.begin()
         # the attention map is only looked at by valid(): no device-to-host copy per train step
         keep, self.model.att_on_host = getattr(self.model, 'att_on_host', True), False
         try:
-            # every persistent launch of the step reports into the optimizer's status row
             with ops.shared_status_row(self.optim.status_row):
-                loss, self.last_logits, _ = self.forward_loss(x, y, x_lens, ans_len)
+                out = self.forward_loss(x, y, x_lens, ans_len)
+                loss, self.last_logits = out[0], out[1]
                 loss.backward(self._one)
         finally:
             self.model.att_on_host = keep
-        scale = self.reducer.finish()
-        self.optim.clip_and_step(self.grad_clip, grad_scale=scale, zero_grad=True)
-        self.flat.clean = True
-        settle_collector()
+        self._update(self.reducer.finish())
         return loss
 
-    def _note(self, done):
-        if done is not None:
-            self.last_done = done
-            self.skipped_steps += int(done[1])
 
-    def finish(self):
-        """Waits for the last step's words: returns its (grad_norm, skipped); raises on a timeout."""
-        self._note(self.optim.poll(wait=True))
-        return self.last_done
-
-
-class MWERTrainStep:
+class MWERTrainStep(ASRTrainStep):
     """BUILD-DEFINED (the reference trains on the masked CE alone): one step of minimum word error rate training
     (Prabhavalkar et al. 2018), the second stage of an attention model -- the expected number of word (or
     character) errors over an n-best list, plus ce_weight times the masked CE of the reference transcript.
-    Optimizer, gradient reduction, status row, poll / finish contract and NaN-skip accounting are ASRTrainStep's.
+    Optimizer, gradient reduction, status row, the step around the loss and NaN-skip accounting are ASRTrainStep's,
+    inherited (its att_on_host switch too: only ASR.forward reads it, which this loss does not call).
 
     forward_loss: the Listener runs ONCE on the batch (blstm_4 recurs over the utterance axis, so a batch of
     repeated utterances would be encoded differently); a beam search without grad on those very features gives K
@@ -148,34 +194,24 @@ class MWERTrainStep:
             raise ValueError('sampling draws from the model alone: lm_weight must be 0 with it, got %r' % (lm_weight,))
         if seed is not None and (isinstance(seed, bool) or int(seed) != seed or seed < 0):
             raise ValueError('seed must be None or an integer >= 0, got %r' % (seed,))
-        if not next(model.parameters()).is_cuda:
-            raise RuntimeError('MWERTrainStep needs the model on the GPU (no CPU path)')
-        self.model, self.beam_size, self.ce_weight, self.unit = model, beam_size, float(ce_weight), unit
+        self._set_up_asr(model, lr, eps, rho, grad_clip)
+        self.beam_size, self.ce_weight, self.unit = beam_size, float(ce_weight), unit
         self.lm, self.lm_weight, self.max_decoding_steps = lm, float(lm_weight), int(max_decoding_steps)
         self.eos = EOS_INDEX if eos is None else int(eos)
         self.space = (TOKENS + ALL_CHARS).index(' ') if space is None else int(space)
         self.first_char = TOKENS.index(UNK_TKN)             # `<` (the pad) and `>` are dropped before scoring
-        self.flat = FlatParameters.of(model)
-        sdist.broadcast_flat(self.flat.data)
-        self.optim = FusedAdadelta(self.flat, lr=lr, rho=rho, eps=eps)
-        self.grad_clip = grad_clip
-        self.reducer = sdist.GradReducer(self.flat, list(model.encoder.blstm_1.parameters()))
-        ops.set_wgrad_listener(self.reducer.wgrad_enqueued)
-        self._one = torch.ones((), device=self.flat.data.device)
         self._ref_of = {}
         self.sampling = bool(sampling)
         self.generator = None          # sampling: the source of search()'s uniforms
         if self.sampling:
             self.generator = torch.Generator(device=self.flat.data.device)
             self.generator.manual_seed(torch.initial_seed() if seed is None else int(seed))
-        self.last_logits = None        # [B * (K + 1), U, V] of the most recent step
+        # last_logits: [B * (K + 1), U, V] of the most recent step
         self.last_rows = None          # int32 [B * (K + 1), L]: its teacher / label rows
         self.last_hyps = None          # (chars [B, K, steps], n_chars [B, K], n_hyps [B]) it was given or searched
         self.last_counts = None        # int32 [B * (K + 1), 8]: every row's edit counts against its reference
         self.last_risk = None          # float [B]: the expected risk per utterance, on the device
         self.last_info = None          # ops.MWERInfo of its loss (p_hat, logp, weight, lse)
-        self.last_done = None
-        self.skipped_steps = 0
 
     def search(self, feat, enc_len_dev):
         """The n-best list of this batch's own features (sampling: K draws per utterance), without grad:
@@ -233,28 +269,11 @@ class MWERTrainStep:
         return loss, logits
 
     def __call__(self, x, y, x_lens, hyps=None):
-        """One train step; returns the loss tensor (on the device).  The previous step's verdict is picked up
-        here without a synchronisation, as in ASRTrainStep."""
-        self._note(self.optim.poll())
-        ops.set_wgrad_listener(self.reducer.wgrad_enqueued)
-        if not self.flat.clean:
-            self.optim.zero_grad()
-        self.flat.clean = False
-        self.reducer.begin()
-        with ops.shared_status_row(self.optim.status_row):
-            loss, _ = self.forward_loss(x, y, x_lens, hyps)
-            loss.backward(self._one)
-        scale = self.reducer.finish()
-        self.optim.clip_and_step(self.grad_clip, grad_scale=scale, zero_grad=True)
-        self.flat.clean = True
-        settle_collector()
-        return loss
-
-    _note = ASRTrainStep._note
-    finish = ASRTrainStep.finish
+        """One train step (ASRTrainStep's, around this loss); returns the loss tensor (on the device)."""
+        return super().__call__(x, y, x_lens, hyps)
 
 
-class TAETrainStep:
+class TAETrainStep(TrainStep):
     """One TAETrainer step (the body of TAETrainer.exec, src/trainer.py:652-677) as a reusable object: the
     text autoencoder's forward through the shared attend-and-spell loop (text_autoencoder.py), the loss of
     :662-672, backward, gradient all-reduce across ranks, then Solver.step as the reference calls it --
@@ -265,8 +284,7 @@ class TAETrainStep:
     the same storage, in turn: the two legs of the Seed loop (src/trainer.py:1126-1177) this build has."""
 
     def __init__(self, asr_model, tae_model, lr=1e-4, eps=1e-8, grad_clip=5.0):
-        if not next(tae_model.parameters()).is_cuda or not next(asr_model.parameters()).is_cuda:
-            raise RuntimeError('TAETrainStep needs both models on the GPU (no CPU path)')
+        self._models_on_gpu('both models', tae_model, asr_model)
         self.asr, self.tae = asr_model, tae_model
         self.asr_flat = FlatParameters.of(asr_model)
         self.tae_flat = FlatParameters.of(tae_model)
@@ -278,11 +296,8 @@ class TAETrainStep:
         self.optim = FusedAdam([(self.tae_flat.data, self.tae_flat.grad, True),
                                 (self.asr_flat.data[self.lo:self.hi], self.asr_flat.grad[self.lo:self.hi], False)],
                                lr=lr, eps=eps)
-        self.grad_clip = grad_clip
-        self._one = torch.ones((), device=self.tae_flat.data.device)
+        self._set_up([self.tae_flat, self.asr_flat], [('last_done', self.optim)], grad_clip)
         self.last_logits = None
-        self.last_done = None
-        self.skipped_steps = 0
 
     def forward_loss(self, y, y_noise, decode_step, noise_lens):
         from .text_autoencoder import tae_loss
@@ -291,48 +306,37 @@ class TAETrainStep:
 
     def __call__(self, y, y_noise, y_lens, noise_lens):
         """y [B, L] clean label rows, y_noise [B, <= L] noised rows (int64, on the GPU), their prepare_y
-        lengths.  Returns the loss tensor.  The previous step's verdict (norm, NaN skip, time-outs) is
-        picked up here without a synchronisation, as in ASRTrainStep."""
-        self._note(self.optim.poll())
-        ops.set_wgrad_listener(None)          # (an ASRTrainStep's reducer must not see this pass's gradients)
-        for flat in (self.tae_flat, self.asr_flat):
-            if not flat.clean:
-                flat.zero_grad()
-        self.tae_flat.clean = self.asr_flat.clean = False
+        lengths.  Returns the loss tensor."""
+        self._open()
         with ops.shared_status_row(self.optim.status_row):
             loss, self.last_logits = self.forward_loss(y, y_noise, max(y_lens), noise_lens)
             loss.backward(self._one)
         scale = sdist.allreduce_grad(self.tae_flat.grad)
         sdist.allreduce_grad(self.asr_flat.grad[self.lo:self.hi])
-        self.optim.clip_and_step(self.grad_clip, grad_scale=scale, zero_grad=True)
-        # the Listener's gradients were never touched by this pass: the whole ASR buffer is clean again
-        self.tae_flat.clean = self.asr_flat.clean = True
-        settle_collector()
+        # (the Listener's gradients were never touched by this pass: the whole ASR buffer is clean again)
+        self._update(scale)
         return loss
 
-    _note = ASRTrainStep._note
-    finish = ASRTrainStep.finish
 
-
-class CharLMTrainStep:
+class CharLMTrainStep(TrainStep):
     """One CHARLMTrainer step (src/trainer.py:229-251) as a reusable object: the chunk loop as ONE forward
     launch (ops.charlm_chunk; teacher forcing flipped per step on the host as the reference's random.random()
     does, :241, the sampled steps drawn in the kernel from device uniforms), ONE backward launch, the parameter
     gradients as deferred products, then Solver.step -- norm, NaN guard, clip at 5 -- fused with
     torch.optim.Adam(lr, eps=1e-8) (:215-218) over the model's one flat buffer."""
 
+    claims_listener = False            # nothing in its two launches notifies the listener
+
     def __init__(self, lm, tf_rate, lr=1e-4, eps=1e-8, grad_clip=5.0, opt_type='Adam'):
         if opt_type != 'Adam':
             raise NotImplementedError("char_lm.opt.type '%s': the fused CharLM step has Adam only" % opt_type)
-        if not next(lm.parameters()).is_cuda:
-            raise RuntimeError('CharLMTrainStep needs the model on the GPU (no CPU path)')
-        self.lm, self.tf_rate, self.grad_clip = lm, float(tf_rate), grad_clip
+        self._models_on_gpu('the model', lm)
+        self.lm, self.tf_rate = lm, float(tf_rate)
         self.flat = FlatParameters.of(lm)
         self.optim = FusedAdam([(self.flat.data, self.flat.grad, True)], lr=lr, eps=eps)
+        self._set_up([self.flat], [('last_done', self.optim)], grad_clip)
         self._ws = None
-        self.last_done = None
         self.last_chunk = None
-        self.skipped_steps = 0
 
     def draw_modes(self, U):
         """0 teacher / 1 sample per step, the reference's coin (src/trainer.py:241)."""
@@ -341,10 +345,7 @@ class CharLMTrainStep:
 
     def __call__(self, y, modes=None, uniforms=None, feed=None):
         """y [B, U] labels on the GPU.  Returns the loss tensor (mean over the batch of the per-row sums, :249)."""
-        self._note(self.optim.poll())
-        if not self.flat.clean:
-            self.flat.zero_grad()
-        self.flat.clean = False
+        self._open()
         B, U = y.shape
         dev = y.device
         if modes is None:
@@ -357,15 +358,9 @@ class CharLMTrainStep:
         chunk = ops.charlm_chunk(self.lm, y, feed=feed, modes=modes, uniforms=uniforms, ws=self._ws)
         self._ws = chunk.ws
         ops.charlm_chunk_backward(self.lm, chunk, dloss=1.0 / B)
-        scale = sdist.allreduce_grad(self.flat.grad)
-        self.optim.clip_and_step(self.grad_clip, grad_scale=scale, zero_grad=True)
-        self.flat.clean = True
         self.last_chunk = chunk
-        settle_collector()
+        self._update(sdist.allreduce_grad(self.flat.grad))
         return chunk.loss_rows.mean()
-
-    _note = ASRTrainStep._note
-    finish = ASRTrainStep.finish
 
 
 def label_geometry(y_cpu):
@@ -386,7 +381,7 @@ def _fused_optimizer(kind, flat, span, lr, eps=1e-8):
     return None
 
 
-class ADVTrainStep:
+class ADVTrainStep(TrainStep):
     """One ADVTrainer iteration (src/trainer.py:968-1032) as a reusable object: the discriminator is trained to
     score the text encoder's frames high (labels 1 - label_smoothing) and the Listener's low (labels 0), then
     the Listener -- the generator -- to be scored high (labels 1) by the UPDATED discriminator; Solver.step
@@ -402,9 +397,7 @@ class ADVTrainStep:
 
     def __init__(self, asr_model, tae_model, discriminator, g_opt=('Adadelta', 1.0), d_opt=('Adadelta', 1.0),
                  label_smoothing=0.1, grad_clip=5.0):
-        for m in (asr_model, tae_model, discriminator):
-            if not next(m.parameters()).is_cuda:
-                raise RuntimeError('ADVTrainStep needs every model on the GPU (no CPU path)')
+        self._models_on_gpu('every model', asr_model, tae_model, discriminator)
         self.asr, self.tae, self.disc = asr_model, tae_model, discriminator
         self.asr_flat = FlatParameters.of(asr_model)
         self.d_flat = FlatParameters.of(discriminator)
@@ -421,11 +414,8 @@ class ADVTrainStep:
             raise NotImplementedError('ADVTrainStep: optimizer types %r / %r (Adadelta and Adam have kernels)'
                                       % (g_opt[0], d_opt[0]))
         self.label_smoothing = float(label_smoothing)
-        self.grad_clip = grad_clip
-        self._one = torch.ones((), device=self.d_flat.data.device)
-        self.last_done = None          # (generator grad norm, skipped) of the last finished iteration
-        self.last_done_d = None
-        self.skipped_steps = 0
+        # D's verdict is polled first; last_done is the generator's (grad norm, skipped) of the last finished iteration
+        self._set_up([self.d_flat, self.asr_flat], [('last_done_d', self.D_optim), ('last_done', self.G_optim)], grad_clip)
 
     def frames(self, x, x_lens, y):
         """The two encoders' frames: (real [B, seq, 512] from the text encoder, no graph; fake [B, T', 512] from
@@ -439,16 +429,7 @@ class ADVTrainStep:
         """x [B, T, F] padded fbanks, x_lens host list (descending), y [B, L] label rows (int64), all on
         the GPU.  Returns (D_realloss, D_fakeloss, G_loss) device tensors."""
         from .seed_ops import bce_loss
-        done = self.D_optim.poll()
-        if done is not None:
-            self.last_done_d = done
-            self.skipped_steps += int(done[1])
-        self._note(self.G_optim.poll())
-        ops.set_wgrad_listener(None)
-        for flat in (self.d_flat, self.asr_flat):
-            if not flat.clean:
-                flat.zero_grad()
-        self.d_flat.clean = self.asr_flat.clean = False
+        self._open()
         lo, hi = self.span
         with ops.shared_status_row(self.G_optim.status_row):
             # --- discriminator: maximise log D(real) + log(1 - D(G(x)))
@@ -463,25 +444,13 @@ class ADVTrainStep:
             # --- generator: maximise log D(G(x)), through the discriminator just updated
             g_loss = bce_loss(self.disc(fake, frozen=True), 1.0)
             g_loss.backward(self._one)
-        scale = sdist.allreduce_grad(self.asr_flat.grad[lo:hi])
-        self.G_optim.clip_and_step(self.grad_clip, grad_scale=scale, zero_grad=True)
-        self.asr_flat.clean = True         # (nothing behind the Listener was touched by this pass)
-        settle_collector()
+        # G_optim's update; nothing behind the Listener was touched by this pass, and the frozen discriminator of the
+        # generator pass took no gradient: both buffers are clean
+        self._update(sdist.allreduce_grad(self.asr_flat.grad[lo:hi]))
         return d_real, d_fake, g_loss
 
-    _note = ASRTrainStep._note
 
-    def finish(self):
-        """Waits for the last iteration's words of BOTH optimizers; raises on a persistent time-out."""
-        done = self.D_optim.poll(wait=True)
-        if done is not None:
-            self.last_done_d = done
-            self.skipped_steps += int(done[1])
-        self._note(self.G_optim.poll(wait=True))
-        return self.last_done
-
-
-class SAETrainStep:
+class SAETrainStep(TrainStep):
     """One SAETrainer iteration (src/trainer.py:803-820) as a reusable object: the shared Listener, the speech
     autoencoder over its output and the raw frames, smooth-L1 against the input frames (:811-818), backward,
     gradient all-reduce, then Solver.step as the reference calls it -- norm, NaN guard and clip over the SPEECH
@@ -491,8 +460,7 @@ class SAETrainStep:
     single-device; they do not enter the training arithmetic)."""
 
     def __init__(self, asr_model, sae_model, opt=('Adam', 1e-4), grad_clip=5.0):
-        if not next(sae_model.parameters()).is_cuda or not next(asr_model.parameters()).is_cuda:
-            raise RuntimeError('SAETrainStep needs both models on the GPU (no CPU path)')
+        self._models_on_gpu('both models', sae_model, asr_model)
         if opt[0] != 'Adam':
             raise NotImplementedError('SAETrainStep: optimizer type %r (Adam has the kernel whose clipped range may '
                                       'differ from its update range)' % (opt[0],))
@@ -506,13 +474,10 @@ class SAETrainStep:
         self.optim = FusedAdam([(self.sae_flat.data, self.sae_flat.grad, True),
                                 (self.asr_flat.data[self.lo:self.hi], self.asr_flat.grad[self.lo:self.hi], False)],
                                lr=opt[1], eps=1e-8)
-        self.grad_clip = grad_clip
+        self._set_up([self.sae_flat, self.asr_flat], [('last_done', self.optim)], grad_clip)
         # SSASR_SAE_OVERLAP: 0 the speech encoder behind the Listener on one stream, 1 / 2 see forward_loss (same results)
         self.overlap = int(os.environ.get('SSASR_SAE_OVERLAP', '1'))
-        self._one = torch.ones((), device=self.sae_flat.data.device)
         self.last_pred = None          # [B, 8 T', F] of the most recent step (for the trainer's figures)
-        self.last_done = None
-        self.skipped_steps = 0
 
     def forward_loss(self, x, x_lens):
         """Listener and global speech encoder both read the fbanks and nothing of each other.  With `overlap` the speech
@@ -544,12 +509,7 @@ class SAETrainStep:
     def __call__(self, x, x_lens):
         """x [B, T, F] padded fbanks on the GPU (T: the corpus' padding, >= max(x_lens)), x_lens host list
         (descending).  Returns the loss tensor."""
-        self._note(self.optim.poll())
-        ops.set_wgrad_listener(None)
-        for flat in (self.sae_flat, self.asr_flat):
-            if not flat.clean:
-                flat.zero_grad()
-        self.sae_flat.clean = self.asr_flat.clean = False
+        self._open()
         with ops.shared_status_row(self.optim.status_row):
             loss, self.last_pred = self.forward_loss(x, x_lens)
             loss.backward(self._one)
@@ -558,10 +518,5 @@ class SAETrainStep:
         ops.join_side_stream()
         scale = sdist.allreduce_grad(self.sae_flat.grad)
         sdist.allreduce_grad(self.asr_flat.grad[self.lo:self.hi])
-        self.optim.clip_and_step(self.grad_clip, grad_scale=scale, zero_grad=True)
-        self.sae_flat.clean = self.asr_flat.clean = True      # (nothing behind the Listener was touched)
-        settle_collector()
+        self._update(scale)            # (nothing behind the Listener was touched: the whole ASR buffer is clean again)
         return loss
-
-    _note = ASRTrainStep._note
-    finish = ASRTrainStep.finish

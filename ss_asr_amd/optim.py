@@ -75,51 +75,23 @@ class FlatParameters:
                 p.grad = self.grad[o:o + p.numel()].view(p.shape)
 
 
-class FusedAdadelta(torch.optim.Optimizer):
-    """torch.optim.Adadelta(lr, rho, eps, weight_decay=0) over FlatParameters,
-    fused with clip_grad_norm_ and the NaN guard of Solver.step."""
+class StepWords:
+    """What both fused optimizers tell the host about a step, in ONE asynchronous copy: [grad_norm, skipped]
+    written by the update kernel (`stats`), then the int32[8] `status_row` of the step's persistent launches
+    (ops.shared_status_row; words 4 / 5 turn non-zero when a launch timed out)."""
 
-    def __init__(self, flat, lr=1.0, rho=0.9, eps=1e-6, span=None):
-        """span (begin, end): the optimizer owns only that run of the flat buffer (FlatParameters.range_of) --
-        ADVTrainer's generator optimizer holds the Listener alone (src/trainer.py:940-943), a run of the ASR
-        model's buffer; norm, NaN guard, clip and update then cover that run."""
-        self.flat = flat
-        lo, hi = span if span is not None else (0, flat.numel)
-        self._data, self._grad = flat.data[lo:hi], flat.grad[lo:hi]
-        owned = [p for p, o in zip(flat.params, flat.offsets) if lo <= o < hi]
-        super().__init__(owned, dict(lr=lr, rho=rho, eps=eps))
-        dev = flat.data.device
-        self.square_avg = torch.zeros_like(self._data)
-        self.acc_delta = torch.zeros_like(self._data)
-        self._ws = ops.clip_adadelta_ws(hi - lo, dev)
-        # per-step words that reach the host in ONE asynchronous copy: [grad_norm, skipped] written
-        # by the update kernel, then the int32[8] status row of the step's persistent launches
-        # (ops.shared_status_row; words 4 / 5 turn non-zero when a launch timed out)
+    def _init_words(self, dev):
         self._words = torch.zeros(2 + 8, device=dev)
         self.stats = self._words[:2]
         self.status_row = self._words[2:].view(torch.int32)
         self._host_words = torch.zeros(2 + 8, pin_memory=dev.type == 'cuda')
         self._pending = None
 
-    def zero_grad(self, set_to_none=False):
-        self.flat.zero_grad()
-
-    def clip_and_step(self, max_norm=5.0, grad_scale=1.0, zero_grad=False):
-        """zero_grad=True leaves the flat gradient zeroed (the next step's zero_grad()
-        folded into the update kernel)."""
-        ops.join_side_stream()       # weight gradients enqueued on the side stream
-        g = self.param_groups[0]
-        ops.clip_adadelta_(self._data, self._grad, self.square_avg, self.acc_delta,
-                           self._ws, self.stats, grad_scale=grad_scale, max_norm=max_norm,
-                           lr=g['lr'], rho=g['rho'], eps=g['eps'], zero_grad=zero_grad)
-        # the norm / NaN flag / status row reach the host asynchronously; see poll()
+    def _send_words(self):
+        """The tail of clip_and_step: the words set out for the host; poll() picks them up."""
         self._host_words.copy_(self._words, non_blocking=True)
         self._pending = torch.cuda.Event()
         self._pending.record()
-
-    def step(self, closure=None):
-        """Plain optimizer step (no clipping): max_norm = inf."""
-        self.clip_and_step(max_norm=float('inf'))
 
     def poll(self, wait=False):
         """Returns (grad_norm, skipped) of the most recent finished step, or None when there is
@@ -139,7 +111,44 @@ class FusedAdadelta(torch.optim.Optimizer):
         return float(self._host_words[0]), bool(self._host_words[1] != 0)
 
 
-class FusedAdam:
+class FusedAdadelta(StepWords, torch.optim.Optimizer):
+    """torch.optim.Adadelta(lr, rho, eps, weight_decay=0) over FlatParameters,
+    fused with clip_grad_norm_ and the NaN guard of Solver.step."""
+
+    def __init__(self, flat, lr=1.0, rho=0.9, eps=1e-6, span=None):
+        """span (begin, end): the optimizer owns only that run of the flat buffer (FlatParameters.range_of) --
+        ADVTrainer's generator optimizer holds the Listener alone (src/trainer.py:940-943), a run of the ASR
+        model's buffer; norm, NaN guard, clip and update then cover that run."""
+        self.flat = flat
+        lo, hi = span if span is not None else (0, flat.numel)
+        self._data, self._grad = flat.data[lo:hi], flat.grad[lo:hi]
+        owned = [p for p, o in zip(flat.params, flat.offsets) if lo <= o < hi]
+        super().__init__(owned, dict(lr=lr, rho=rho, eps=eps))
+        dev = flat.data.device
+        self.square_avg = torch.zeros_like(self._data)
+        self.acc_delta = torch.zeros_like(self._data)
+        self._ws = ops.clip_adadelta_ws(hi - lo, dev)
+        self._init_words(dev)
+
+    def zero_grad(self, set_to_none=False):
+        self.flat.zero_grad()
+
+    def clip_and_step(self, max_norm=5.0, grad_scale=1.0, zero_grad=False):
+        """zero_grad=True leaves the flat gradient zeroed (the next step's zero_grad()
+        folded into the update kernel)."""
+        ops.join_side_stream()       # weight gradients enqueued on the side stream
+        g = self.param_groups[0]
+        ops.clip_adadelta_(self._data, self._grad, self.square_avg, self.acc_delta,
+                           self._ws, self.stats, grad_scale=grad_scale, max_norm=max_norm,
+                           lr=g['lr'], rho=g['rho'], eps=g['eps'], zero_grad=zero_grad)
+        self._send_words()
+
+    def step(self, closure=None):
+        """Plain optimizer step (no clipping): max_norm = inf."""
+        self.clip_and_step(max_norm=float('inf'))
+
+
+class FusedAdam(StepWords):
     """torch.optim.Adam(lr, betas, eps, weight_decay=0, amsgrad=False) fused with Solver.step's clip and NaN
     guard, over parameters that live in SEVERAL flat buffers: TAETrainer's optimizer holds the text
     autoencoder and the ASR model's embed / attention / decoder / char_trans (src/trainer.py:633-641), and
@@ -159,11 +168,7 @@ class FusedAdam:
         self.exp_avg_sq = [torch.zeros_like(d) for d, _, _ in self.segments]
         self.state_step = torch.zeros(1, device=dev)
         self._ws = torch.empty(int(ops._lib.load().ssasr_adam_ws(clipped[0][1].numel())), device=dev)
-        self._words = torch.zeros(2 + 8, device=dev)
-        self.stats = self._words[:2]
-        self.status_row = self._words[2:].view(torch.int32)
-        self._host_words = torch.zeros(2 + 8, pin_memory=dev.type == 'cuda')
-        self._pending = None
+        self._init_words(dev)
 
     def clip_and_step(self, max_norm=5.0, grad_scale=1.0, zero_grad=False):
         ops.join_side_stream()
@@ -173,8 +178,4 @@ class FusedAdam:
         for (d, g, c), m, v in zip(self.segments, self.exp_avg, self.exp_avg_sq):
             ops.adam_update_(d, g, m, v, self._ws, self.stats, clipped=c, grad_scale=grad_scale, betas=self.betas,
                              eps=self.eps, zero_grad=zero_grad)
-        self._host_words.copy_(self._words, non_blocking=True)
-        self._pending = torch.cuda.Event()
-        self._pending.record()
-
-    poll = FusedAdadelta.poll
+        self._send_words()

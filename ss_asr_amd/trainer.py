@@ -158,6 +158,105 @@ class Solver:
         return None
 
 
+class Trainer(Solver):
+    """The epoch loop, the best-checkpoint rule and close() of ASRTrainer, TAETrainer, ADVTrainer and SAETrainer.  A
+    subclass supplies `_prepare` (a loader's batch on the device: the arguments of its engine step object, which is
+    `self.train_step`, or None when the config's optimizer has no fused form), `_reference` (the reference's sequence
+    with a torch optimizer), `_log` (rank 0's scalars at a logging step) and `_checkpoint` (what is saved where)."""
+
+    # Within an iteration the reference's ASRTrainer checkpoints BEFORE it validates (src/trainer.py:448-455); its
+    # TAETrainer (:682-686), SAETrainer (:827-831) and ADVTrainer (:1035-1040) validate first.
+    save_before_valid = False
+    batches_line = 'Training set total {} batches'
+    close_line_end = ' as well as the ASR model'
+    # valid() of the reference's ADVTrainer says nothing when the metric is no better (src/trainer.py:1106-1112);
+    # the others do (:534, :748, :894)
+    reports_worse = True
+
+    def _train_batches(self):
+        """(batch index, _prepare's batch) for this rank's batches of one epoch.  Every rank yields the same number:
+        a tail that does not fill a round of `world` batches is dropped (a rank alone in an all-reduce would wait
+        for ever)."""
+        from .gpu_loader import rank_batches
+        mine = set(rank_batches(len(self.train_set), self.rank, self.world))
+        for b_ind, raw in enumerate(self.train_set):
+            if b_ind in mine:
+                yield b_ind, self._prepare(raw)
+
+    def _fused(self, batch):
+        """One call of the engine step object on _prepare's batch -> what _log takes."""
+        return self.train_step(*batch)
+
+    def _log_own_cadence(self, result):
+        """Rank 0, every iteration: scalars on a step count of the trainer's own."""
+
+    def _save(self):
+        for module, path in self._checkpoint():
+            sdist.save_atomic(module.state_dict(), path)
+
+    def exec(self):
+        self.verbose(self.batches_line.format(len(self.train_set)))
+        nan_reported = self.train_step.skipped_steps if self.train_step is not None else 0
+        for epoch in range(self.n_epochs):
+            self.verbose("Starting epoch {} out of {}".format(epoch + 1, self.n_epochs))
+            for b_ind, batch in self._train_batches():
+                self.verbose('Batch: {}/{}, global step: {}'.format(b_ind, len(self.train_set), self.tr.step),
+                             progress=True)
+                if self.train_step is not None:
+                    # one fused step; a persistent launch that timed out in the previous step raises here (its status
+                    # words arrive with the optimizer's)
+                    result = self._fused(batch)
+                    if self.train_step.skipped_steps > nan_reported:
+                        nan_reported = self.train_step.skipped_steps
+                        self.verbose('Error : grad norm is NaN @ step {}'.format(self.tr.step - 1))
+                else:
+                    result = self._reference(batch)
+                    if self.tr.step % self.logging_step == 0:
+                        ops.check_persistent_status()      # the host synchronises here anyway
+                if self.rank == 0:
+                    if self.tr.step % self.logging_step == 0:
+                        self._log(result)
+                    self._log_own_cadence(result)
+                if self.save_before_valid:
+                    self._save_at_save_step()
+                if self.tr.step % self.valid_step == 0:
+                    self.valid()
+                if not self.save_before_valid:
+                    self._save_at_save_step()
+                self.tr.do_step()
+        if self.train_step is not None:
+            self.train_step.finish()           # the last step's verdict (raises on a timeout)
+
+    def _save_at_save_step(self):
+        if self.rank == 0 and self.tr.step % self.save_step == 0:
+            if self.train_step is not None:
+                self.train_step.finish()       # this step's verdict first: never checkpoint after a time-out
+            self.verbose("Model saved at step {}".format(self.tr.step))
+            self._save()
+
+    def _keep_best(self, avg_loss, module, lines=('Best validation loss : {:.4f} @ global step {}',)):
+        """The tail of valid() on rank 0: a metric below the tracker's best becomes the best, is announced with
+        `lines` and `module` goes to the best-checkpoint file.  -> whether it was."""
+        if avg_loss < self.tr.get_best():
+            self.tr.set_best(avg_loss)
+            for line in lines:
+                self.verbose(line.format(self.tr.get_best(), self.tr.step))
+            sdist.save_atomic(module.state_dict(), self.best_ckppath)
+            return True
+        if self.reports_worse:
+            self.verbose("Validation metric worse : ({:.4f} vs. {:.4f})".format(avg_loss, self.tr.get_best()))
+        return False
+
+    def close(self):
+        self.verbose("Finished training! The most recent model will" +
+                     "be saved at step {}{}".format(self.tr.step, self.close_line_end))
+        if getattr(self, 'train_step', None) is not None:
+            self.train_step.finish()
+        if self.rank == 0:
+            self._save()
+        sdist.barrier()        # the next reader of these files (the Seed loop's next leg) runs on every rank
+
+
 class CHARLMTrainer(Solver):
     """Trains the character language model, src/trainer.py:197-372: the same config keys (char_lm.chunk_size,
     mdl.tf_rate, mdl.hidden_size, opt.type, opt.learning_rate, train_index), loss per character, tracker best,
@@ -248,7 +347,7 @@ class CHARLMTrainer(Solver):
 LMTrainer = CHARLMTrainer
 
 
-class ASRTrainer(Solver):
+class ASRTrainer(Trainer):
     """src/trainer.py:377-537.  BUILD-DEFINED keys (the reference's recipe has neither; both absent: off, and
     training is the reference's plain masked CE on unaugmented filterbanks):
     asr.label_smoothing in [0, 1): the train loss is the smoothed CE of ops.masked_ce_loss (the attention branch
@@ -384,20 +483,14 @@ class ASRTrainer(Solver):
                                'keep on the device): refusing to train unaugmented')
 
     def _train_batches(self):
-        """(batch index, x, x_lens, y, y_lens) for this rank's batches of one epoch.  Every rank
-        yields the same number of batches: a tail that does not fill a round of `world` batches
-        is dropped (a rank alone in an all-reduce would wait for ever)."""
-        if self.gpu_loader is not None:
-            yield from self.gpu_loader
-            return
-        from .gpu_loader import rank_batches
-        mine = set(rank_batches(len(self.train_set), self.rank, self.world))
-        for b_ind, (x, y) in enumerate(self.train_set):
-            if b_ind not in mine:
-                continue
-            (x, x_lens) = prepare_x(x, device=self.device)
-            (y, y_lens) = prepare_y(y, device=self.device)
-            yield b_ind, x, x_lens, y, y_lens
+        """The resident loader deals this rank's batches itself, already on the device."""
+        if self.gpu_loader is None:
+            return super()._train_batches()
+        return ((b_ind, batch) for b_ind, *batch in self.gpu_loader)
+
+    def _prepare(self, raw):
+        """-> [x, x_lens, y, y_lens]"""
+        return [*prepare_x(raw[0], device=self.device), *prepare_y(raw[1], device=self.device)]
 
     def set_model(self, asrpath=None):
         """asrpath (this build; the Seed loop passes it): (checkpoint to load, checkpoint to save) instead of
@@ -440,62 +533,46 @@ class ASRTrainer(Solver):
             return ops.masked_ce_loss(prediction, y, ans_len, label_smoothing)
         raise RuntimeError('ss_asr_amd computes on the GPU only')
 
-    def exec(self):
-        self.verbose('Training set total {} batches'.format(len(self.train_set)))
-        self._nan_reported = self.train_step.skipped_steps if self.train_step is not None else 0
-        epoch = 0
-        while epoch < self.n_epochs:
-            self.verbose("Starting epoch {} out of {}".format(epoch + 1, self.n_epochs))
-            for b_ind, x, x_lens, y, y_lens in self._train_batches():
-                self.verbose('Batch: {}/{}, global step: {}'.format(
-                    b_ind, len(self.train_set), self.tr.step), progress=True)
-                state_len = x_lens
-                ans_len = max(y_lens) - 1
+    save_before_valid = True
+    close_line_end = ''
 
-                if self.train_step is not None:
-                    # src/trainer.py:419-438 as one fused step; a persistent launch that timed out
-                    # in the previous step raises here (its status words arrive with the optimizer's)
-                    if self.mwer is not None:
-                        loss = self.train_step(x, y, state_len)
-                        # the reference rows of the teacher-forced pass are the CE step's logits
-                        prediction = self.train_step.last_logits[self.mwer['beam_size']::self.mwer['beam_size'] + 1]
-                        prediction = prediction[:, :ans_len]
-                    else:
-                        loss = self.train_step(x, y, state_len, ans_len)
-                        prediction = self.train_step.last_logits
-                    if self.train_step.skipped_steps > self._nan_reported:
-                        self._nan_reported = self.train_step.skipped_steps
-                        self.verbose('Error : grad norm is NaN @ step {}'.format(self.tr.step - 1))
-                else:
-                    self.optim.zero_grad()
-                    _, prediction, _ = self.asr_model(x, ans_len, teacher=y, state_len=state_len)
-                    loss = self._loss(prediction, y, ans_len, self.label_smoothing)
-                    loss.backward()
-                    self.step(self.asr_model.parameters(), self.optim)
-                    if self.tr.step % self.logging_step == 0:
-                        ops.check_persistent_status()      # the host synchronises here anyway
-                label = y[:, 1:ans_len + 1]
-                if self.rank == 0:
-                    if self.tr.step % self.logging_step == 0:
-                        self.lg.scalar('train_loss', loss.item(), self.tr.step)
-                        if self.mwer is not None:
-                            self.lg.scalar('mwer_risk', self.train_step.last_risk.mean().item(), self.tr.step)
-                        self.lg.scalar('train_acc', calc_acc(prediction, label), self.tr.step)
-                    if self.tr.step % self.wer_step == 0:
-                        self.lg.scalar('train_error',
-                                       calc_err(prediction, label, mapper=self.mapper),
-                                       self.tr.step)
-                    if self.tr.step % self.save_step == 0:
-                        if self.train_step is not None:
-                            self.train_step.finish()   # this step's verdict first: never checkpoint after a time-out
-                        self.verbose("Model saved at step {}".format(self.tr.step))
-                        sdist.save_atomic(self.asr_model.state_dict(), self.ckppath)
-                if self.tr.step % self.valid_step == 0:
-                    self.valid()
-                self.tr.do_step()
-            epoch += 1
-        if self.train_step is not None:
-            self.train_step.finish()           # the last step's verdict (raises on a timeout)
+    def _fused(self, batch):
+        """src/trainer.py:419-438 as one fused step -> (loss, logits [B, ans_len, V], labels [B, ans_len])."""
+        x, x_lens, y, y_lens = batch
+        ans_len = max(y_lens) - 1
+        if self.mwer is None:
+            loss = self.train_step(x, y, x_lens, ans_len)
+            prediction = self.train_step.last_logits
+        else:
+            loss = self.train_step(x, y, x_lens)
+            # the reference rows of the teacher-forced pass are the CE step's logits
+            prediction = self.train_step.last_logits[self.mwer['beam_size']::self.mwer['beam_size'] + 1]
+            prediction = prediction[:, :ans_len]
+        return loss, prediction, y[:, 1:ans_len + 1]
+
+    def _reference(self, batch):
+        x, x_lens, y, y_lens = batch
+        ans_len = max(y_lens) - 1
+        self.optim.zero_grad()
+        _, prediction, _ = self.asr_model(x, ans_len, teacher=y, state_len=x_lens)
+        loss = self._loss(prediction, y, ans_len, self.label_smoothing)
+        loss.backward()
+        self.step(self.asr_model.parameters(), self.optim)
+        return loss, prediction, y[:, 1:ans_len + 1]
+
+    def _log(self, result):
+        loss, prediction, label = result
+        self.lg.scalar('train_loss', loss.item(), self.tr.step)
+        if self.mwer is not None:
+            self.lg.scalar('mwer_risk', self.train_step.last_risk.mean().item(), self.tr.step)
+        self.lg.scalar('train_acc', calc_acc(prediction, label), self.tr.step)
+
+    def _log_own_cadence(self, result):
+        if self.tr.step % self.wer_step == 0:
+            self.lg.scalar('train_error', calc_err(result[1], result[2], mapper=self.mapper), self.tr.step)
+
+    def _checkpoint(self):
+        return ((self.asr_model, self.ckppath),)
 
     def valid(self):
         """Greedy decoding for ans_len + 30 steps without a teacher, loss on the
@@ -554,28 +631,12 @@ class ASRTrainer(Solver):
                 self.lg.image('eval_att_' + str(idx), attmap, self.tr.step)
                 self.lg.text('eval_hyp_' + str(idx), "{} |predict vs. real| {}".format(
                     val_hyp[idx], val_txt[idx]), self.tr.step)
-            if avg_loss < self.tr.get_best():
-                self.tr.set_best(avg_loss)
-                self.verbose('Best validation loss for ASR : {:.4f} @ global step {}'.format(
-                    self.tr.get_best(), self.tr.step))
-                self.verbose('Saving best model.')
-                sdist.save_atomic(self.asr_model.state_dict(), self.best_ckppath)
+            if self._keep_best(avg_loss, self.asr_model, ('Best validation loss for ASR : {:.4f} @ global step {}',
+                                                          'Saving best model.')):
                 with open(os.path.join(self.ckpdir, 'best_hyp.txt'), 'w') as f:
                     for hyp, txt in zip(val_hyp, val_txt):
                         f.write(hyp + ',' + txt + '\n')
-            else:
-                self.verbose("Validation metric worse : ({:.4f} vs. {:.4f})".format(
-                    avg_loss, self.tr.get_best()))
         self.asr_model.train()
-
-    def close(self):
-        self.verbose("Finished training! The most recent model will" +
-                     "be saved at step {}".format(self.tr.step))
-        if getattr(self, 'train_step', None) is not None:
-            self.train_step.finish()
-        if self.rank == 0:
-            sdist.save_atomic(self.asr_model.state_dict(), self.ckppath)
-        sdist.barrier()        # the next reader of these files (the Seed loop's next leg) runs on every rank
 
 
 class ASRTester(Solver):
@@ -786,7 +847,7 @@ class ASRTester(Solver):
         return results
 
 
-class TAETrainer(Solver):
+class TAETrainer(Trainer):
     """Trains the text autoencoder, and through it the ASR model's attention / speller / embedding /
     char_trans (src/trainer.py:594-758; config 5's first leg).  With Adam (conf/default.yaml:43-45) on the
     GPU one iteration of exec() is ONE engine.TAETrainStep call; any other optimizer type takes the
@@ -837,52 +898,26 @@ class TAETrainer(Solver):
             raise RuntimeError('ss_asr_amd computes on the GPU only')
         return tae_loss(enc_out, y)
 
-    def _rank_batches(self):
-        from .gpu_loader import rank_batches
-        mine = set(rank_batches(len(self.train_set), self.rank, self.world))
-        for b_ind, (y, y_noise) in enumerate(self.train_set):
-            if b_ind in mine:
-                yield b_ind, y, y_noise
+    def _prepare(self, raw):
+        """-> (y, y_noise, y_lens, y_noise_lens)"""
+        (y, y_lens), (y_noise, y_noise_lens) = (prepare_y(r, device=self.device) for r in raw)
+        return y, y_noise, y_lens, y_noise_lens
 
-    def exec(self):
-        self.verbose('Training set total {} batches'.format(len(self.train_set)))
-        nan_reported = self.train_step.skipped_steps if self.train_step is not None else 0
-        epoch = 0
-        while epoch < self.n_epochs:
-            self.verbose("Starting epoch {} out of {}".format(epoch + 1, self.n_epochs))
-            for b_ind, y, y_noise in self._rank_batches():
-                self.verbose('Batch: {}/{}, global step: {}'.format(
-                    b_ind, len(self.train_set), self.tr.step), progress=True)
-                y, y_lens = prepare_y(y, device=self.device)
-                y_noise, y_noise_lens = prepare_y(y_noise, device=self.device)
-                if self.train_step is not None:
-                    loss = self.train_step(y, y_noise, y_lens, y_noise_lens)
-                    if self.train_step.skipped_steps > nan_reported:
-                        nan_reported = self.train_step.skipped_steps
-                        self.verbose('Error : grad norm is NaN @ step {}'.format(self.tr.step - 1))
-                else:
-                    self.optim.zero_grad()
-                    # decode steps == longest target
-                    _, enc_out = self.text_autoenc(self.asr_model, y, y_noise, max(y_lens), noise_lens=y_noise_lens)
-                    loss = self._loss(enc_out, y)
-                    loss.backward()
-                    self.step(self.text_autoenc.parameters(), self.optim)
-                    if self.tr.step % self.logging_step == 0:
-                        ops.check_persistent_status()
-                if self.rank == 0 and self.tr.step % self.logging_step == 0:
-                    self.lg.scalar('train_loss', loss.item(), self.tr.step)
-                if self.tr.step % self.valid_step == 0:
-                    self.valid()
-                if self.rank == 0 and self.tr.step % self.save_step == 0:
-                    if self.train_step is not None:
-                        self.train_step.finish()       # never checkpoint after a time-out
-                    self.verbose("Model saved at step {}".format(self.tr.step))
-                    sdist.save_atomic(self.text_autoenc.state_dict(), self.ckppath)
-                    sdist.save_atomic(self.asr_model.state_dict(), self.asrpath_out)
-                self.tr.do_step()
-            epoch += 1
-        if self.train_step is not None:
-            self.train_step.finish()
+    def _reference(self, batch):
+        y, y_noise, y_lens, y_noise_lens = batch
+        self.optim.zero_grad()
+        # decode steps == longest target
+        _, enc_out = self.text_autoenc(self.asr_model, y, y_noise, max(y_lens), noise_lens=y_noise_lens)
+        loss = self._loss(enc_out, y)
+        loss.backward()
+        self.step(self.text_autoenc.parameters(), self.optim)
+        return loss
+
+    def _log(self, loss):
+        self.lg.scalar('train_loss', loss.item(), self.tr.step)
+
+    def _checkpoint(self):
+        return ((self.text_autoenc, self.ckppath), (self.asr_model, self.asrpath_out))
 
     def valid(self):
         """src/trainer.py:683-748."""
@@ -912,31 +947,16 @@ class TAETrainer(Solver):
         for i in range(min(self.valid_batch_size, len(labels))):
             self.lg.text('eval_text' + str(i), '{} |vs.| {}'.format(labels[i], predicts[i]), self.tr.step)
         self.lg.scalar('eval_loss', avg_loss, self.tr.step)
-        if avg_loss < self.tr.get_best():
-            self.tr.set_best(avg_loss)
-            self.verbose('Best validation loss : {:.4f} @ global step {}'.format(self.tr.get_best(), self.tr.step))
-            sdist.save_atomic(self.text_autoenc.state_dict(), self.best_ckppath)
+        if self._keep_best(avg_loss, self.text_autoenc):
             self.verbose("Both the text autoencoder and ASR have been saved")
-        else:
-            self.verbose("Validation metric worse : ({:.4f} vs. {:.4f})".format(avg_loss, self.tr.get_best()))
-
-    def close(self):
-        self.verbose("Finished training! The most recent model will" +
-                     "be saved at step {} as well as the ASR model".format(self.tr.step))
-        if getattr(self, 'train_step', None) is not None:
-            self.train_step.finish()
-        if self.rank == 0:
-            sdist.save_atomic(self.text_autoenc.state_dict(), self.ckppath)
-            sdist.save_atomic(self.asr_model.state_dict(), self.asrpath_out)
-        sdist.barrier()        # the next reader of these files (the Seed loop's next leg) runs on every rank
 
 
-class ADVTrainer(Solver):
+class ADVTrainer(Trainer):
     """Adversarial training of the Listener against the text encoder's frames (src/trainer.py:909-1124;
     config 5's second leg).  Generator: the ASR model's Listener; data distribution: the text autoencoder's
     encoder; discriminator: discriminator.Discriminator.  One iteration of exec() is ONE engine.ADVTrainStep
     call when G_opt / D_opt are Adadelta or Adam; any other optimizer type takes the reference's sequence with
-    torch optimizers (`_iteration`).
+    torch optimizers (`_reference`).
 
     The reference's ADVTrainer cannot run as shipped; what is fixed here, and
     nothing else: `self.loss_metric` (used at :984, never set) is nn.BCELoss -- on the ssasr_bce kernels; the
@@ -994,9 +1014,16 @@ class ADVTrainer(Solver):
         fake, _ = self.asr_model.encoder(x, x_lens)
         return real, fake
 
-    def _iteration(self, x, x_lens, y):
+    reports_worse = False
+
+    def _prepare(self, raw):
+        """-> (x, x_lens, y)"""
+        return (*prepare_x(raw[0], device=self.device), prepare_y(raw[1], device=self.device)[0])
+
+    def _reference(self, batch):
         """src/trainer.py:968-1032 with torch optimizers (the fused form is engine.ADVTrainStep)."""
         from .seed_ops import bce_loss
+        x, x_lens, y = batch
         self.discriminator.zero_grad()
         real, fake = self._frames(x, x_lens, y)
         D_realloss = bce_loss(self.discriminator(real), 1.0 - self.config['adv']['label_smoothing'])
@@ -1008,52 +1035,17 @@ class ADVTrainer(Solver):
         G_loss = bce_loss(self.discriminator(fake, frozen=True), 1.0)
         G_loss.backward()
         self.step(self.asr_model.encoder.parameters(), self.G_optim)
-        if self.tr.step % self.logging_step == 0:
-            ops.check_persistent_status()
         return D_realloss, D_fakeloss, G_loss
 
-    def _rank_batches(self):
-        from .gpu_loader import rank_batches
-        mine = set(rank_batches(len(self.train_set), self.rank, self.world))
-        for b_idx, (x, y) in enumerate(self.train_set):
-            if b_idx in mine:
-                yield b_idx, x, y
+    def _log(self, losses):
+        D_realloss, D_fakeloss, G_loss = losses
+        self.lg.scalar('discrim_real_loss_train', D_realloss.item(), self.tr.step)
+        self.lg.scalar('discrim_fake_loss_train', D_fakeloss.item(), self.tr.step)
+        self.lg.scalar('discrim_loss_train', (D_realloss + D_fakeloss).item(), self.tr.step)
+        self.lg.scalar('gen_loss_train', G_loss.item(), self.tr.step)
 
-    def exec(self):
-        self.verbose('Training set total {} batches'.format(len(self.train_set)))
-        nan_reported = self.train_step.skipped_steps if self.train_step is not None else 0
-        epoch = 0
-        while epoch < self.n_epochs:
-            self.verbose("Starting epoch {} out of {}".format(epoch + 1, self.n_epochs))
-            for b_idx, x, y in self._rank_batches():
-                self.verbose('Global step - {} ( {} / {} )'.format(self.tr.step, b_idx, len(self.train_set)),
-                             progress=True)
-                x, x_lens = prepare_x(x, device=self.device)
-                y, _ = prepare_y(y, device=self.device)
-                if self.train_step is not None:
-                    D_realloss, D_fakeloss, G_loss = self.train_step(x, x_lens, y)
-                    if self.train_step.skipped_steps > nan_reported:
-                        nan_reported = self.train_step.skipped_steps
-                        self.verbose('Error : grad norm is NaN @ step {}'.format(self.tr.step - 1))
-                else:
-                    D_realloss, D_fakeloss, G_loss = self._iteration(x, x_lens, y)
-                if self.rank == 0 and self.tr.step % self.logging_step == 0:
-                    self.lg.scalar('discrim_real_loss_train', D_realloss.item(), self.tr.step)
-                    self.lg.scalar('discrim_fake_loss_train', D_fakeloss.item(), self.tr.step)
-                    self.lg.scalar('discrim_loss_train', (D_realloss + D_fakeloss).item(), self.tr.step)
-                    self.lg.scalar('gen_loss_train', G_loss.item(), self.tr.step)
-                if self.tr.step % self.valid_step == 0:
-                    self.valid()
-                if self.rank == 0 and self.tr.step % self.save_step == 0:
-                    if self.train_step is not None:
-                        self.train_step.finish()       # never checkpoint after a time-out
-                    self.verbose("Model saved at step {}".format(self.tr.step))
-                    sdist.save_atomic(self.discriminator.state_dict(), self.ckppath)
-                    sdist.save_atomic(self.asr_model.state_dict(), self.asrpath_out)
-                self.tr.do_step()
-            epoch += 1
-        if self.train_step is not None:
-            self.train_step.finish()
+    def _checkpoint(self):
+        return ((self.discriminator, self.ckppath), (self.asr_model, self.asrpath_out))
 
     def valid(self):
         """src/trainer.py:1038-1113: the discriminator's two losses (real labels unsmoothed here, :1059) averaged
@@ -1087,24 +1079,11 @@ class ADVTrainer(Solver):
         self.lg.scalar('discrim_real_loss_eval', avg_real, self.tr.step)
         self.lg.scalar('discrim_fake_loss_eval', avg_fake, self.tr.step)
         self.lg.scalar('discrim_loss_eval', avg_loss, self.tr.step)
-        if avg_loss < self.tr.get_best():
-            self.tr.set_best(avg_loss)
-            self.verbose('Best validation loss : {:.4f} @ global step {}'.format(self.tr.get_best(), self.tr.step))
-            sdist.save_atomic(self.discriminator.state_dict(), self.best_ckppath)
+        if self._keep_best(avg_loss, self.discriminator):
             self.verbose("Both the discriminator and ASR have been saved")
 
-    def close(self):
-        self.verbose("Finished training! The most recent model will" +
-                     "be saved at step {} as well as the ASR model".format(self.tr.step))
-        if self.train_step is not None:
-            self.train_step.finish()
-        if self.rank == 0:
-            sdist.save_atomic(self.discriminator.state_dict(), self.ckppath)
-            sdist.save_atomic(self.asr_model.state_dict(), self.asrpath_out)
-        sdist.barrier()        # the next reader of these files (the Seed loop's next leg) runs on every rank
 
-
-class SAETrainer(Solver):
+class SAETrainer(Trainer):
     """Trains the speech autoencoder and, through it, the ASR model's Listener on audio alone
     (src/trainer.py:760-907; config 5's third leg).  With Adam (conf/default.yaml:24-26) one iteration of
     exec() is ONE engine.SAETrainStep call; any other optimizer type takes the reference's sequence (zero_grad,
@@ -1154,49 +1133,24 @@ class SAETrainer(Solver):
         pred = self.speech_autoenc(x, listener_out)
         return sae_loss(pred, x, max(x_lens)), pred
 
-    def _rank_batches(self):
-        from .gpu_loader import rank_batches
-        mine = set(rank_batches(len(self.train_set), self.rank, self.world))
-        for b_ind, (x, y) in enumerate(self.train_set):
-            if b_ind in mine:
-                yield b_ind, x
+    batches_line = 'Training set total {} batches.'
 
-    def exec(self):
-        self.verbose('Training set total {} batches.'.format(len(self.train_set)))
-        nan_reported = self.train_step.skipped_steps if self.train_step is not None else 0
-        epoch = 0
-        while epoch < self.n_epochs:
-            self.verbose("Starting epoch {} out of {}".format(epoch + 1, self.n_epochs))
-            for b_ind, x in self._rank_batches():
-                self.verbose('Batch: {}/{}, global step: {}'.format(b_ind, len(self.train_set), self.tr.step),
-                             progress=True)
-                x, x_lens = prepare_x(x, device=self.device)
-                if self.train_step is not None:
-                    loss = self.train_step(x, x_lens)
-                    if self.train_step.skipped_steps > nan_reported:
-                        nan_reported = self.train_step.skipped_steps
-                        self.verbose('Error : grad norm is NaN @ step {}'.format(self.tr.step - 1))
-                else:
-                    self.optim.zero_grad()
-                    loss, _ = self._forward_loss(x, x_lens)
-                    loss.backward()
-                    self.step(self.speech_autoenc.parameters(), self.optim)
-                    if self.tr.step % self.logging_step == 0:
-                        ops.check_persistent_status()
-                if self.rank == 0 and self.tr.step % self.logging_step == 0:
-                    self.lg.scalar('train_loss', loss.item(), self.tr.step)
-                if self.tr.step % self.valid_step == 0:
-                    self.valid()
-                if self.rank == 0 and self.tr.step % self.save_step == 0:
-                    if self.train_step is not None:
-                        self.train_step.finish()       # never checkpoint after a time-out
-                    self.verbose("Model saved at step {}".format(self.tr.step))
-                    sdist.save_atomic(self.speech_autoenc.state_dict(), self.ckppath)
-                    sdist.save_atomic(self.asr_model.state_dict(), self.asrpath_out)
-                self.tr.do_step()
-            epoch += 1
-        if self.train_step is not None:
-            self.train_step.finish()
+    def _prepare(self, raw):
+        """-> (x, x_lens)"""
+        return prepare_x(raw[0], device=self.device)
+
+    def _reference(self, batch):
+        self.optim.zero_grad()
+        loss, _ = self._forward_loss(*batch)
+        loss.backward()
+        self.step(self.speech_autoenc.parameters(), self.optim)
+        return loss
+
+    def _log(self, loss):
+        self.lg.scalar('train_loss', loss.item(), self.tr.step)
+
+    def _checkpoint(self):
+        return ((self.speech_autoenc, self.ckppath), (self.asr_model, self.asrpath_out))
 
     def valid(self):
         """src/trainer.py:840-897: the eval-mode loss (running batch-norm statistics) averaged over the
@@ -1227,22 +1181,7 @@ class SAETrainer(Solver):
             self.lg.figure('encode_compare_' + str(i), [label_img.numpy(), predict_img.numpy()], self.tr.step)
         avg_loss = total / n_batches
         self.lg.scalar('eval_loss', avg_loss, self.tr.step)
-        if avg_loss < self.tr.get_best():
-            self.tr.set_best(avg_loss)
-            self.verbose('Best validation loss : {:.4f} @ global step {}'.format(self.tr.get_best(), self.tr.step))
-            sdist.save_atomic(self.speech_autoenc.state_dict(), self.best_ckppath)
-        else:
-            self.verbose("Validation metric worse : ({:.4f} vs. {:.4f})".format(avg_loss, self.tr.get_best()))
-
-    def close(self):
-        self.verbose("Finished training! The most recent model will" +
-                     "be saved at step {} as well as the ASR model".format(self.tr.step))
-        if self.train_step is not None:
-            self.train_step.finish()
-        if self.rank == 0:
-            sdist.save_atomic(self.speech_autoenc.state_dict(), self.ckppath)
-            sdist.save_atomic(self.asr_model.state_dict(), self.asrpath_out)
-        sdist.barrier()        # the next reader of these files (the Seed loop's next leg) runs on every rank
+        self._keep_best(avg_loss, self.speech_autoenc)
 
 
 # src/train.py:19-20 offers the choice 'AdvTrainer' and resolves it with getattr(trainer, ...); the reference's

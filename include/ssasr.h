@@ -403,7 +403,9 @@ int ssasr_ce_loss_ls_bwd(const float* logits, const int32_t* y, int64_t y_ld, co
  * matrix); Lmax >= every label length, 2 * Lmax + 1 <= 1024; blank is a class no label uses.
  * ws: ssasr_ctc_ws_floats(B, T, V, Lmax) floats, 8-byte aligned (alpha lattice and per-row
  * nll, held in double), written by _fwd and read by _bwd.  loss = mean_b(nll_b / max(label_len_b, 1)), rows with no
- * alignment counting 0.  _bwd writes dlogits [B][T][V] (zero past frame_lens) and, when
+ * alignment counting 0.  frame_lens[b] > T is clamped to T; a row with label_lens[b] > Lmax or frame_lens[b] < 1
+ * is treated as having no alignment (loss contribution 0, zero gradient), like one whose frames cannot hold its
+ * labels.  _bwd writes dlogits [B][T][V] (zero past frame_lens) and, when
  * dbias is given, ADDS sum_{b,t} dlogits[b][t][:] to dbias [V]. */
 int64_t ssasr_ctc_ws_floats(int64_t B, int64_t T, int64_t V, int64_t Lmax);
 int ssasr_ctc_loss_fwd(const float* logits, const int32_t* frame_lens, const int32_t* y, int64_t y_ld,

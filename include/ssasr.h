@@ -28,7 +28,7 @@
  * ssasr_decode_beam_ctc_ws_bytes, ssasr_decode_beam_ctc; length bonus, coverage term and end detection in the beam
  * search -- ssasr_beam_terms, ssasr_decode_beam_ex_ws_bytes, ssasr_decode_beam_ex; SpecAugment in batch assembly and label smoothing in the
  * masked CE -- ssasr_specaug, ssasr_gather_batch_aug, ssasr_specaug_plan, ssasr_ce_loss_ls_fwd, ssasr_ce_loss_ls_bwd; CTC forced
- * alignment -- ssasr_ctc_align_ws_bytes, ssasr_ctc_align; edit-distance scoring -- ssasr_edit_score; MWER training --
+ * alignment -- ssasr_ctc_align_ws_bytes, ssasr_ctc_align; CTC-only decoding -- ssasr_ctc_decode_ws_bytes, ssasr_ctc_decode; edit-distance scoring -- ssasr_edit_score; MWER training --
  * ssasr_mwer_ws_bytes, ssasr_mwer_loss_fwd, ssasr_mwer_loss_bwd, ssasr_mwer_pack, ssasr_rows_repeat_fwd, ssasr_rows_repeat_bwd; sampled
  * decoding -- ssasr_sample, ssasr_decode_sample_ws_bytes, ssasr_decode_sample, ssasr_mwer_loss_fwd_ex; minimum-Bayes-risk
  * selection -- ssasr_mbr_select.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
@@ -454,6 +454,46 @@ int ssasr_ctc_align(const float* logits, const int32_t* frame_lens, const int32_
                     const int32_t* label_lens, int64_t B, int64_t T, int64_t V, int64_t Lmax, int blank,
                     void* ws, int64_t ws_bytes, int32_t* path, int32_t* first, int32_t* last,
                     float* char_logp, double* score, void* stream);
+
+/* ---- CTC-only decoding (added under ABI 16) ----------------------------------------------------------------------
+ * BUILD-DEFINED: the reference has no CTC.  A transcript from the head's posteriors alone, with no Speller step: the
+ * best path (K = 0) or a prefix beam search of width K (Graves 2012, 7.5.3; Hannun et al. 2014, alg. 1, without a
+ * language model) over the frames of the head that ssasr_ctc_loss_fwd trains.  logits [B][T][V] are the raw head
+ * outputs, frame_lens and blank as ssasr_ctc_align takes them.  Outputs, in the layout of ssasr_decode_beam's, with
+ * Kr = max(K, 1): chars int32 [B][Kr][T], n_chars int32 [B][Kr], scores float [B][Kr], n_hyps int32 [B].  Every
+ * element is written: slots from n_hyps on get length 0 and score -inf, characters from n_chars on are 0.
+ *   len = min(frame_lens[b], T); lp[t][v] = (double)logit[t][v] - lse_t, lse_t = (double)max + (double)logf(sum
+ *   expf(x - max)) as ssasr_ctc_align forms it.
+ *   K = 0, best path: c_t = argmax_v logit[t][v], the lowest index among equal values; the text is c_0 .. c_{len-1}
+ *   with repeats merged, then blanks removed; score = sum_t lp[t][c_t] accumulated in double; n_hyps = 1.  len < 1: the
+ *   empty text, score 0.  Text and length are defined exactly (comparisons only): tests compare them for equality.
+ *   K >= 1, prefix beam search, a search over TEXTS: a text occurs at most once in a beam however it was reached.
+ *   Each member u of the beam B_t carries g_b(u) and g_n(u), the log-probabilities of the labellings of frames 0..t
+ *   that collapse to u and end in a blank / a non-blank, restricted to labellings whose every earlier prefix was in
+ *   its frame's beam.  B_{-1} = {empty: g_b = 0, g_n = -inf}.  Frame t: the candidates are every u in B_{t-1} and
+ *   every u.c for non-blank c; with either(u) = logaddexp(g_b(u), g_n(u)), a candidate w with parent p (w minus its
+ *   last character c) gets
+ *     g_b'(w) = lp[t][blank] + either(w)                      if w in B_{t-1}, else -inf
+ *     g_n'(w) = lp[t][c] + logaddexp(g_n(w) if w in B_{t-1},  (last(p) == c ? g_b(p) : either(p)) if p in B_{t-1})
+ *   an absent term being -inf; the empty text has g_n' = -inf.  B_t is the min(K, number of finite candidates)
+ *   candidates with the largest logaddexp(g_b', g_n') (among equal values: a kept text before an extension, then the
+ *   lower slot, then the lower character).  After frame len - 1 the members are written best first, score = that
+ *   value, n_hyps = their count (len < 1: the empty text alone, score 0).  g is held in double; exp and log run in
+ *   float on differences from the larger operand.
+ *   Identity of texts is established on the stored texts: each frame, a member's parent is looked up among the
+ *   members by length and a 64-bit rolling hash as a filter, and then by comparing the characters.  An extension
+ *   u.c that is itself a member is not a second candidate: its probability enters that member's g_n'.
+ * Accepted: 1 <= B <= 65535, 1 <= T <= 4096 (the frame loop is serial and each member's text is copied once per frame:
+ * the limit keeps a launch to tens of milliseconds), 0 <= K <= 32, 2 <= V <= 64 for K >= 1 (the lp[T][64] width of
+ * ssasr_decode_beam_ctc) and V <= 1024 for K = 0, 0 <= blank < V, ws 8-byte aligned with ws_bytes >=
+ * ssasr_ctc_decode_ws_bytes(...) (0: no kernel for the shape).  Argument errors return before any HIP call.
+ * One launch of 256 threads per utterance, no exchange between workgroups, no spins; every loop is bounded by len, K,
+ * V or T.  LDS holds the beam's scalars and ONE frame's candidates (K + K V totals, 17 KB at the limits); the texts
+ * of the two beams B_{t-1} and B_t, [B][2][K][T] int32, live in the workspace (K = 0: the frame labels, [B][T]). */
+int64_t ssasr_ctc_decode_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K);
+int ssasr_ctc_decode(const float* logits, const int32_t* frame_lens, int64_t B, int64_t T, int64_t V, int64_t K,
+                     int blank, void* ws, int64_t ws_bytes, int32_t* chars, int32_t* n_chars, float* scores,
+                     int32_t* n_hyps, void* stream);
 
 /* ---- Edit-distance scoring (added under ABI 16) -----------------------------------------------------------------
  * BUILD-DEFINED: the reference scores on the host (its calc_err).  Character and word error counts of P

@@ -304,6 +304,9 @@ class ASR(nn.Module):
         # sample's device results: (chars [N, K, steps] int32 in slot order, n_chars [N, K] int32, hyp_scores [N, K],
         # n_hyps [N] int32, logq [N, K])
         self.last_samples = None
+        # decode_ctc's device results: (chars [N, Kr, T'] int32, n_chars [N, Kr] int32, scores [N, Kr], n_hyps [N] int32,
+        # logits [N, T', V])
+        self.last_ctc_decode = None
         self.init_parameters()
 
     def init_parameters(self):
@@ -693,6 +696,29 @@ class ASR(nn.Module):
                 hyps = (self.last_beam[0], self.last_beam[1], self.last_beam[3], self.last_beam[2])
             self._keep_hyps(*hyps, sampled=False)
         return self._texts(*hyps, mapper)
+
+    def decode_ctc(self, xs, x_lens, mapper, *, beam_size=8):
+        """BUILD-DEFINED: transcripts from the ctc_head's posteriors alone, for a list of single utterances in ONE
+        launch with no Speller step (ssasr_ctc_decode, include/ssasr.h): per utterance the list of (text, score), best
+        first.  beam_size 0: the best path (per frame the most probable class, repeats merged, blanks removed; score =
+        the path's log-probability); 1 .. 32: CTC prefix beam search of that width, score = the log-probability that
+        the search found for the text.  Each utterance is encoded alone, as in decode_nbest.  last_ctc_decode keeps
+        (chars [N, Kr, T'], n_chars [N, Kr], scores [N, Kr], n_hyps [N], logits [N, T', V]) on the device, Kr =
+        max(beam_size, 1); last_hyps is set, so score(), mbr() and align() follow it as they follow decode_nbest."""
+        head = getattr(self, 'ctc_head', None)
+        if head is None:
+            raise ValueError(self._NO_CTC_HEAD % type(self).__name__)
+        if isinstance(beam_size, bool) or not isinstance(beam_size, int) or not 0 <= beam_size <= ops.CTC_DECODE_MAX_BEAM:
+            raise ValueError('beam_size must be an integer in 0..%d, got %r' % (ops.CTC_DECODE_MAX_BEAM, beam_size))
+        if len(xs) != len(x_lens) or not len(xs):
+            raise ValueError('decode_ctc: %d utterances, %d lengths' % (len(xs), len(x_lens)))
+        with torch.no_grad():
+            packed, enc_lens = self._encode_packed(xs, x_lens)
+            self.last_ctc_decode = ops.ctc_head_decode(packed, head.weight, head.bias, enc_lens, beam_size,
+                                                       ops.CTC_BLANK)
+            chars, n_chars, scores, n_hyps, _ = self.last_ctc_decode
+            self._keep_hyps(chars, n_chars, n_hyps, scores, sampled=False)
+        return self._texts(chars, n_chars, n_hyps, scores, mapper)
 
     def sample(self, xs, x_lens, mapper, n_samples, *, temperature=1.0, rnn_lm=None, lm_weight=0.0,
                max_decoding_steps=200, generator=None, uniforms=None):

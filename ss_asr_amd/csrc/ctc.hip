@@ -457,7 +457,287 @@ int align_check_shape(int64_t B, int64_t T, int64_t V, int64_t Lmax) {
   return SSASR_OK;
 }
 
+// ---- CTC-only decoding: best path and prefix beam search (include/ssasr.h) -----------------------------------------
+// BUILD-DEFINED like the rest of this file.  One workgroup of 256 threads per utterance, a serial loop over its
+// frames.  The prefix search keeps, per beam member, g_b / g_n in double, the text's length, last character and a
+// rolling hash of the text and of its parent in LDS, and the texts themselves in the workspace, one block per beam
+// (B_{t-1} is read, B_t written).  A frame is: the row's log-softmax (wave 0, the next row's logits loaded one frame
+// ahead); each member's parent looked up among the members (length and hash as a filter, then the characters,
+// one wave per member); the K + K V candidate totals into LDS, an extension that is itself a member being no
+// candidate; K rounds of a block-wide argmax; the winners' scalars and texts written to the other beam.
+constexpr int DEC_NT = 256;
+constexpr int DEC_WAVES = DEC_NT / 64;
+constexpr int DEC_MAX_K = 32;
+constexpr int DEC_MAX_V = 64;
+constexpr int DEC_MAX_V_BEST = 1024;
+constexpr int DEC_MAX_T = 4096;
+constexpr unsigned long long DEC_HASH_MUL = 0x9E3779B97F4A7C15ull;
+
+struct DecodeArgs {
+  const float* logits;       // [B][T][V]
+  const int32_t* frame_lens; // [B]
+  int T, V, K, blank;
+  int32_t* text;             // K >= 1: [B][2][K][T] the two beams' texts; K = 0: [B][T] the frames' labels
+  int32_t* chars;            // [B][max(K,1)][T]
+  int32_t* n_chars;          // [B][max(K,1)]
+  float* scores;             // [B][max(K,1)]
+  int32_t* n_hyps;           // [B]
+};
+
+// log(exp(a) + exp(b)): double operands, exp and log in float on the difference from the larger one
+__device__ __forceinline__ double dec_lae(double a, double b) {
+  const double m = fmax(a, b), n = fmin(a, b);
+  if (n == NEG_INF) return m;
+  return m + (double)logf(1.f + expf((float)(n - m)));
+}
+
+__global__ __launch_bounds__(DEC_NT) void ctc_best_path_kernel(DecodeArgs a) {
+  __shared__ double red[DEC_WAVES];
+  __shared__ int cnt[DEC_NT];
+  __shared__ int n_sh;
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int len = max(min(a.frame_lens[b], a.T), 0), V = a.V;
+  const float* logits = a.logits + (int64_t)b * a.T * V;
+  int32_t* lab = a.text + (int64_t)b * a.T;
+  int32_t* out = a.chars + (int64_t)b * a.T;
+  double part = 0.0;
+  for (int t = wave; t < len; t += DEC_WAVES) {
+    const float* row = logits + (int64_t)t * V;
+    float m = lane < V ? row[lane] : -INFINITY;
+    int am = lane < V ? lane : INT32_MAX;
+    for (int v = lane + 64; v < V; v += 64) {
+      const float x = row[v];
+      if (x > m) { m = x; am = v; }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {                // the largest value, the lowest index among equals
+      const float om = __shfl_xor(m, off);
+      const int oa = __shfl_xor(am, off);
+      if (om > m || (om == m && oa < am)) { m = om; am = oa; }
+    }
+    float s = 0.f;
+    for (int v = lane; v < V; v += 64) s += expf(row[v] - m);
+    s = wave_sum(s);
+    part += (double)row[am] - ((double)m + (double)logf(s));
+    if (lane == 0) lab[t] = am;
+  }
+  if (lane == 0) red[wave] = part;
+  __syncthreads();
+  // merge repeats, drop blanks: a thread counts the kept labels of its run of frames, then writes them behind
+  // those of the threads before it
+  const int chunk = (len + DEC_NT - 1) / DEC_NT;
+  const int t0 = min(tid * chunk, len), t1 = min(t0 + chunk, len);
+  int keep = 0;
+  for (int t = t0; t < t1; ++t) keep += lab[t] != a.blank && (t == 0 || lab[t] != lab[t - 1]);
+  cnt[tid] = keep;
+  __syncthreads();
+  int at = 0;
+  for (int i = 0; i < tid; ++i) at += cnt[i];
+  if (tid == DEC_NT - 1) n_sh = at + keep;
+  for (int t = t0; t < t1; ++t)
+    if (lab[t] != a.blank && (t == 0 || lab[t] != lab[t - 1])) out[at++] = lab[t];
+  __syncthreads();
+  const int n = n_sh;
+  for (int i = n + tid; i < a.T; i += DEC_NT) out[i] = 0;
+  if (tid == 0) {
+    double total = 0.0;
+    for (int w = 0; w < DEC_WAVES; ++w) total += red[w];
+    a.n_chars[b] = n;
+    a.scores[b] = (float)total;
+    a.n_hyps[b] = 1;
+  }
+}
+
+__global__ __launch_bounds__(DEC_NT) void ctc_prefix_beam_kernel(DecodeArgs a) {
+  __shared__ double gb[2][DEC_MAX_K], gn[2][DEC_MAX_K];      // the two beams' members
+  __shared__ unsigned long long hs[2][DEC_MAX_K], hp[2][DEC_MAX_K];   // hash of the text, of the text's parent
+  __shared__ int tlen[2][DEC_MAX_K], tlast[2][DEC_MAX_K];    // length, last character (-1: the empty text)
+  __shared__ int par[DEC_MAX_K];                             // the member that is this member's parent, -1: none
+  __shared__ signed char child[DEC_MAX_K * DEC_MAX_V];       // [u][c]: the member that is u.c, -1: none
+  __shared__ double lpd[DEC_MAX_V];                          // the frame's log-softmax
+  __shared__ double sgb[DEC_MAX_K], sgn[DEC_MAX_K];          // g_b', g_n' of the kept texts
+  __shared__ double tot[DEC_MAX_K + DEC_MAX_K * DEC_MAX_V];  // the candidates' totals: [K] kept, then [K][V] extensions
+  __shared__ double wv[2][DEC_WAVES], winv[DEC_MAX_K];
+  __shared__ int wi[2][DEC_WAVES], win[DEC_MAX_K];
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int len = max(min(a.frame_lens[b], a.T), 0), V = a.V, K = a.K, T = a.T, blank = a.blank;
+  const float* logits = a.logits + (int64_t)b * T * V;
+  int32_t* text = a.text + (int64_t)b * 2 * K * T;
+  const int ncand = K + K * V;
+  int n = 1, cur = 0;
+  if (tid == 0) {
+    gb[0][0] = 0.0; gn[0][0] = NEG_INF;
+    hs[0][0] = 0; hp[0][0] = 0;
+    tlen[0][0] = 0; tlast[0][0] = -1;
+  }
+  float x_next = (wave == 0 && lane < V && len > 0) ? logits[lane] : -INFINITY;
+  __syncthreads();
+  for (int t = 0; t < len; ++t) {
+    const int32_t* told = text + (int64_t)cur * K * T;
+    int32_t* tnew = text + (int64_t)(cur ^ 1) * K * T;
+    for (int i = tid; i < K * V; i += DEC_NT) child[i] = -1;
+    if (wave == 0) {                                         // the row's log-softmax (ctc_table's normaliser)
+      const float x = x_next;
+      if (t + 1 < len && lane < V) x_next = logits[(int64_t)(t + 1) * V + lane];
+      const float m = wave_max(x);
+      const float s = wave_sum(lane < V ? expf(x - m) : 0.f);
+      const double lse = (double)m + (double)logf(s);
+      if (lane < V) lpd[lane] = (double)x - lse;
+    }
+    __syncthreads();
+    // each member's parent among the members: a lane per possible parent filters, the wave compares the characters
+    for (int w = wave; w < n; w += DEC_WAVES) {
+      const int lw = tlen[cur][w];
+      int found = -1;
+      if (lw >= 1) {
+        unsigned long long mask = __ballot(lane < n && tlen[cur][lane < n ? lane : 0] == lw - 1 &&
+                                           hs[cur][lane < n ? lane : 0] == hp[cur][w]);
+        while (mask != 0 && found < 0) {                     // at most n turns
+          const int u = __ffsll((long long)mask) - 1;
+          mask &= mask - 1;
+          int differ = 0;
+          for (int i = lane; i < lw - 1; i += 64) differ |= told[(int64_t)w * T + i] != told[(int64_t)u * T + i];
+          if (!__any(differ)) found = u;
+        }
+        if (lane == 0 && found >= 0) child[found * V + tlast[cur][w]] = (signed char)w;
+      }
+      if (lane == 0) par[w] = found;
+    }
+    __syncthreads();
+    // the candidates' totals; each thread remembers the best of its own
+    const double lpb = lpd[blank];
+    double best = NEG_INF;
+    int bidx = INT32_MAX;
+    for (int idx = tid; idx < ncand; idx += DEC_NT) {
+      double v = NEG_INF;
+      if (idx < K) {
+        const int w = idx;
+        if (w < n) {
+          const double nb = lpb + dec_lae(gb[cur][w], gn[cur][w]);
+          double nn = NEG_INF;
+          const int c = tlast[cur][w];
+          if (c >= 0) {
+            const int p = par[w];
+            double via = NEG_INF;
+            if (p >= 0) via = tlast[cur][p] == c ? gb[cur][p] : dec_lae(gb[cur][p], gn[cur][p]);
+            nn = lpd[c] + dec_lae(gn[cur][w], via);
+          }
+          sgb[w] = nb;
+          sgn[w] = nn;
+          v = dec_lae(nb, nn);
+        }
+      } else {
+        const int u = (idx - K) / V, c = (idx - K) % V;
+        if (u < n && c != blank && child[u * V + c] < 0)
+          v = lpd[c] + (tlast[cur][u] == c ? gb[cur][u] : dec_lae(gb[cur][u], gn[cur][u]));
+      }
+      tot[idx] = v;
+      if (v > best) { best = v; bidx = idx; }
+    }
+    // B_t: K rounds of a block-wide argmax (the lowest index among equals), the winner leaving the pool
+    int n_new = 0;
+    for (int r = 0; r < K; ++r) {
+      double m = best;
+      int mi = bidx;
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+        const double om = __shfl_xor(m, off);
+        const int oi = __shfl_xor(mi, off);
+        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+      }
+      if (lane == 0) { wv[r & 1][wave] = m; wi[r & 1][wave] = mi; }
+      __syncthreads();
+      double gm = wv[r & 1][0];
+      int gi = wi[r & 1][0];
+#pragma unroll
+      for (int w = 1; w < DEC_WAVES; ++w) {
+        const double om = wv[r & 1][w];
+        const int oi = wi[r & 1][w];
+        if (om > gm || (om == gm && oi < gi)) { gm = om; gi = oi; }
+      }
+      if (!(gm > NEG_INF)) break;                            // fewer finite candidates than K
+      if (tid == 0) { win[r] = gi; winv[r] = gm; }
+      n_new = r + 1;
+      if (gi % DEC_NT == tid) {
+        tot[gi] = NEG_INF;
+        best = NEG_INF;
+        bidx = INT32_MAX;
+        for (int idx = tid; idx < ncand; idx += DEC_NT) {
+          const double v = tot[idx];
+          if (v > best) { best = v; bidx = idx; }
+        }
+      }
+    }
+    __syncthreads();
+    // the winners become B_t: scalars, then texts
+    const int nxt = cur ^ 1;
+    if (tid < n_new) {
+      const int gi = win[tid];
+      if (gi < K) {
+        gb[nxt][tid] = sgb[gi]; gn[nxt][tid] = sgn[gi];
+        hs[nxt][tid] = hs[cur][gi]; hp[nxt][tid] = hp[cur][gi];
+        tlen[nxt][tid] = tlen[cur][gi]; tlast[nxt][tid] = tlast[cur][gi];
+      } else {
+        const int u = (gi - K) / V, c = (gi - K) % V;
+        gb[nxt][tid] = NEG_INF; gn[nxt][tid] = winv[tid];
+        hs[nxt][tid] = hs[cur][u] * DEC_HASH_MUL + (unsigned long long)(c + 1); hp[nxt][tid] = hs[cur][u];
+        tlen[nxt][tid] = tlen[cur][u] + 1; tlast[nxt][tid] = c;
+      }
+    }
+    for (int j = 0; j < n_new; ++j) {
+      const int gi = win[j];
+      const int src = gi < K ? gi : (gi - K) / V;
+      const int l = tlen[cur][src];                          // l <= t < T: the appended character stays in the row
+      for (int i = tid; i < l; i += DEC_NT) tnew[(int64_t)j * T + i] = told[(int64_t)src * T + i];
+      if (gi >= K && tid == 0) tnew[(int64_t)j * T + l] = (gi - K) % V;
+    }
+    __syncthreads();
+    cur = nxt;
+    n = n_new;
+  }
+  // the members are in the order they won: best first
+  const int32_t* tfin = text + (int64_t)cur * K * T;
+  for (int j = 0; j < K; ++j) {
+    const int l = j < n ? tlen[cur][j] : 0;
+    int32_t* out = a.chars + ((int64_t)b * K + j) * T;
+    for (int i = tid; i < T; i += DEC_NT) out[i] = i < l ? tfin[(int64_t)j * T + i] : 0;
+  }
+  if (tid < K) {
+    a.n_chars[(int64_t)b * K + tid] = tid < n ? tlen[cur][tid] : 0;
+    a.scores[(int64_t)b * K + tid] = tid < n ? (float)dec_lae(gb[cur][tid], gn[cur][tid]) : -INFINITY;
+  }
+  if (tid == 0) a.n_hyps[b] = n;
+}
+
+int decode_check_shape(int64_t B, int64_t T, int64_t V, int64_t K) {
+  if (B < 1 || B > 65535 || T < 1 || T > DEC_MAX_T || V < 2 || K < 0 || K > DEC_MAX_K) return SSASR_EARG;
+  if (V > (K == 0 ? DEC_MAX_V_BEST : DEC_MAX_V)) return SSASR_EARG;
+  return SSASR_OK;
+}
+
 }  // namespace
+
+extern "C" int64_t ssasr_ctc_decode_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K) {
+  if (decode_check_shape(B, T, V, K) != SSASR_OK) return 0;
+  return (K == 0 ? B * T : B * 2 * K * T) * 4;
+}
+
+extern "C" int ssasr_ctc_decode(const float* logits, const int32_t* frame_lens, int64_t B, int64_t T, int64_t V,
+                                int64_t K, int blank, void* ws, int64_t ws_bytes, int32_t* chars, int32_t* n_chars,
+                                float* scores, int32_t* n_hyps, void* stream) {
+  if (!logits || !frame_lens || !ws || !chars || !n_chars || !scores || !n_hyps) return SSASR_EARG;
+  if (decode_check_shape(B, T, V, K) != SSASR_OK || blank < 0 || blank >= V) return SSASR_EARG;
+  if ((reinterpret_cast<uintptr_t>(ws) & 7) || ws_bytes < ssasr_ctc_decode_ws_bytes(B, T, V, K)) return SSASR_EARG;
+  DecodeArgs a{};
+  a.logits = logits; a.frame_lens = frame_lens;
+  a.T = (int)T; a.V = (int)V; a.K = (int)K; a.blank = blank;
+  a.text = reinterpret_cast<int32_t*>(ws);
+  a.chars = chars; a.n_chars = n_chars; a.scores = scores; a.n_hyps = n_hyps;
+  void (*fn)(DecodeArgs) = K == 0 ? ctc_best_path_kernel : ctc_prefix_beam_kernel;
+  hipLaunchKernelGGL(fn, dim3((unsigned)B), dim3(DEC_NT), 0, (hipStream_t)stream, a);
+  SSASR_LAUNCH_CHECK();
+  return SSASR_OK;
+}
 
 extern "C" int64_t ssasr_ctc_align_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t Lmax) {
   if (align_check_shape(B, T, V, Lmax) != SSASR_OK) return 0;

@@ -1033,6 +1033,53 @@ def ctc_head_align(feat, weight, bias, frame_lens, y32, label_lens, lmax, blank=
     return ctc_align(logits, frame_lens, y32, label_lens, lmax, blank) + (logits,)
 
 
+CTC_DECODE_MAX_BEAM = 32       # ssasr_ctc_decode's limits (include/ssasr.h)
+CTC_DECODE_MAX_FRAMES = 4096
+
+
+def ctc_decode(logits, frame_lens, beam_size, blank=0):
+    """ssasr_ctc_decode: a transcript per row from the CTC posteriors alone, in one launch (include/ssasr.h).  logits
+    [B, T, V] raw head outputs, frame_lens int32 [B] on the device.  beam_size 0: the best path (V <= 1024); 1 .. 32:
+    prefix beam search of that width (V <= 64).  -> (chars [B, Kr, T] int32, n_chars [B, Kr] int32, scores [B, Kr]
+    float32, n_hyps [B] int32) on the device, Kr = max(beam_size, 1), best first; slots from n_hyps on have length 0
+    and score -inf.  No autograd."""
+    lib = _lib.load()
+    beam_size, blank = int(beam_size), int(blank)
+    _need_gpu(logits, frame_lens)
+    logits = _f32c(logits.detach())
+    if logits.dim() != 3:
+        raise ValueError('ctc_decode: logits must be [B, T, V], got %r' % (tuple(logits.shape),))
+    if frame_lens.dtype != torch.int32 or frame_lens.numel() != logits.shape[0]:
+        raise TypeError('ctc_decode: frame_lens must be int32 [B]')
+    B, T, V = logits.shape
+    if not 0 <= beam_size <= CTC_DECODE_MAX_BEAM:
+        raise ValueError('ctc_decode: beam_size must be in 0..%d, got %d' % (CTC_DECODE_MAX_BEAM, beam_size))
+    if not 0 <= blank < V:
+        raise ValueError('ctc_decode: blank %d is no class of V=%d' % (blank, V))
+    need = int(lib.ssasr_ctc_decode_ws_bytes(B, T, V, beam_size))
+    if need <= 0:
+        raise ValueError('ctc_decode: shape B=%d T=%d V=%d beam_size=%d has no kernel' % (B, T, V, beam_size))
+    dev, kr = logits.device, max(beam_size, 1)
+    ws = torch.empty((need + 7) // 8, device=dev, dtype=torch.int64)
+    chars = torch.empty(B, kr, T, device=dev, dtype=torch.int32)
+    n_chars = torch.empty(B, kr, device=dev, dtype=torch.int32)
+    scores = torch.empty(B, kr, device=dev, dtype=torch.float32)
+    n_hyps = torch.empty(B, device=dev, dtype=torch.int32)
+    check(lib.ssasr_ctc_decode(_p(logits), _p(frame_lens.contiguous()), B, T, V, beam_size, blank, _p(ws), ws.numel() * 8,
+                               _p(chars), _p(n_chars), _p(scores), _p(n_hyps), _stream()), 'ssasr_ctc_decode')
+    return chars, n_chars, scores, n_hyps
+
+
+def ctc_head_decode(feat, weight, bias, frame_lens, beam_size, blank=0):
+    """ctc_decode on the head's logits, the product issued exactly as the training node issues it (_CTCHead.forward).
+    -> ctc_decode's four tensors and the logits [B, T, V] they were decoded from.  No autograd."""
+    _need_gpu(feat, weight, bias)
+    feat, w, b = _f32c(feat.detach()), _f32c(weight.detach()), _f32c(bias.detach())
+    B, T, E = feat.shape
+    logits = gemm(feat.view(B * T, E), w, bias=b).view(B, T, w.shape[0])
+    return ctc_decode(logits, frame_lens, beam_size, blank) + (logits,)
+
+
 EDIT_SCORE_MAX_HYP = 8191      # ssasr_edit_score's limits on a row's tokens, counted before dropping
 EDIT_SCORE_MAX_REF = 1023
 

@@ -189,6 +189,72 @@ def mbr_reference(hyps, n_hyps, scores, space, first_char=2, unit='word', poster
     return best, risks, pairs
 
 
+def ctc_prefix_beam_reference(lp, K, blank=0, dtype=np.float64, trace=None):
+    """BUILD-DEFINED: CTC-only decoding, ssasr_ctc_decode (include/ssasr.h) restated over Python tuples as texts --
+    what the kernel is defined and tested against.  lp [T, V]: one utterance's log-probabilities, already cut to its
+    frames; every sum runs in `dtype` (float64; float32 measures the arithmetic's noise).
+    K = 0, the best path: per frame the class of the largest entry (the lowest index among equals), repeats merged,
+    blanks removed; score = the sum of the chosen entries.
+    K >= 1, prefix beam search over TEXTS, a dict from text to (g_b, g_n): the log-probabilities of the labellings of
+    the frames so far that collapse to the text and end in a blank / a non-blank, restricted to labellings whose
+    every earlier prefix was in its frame's beam.  Frame t's candidates are the members u and every u + (c,) for a
+    non-blank c; with either(u) = logaddexp(g_b(u), g_n(u)) a candidate w = p + (c,) gets
+      g_b'(w) = lp[t, blank] + either(w) if w is a member, else -inf
+      g_n'(w) = lp[t, c] + logaddexp(g_n(w) if w is a member, (g_b(p) if p ends in c else either(p)) if p is a member)
+    (an absent term is -inf; the empty text has g_n' = -inf), and the K finite candidates with the largest
+    logaddexp(g_b', g_n') are the next members.
+    -> ([(text, score)] best first, the smallest gap that any frame left between the lowest kept and the highest
+    dropped total -- inf when nothing finite was ever dropped: below it a rounding can change the search).  trace: a
+    list that receives each frame's beam as a frozenset of texts (K >= 1)."""
+    lp = np.asarray(lp, dtype=dtype)
+    K, blank = int(K), int(blank)
+    if lp.ndim != 2:
+        raise ValueError('ctc_prefix_beam_reference: lp must be [T, V], got %r' % (lp.shape,))
+    if K < 0:
+        raise ValueError('ctc_prefix_beam_reference: K must be >= 0, got %d' % K)
+    if np.dtype(dtype) == np.float64:                           # Python floats ARE float64, and ten times faster
+        rows, zero, neg = lp.tolist(), 0.0, -math.inf
+
+        def lae(a, b):
+            if a < b:
+                a, b = b, a
+            return a if b == -math.inf else a + math.log1p(math.exp(b - a))
+    else:
+        rows, zero, neg, lae = [list(row) for row in lp], dtype(0), dtype(-np.inf), np.logaddexp
+    if K == 0:
+        path = [int(np.argmax(row)) for row in lp]
+        text = tuple(c for t, c in enumerate(path) if c != blank and (t == 0 or c != path[t - 1]))
+        score = zero
+        for t, c in enumerate(path):
+            score = score + rows[t][c]
+        return [(text, float(score))], math.inf
+    beam = {(): (zero, neg)}
+    gap = math.inf
+    classes = [c for c in range(lp.shape[1]) if c != blank]
+    for row in rows:
+        either = {u: lae(g[0], g[1]) for u, g in beam.items()}
+        new, total = {}, {}
+        for w in set(beam) | {u + (c,) for u in beam for c in classes}:
+            g_b = row[blank] + either[w] if w in beam else neg
+            g_n = neg
+            if w:
+                p, c = w[:-1], w[-1]
+                stay = beam[w][1] if w in beam else neg
+                grow = neg
+                if p in beam:
+                    grow = beam[p][0] if p and p[-1] == c else either[p]
+                g_n = row[c] + lae(stay, grow)
+            new[w] = (g_b, g_n)
+            total[w] = lae(g_b, g_n)
+        ranked = sorted((w for w in new if total[w] > neg), key=lambda w: (-total[w], w))
+        if len(ranked) > K:
+            gap = min(gap, float(total[ranked[K - 1]] - total[ranked[K]]))
+        beam = {w: new[w] for w in ranked[:K]}
+        if trace is not None:
+            trace.append(frozenset(beam))
+    return sorted(((w, float(lae(g[0], g[1]))) for w, g in beam.items()), key=lambda e: (-e[1], e[0])), gap
+
+
 class ErrorStats:
     """Corpus-level error rates: sums (S, D, I, N) rows of characters and of words; cer / wer =
     sum(S + D + I) / sum(N), nan when N == 0.  (calc_err below stays the reference's mean of per-utterance ratios.)"""

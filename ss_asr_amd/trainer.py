@@ -671,7 +671,13 @@ class ASRTester(Solver):
     `_mbr<unit>` and `last_mbr_choices` holds the chosen slot per utterance in index order.  With asr.decode_score on,
     `last_scores` keeps scoring slot 0 and `last_error_rates` gains 'mbr_cer' / 'mbr_wer', the corpus-level rates of
     the chosen slots (read from the scorer's per-hypothesis rows, no second launch); an align then aligns the chosen
-    transcripts."""
+    transcripts.
+    asr.decode_ctc_only: {beam_size: 8} (absent: off; beam_size an integer in 0..32, 0 the best path; needs
+    'ctc_weight' in asr.mdl, else set_model raises): every group is transcribed from the ctc_head's posteriors alone,
+    with no Speller step (ASR.decode_ctc, ssasr_ctc_decode); asr.decode_beam_size, the language model and
+    max_decode_step_ratio then play no part, and `decode_file` gains `_ctconly<beam_size>`.  It composes with
+    decode_score, decode_mbr (which then needs THIS beam_size >= 2) and decode_align; together with a positive
+    asr.decode_ctc_weight or any of the beam search's terms it is an error."""
     decode_group = 32
     TERM_KEYS = ('decode_length_bonus', 'decode_coverage_weight', 'decode_coverage_threshold', 'decode_end_margin')
 
@@ -720,11 +726,27 @@ class ASRTester(Solver):
             raise ValueError("asr.decode_mbr.unit must be 'word' or 'char', got {!r}".format(unit))
         if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale) or scale < 0:
             raise ValueError('asr.decode_mbr.scale must be a finite number >= 0, got {!r}'.format(scale))
-        beam = asr_config.get('decode_beam_size')
+        ctc_only = ASRTester.ctc_only_beam(asr_config)
+        beam = asr_config.get('decode_beam_size') if ctc_only is None else ctc_only
         if isinstance(beam, bool) or not isinstance(beam, int) or beam < 2:
-            raise ValueError('asr.decode_mbr chooses among an n-best list: asr.decode_beam_size must be >= 2, '
-                             'got {!r}'.format(beam))
+            raise ValueError('asr.decode_mbr chooses among an n-best list: asr.decode_{} must be >= 2, '
+                             'got {!r}'.format('beam_size' if ctc_only is None else 'ctc_only.beam_size', beam))
         return {'unit': unit, 'scale': float(scale)}
+
+    @staticmethod
+    def ctc_only_beam(asr_config):
+        """ASR.decode_ctc's beam_size from asr.decode_ctc_only, validated; None when the key is absent (or false)."""
+        conf = asr_config.get('decode_ctc_only')
+        if conf is None or conf is False:
+            return None
+        if conf is True:
+            conf = {}
+        if not isinstance(conf, dict) or set(conf) - {'beam_size'}:
+            raise ValueError('asr.decode_ctc_only must be a mapping with the key beam_size, got {!r}'.format(conf))
+        beam = conf.get('beam_size', 8)
+        if isinstance(beam, bool) or not isinstance(beam, int) or not 0 <= beam <= 32:
+            raise ValueError('asr.decode_ctc_only.beam_size must be an integer in 0..32, got {!r}'.format(beam))
+        return beam
 
     def __init__(self, config, paras):
         super().__init__(config, paras, 'asr')
@@ -743,6 +765,16 @@ class ASRTester(Solver):
         if self.decode_align and 'ctc_weight' not in self.config['asr']['mdl']:
             raise ValueError('asr.decode_align needs a model with a ctc_head: set asr.mdl.ctc_weight '
                              '(ctc.JointCTCASR)')
+        self.decode_ctc_only = self.ctc_only_beam(self.config['asr'])
+        if self.decode_ctc_only is not None:
+            if 'ctc_weight' not in self.config['asr']['mdl']:
+                raise ValueError('asr.decode_ctc_only needs a model with a ctc_head: set asr.mdl.ctc_weight '
+                                 '(ctc.JointCTCASR)')
+            clash = ['decode_ctc_weight'] if self.config['asr'].get('decode_ctc_weight', 0) != 0 else []
+            clash += ['decode_' + k for k in self.decode_terms(self.config['asr'])[0] if k != 'coverage_threshold']
+            if clash:
+                raise ValueError('asr.decode_ctc_only runs no attention beam search: it cannot be combined with '
+                                 'asr.{}'.format(', asr.'.join(clash)))
         asr_cls = ASR
         if 'ctc_weight' in self.config['asr']['mdl']:
             from .ctc import JointCTCASR
@@ -768,6 +800,8 @@ class ASRTester(Solver):
         self.decode_ctc_weight = self.config['asr'].get('decode_ctc_weight', 0)
         if self.decode_ctc_weight > 0:
             self.decode_file += '_ctc{:}'.format(self.decode_ctc_weight)
+        if self.decode_ctc_only is not None:
+            self.decode_file += '_ctconly{:}'.format(self.decode_ctc_only)
         self.decode_term_args, suffix = self.decode_terms(self.config['asr'])
         self.decode_file += suffix
         if self.decode_align:
@@ -787,7 +821,10 @@ class ASRTester(Solver):
         if isinstance(ctc_weight, bool) or not isinstance(ctc_weight, (int, float)) or not 0 <= ctc_weight <= 1:
             raise ValueError('asr.decode_ctc_weight must be a number in [0, 1], got {!r}'.format(ctc_weight))
         terms = self.decode_term_args
+        ctc_only = self.decode_ctc_only
         self.verbose('Start decoding ({}{}{})'.format(
+            ('CTC only, ' + ('prefix beam search, beam size {}'.format(ctc_only) if ctc_only else 'best path'))
+            if ctc_only is not None else
             'beam search, beam size {}'.format(beam) if beam > 1 else 'greedy, beam size 1',
             ', joint CTC / attention scores, CTC weight {}'.format(ctc_weight) if ctc_weight > 0 else '',
             ''.join(', {} {}'.format(k.replace('_', ' '), v) for k, v in terms.items())))
@@ -803,8 +840,12 @@ class ASRTester(Solver):
 
         def flush():
             if xs:
-                texts = self.asr_model.decode_many(xs, x_lens, self.lm, self.mapper, lm_weight,
-                                                   beam_size=beam, ctc_weight=ctc_weight, **terms)
+                if ctc_only is not None:
+                    texts = [hyps[0][0] for hyps in
+                             self.asr_model.decode_ctc(xs, x_lens, self.mapper, beam_size=ctc_only)]
+                else:
+                    texts = self.asr_model.decode_many(xs, x_lens, self.lm, self.mapper, lm_weight,
+                                                       beam_size=beam, ctc_weight=ctc_weight, **terms)
                 if self.decode_mbr is not None:  # the n-best lists are still on the device: one launch for the group
                     chosen = self.asr_model.mbr(self.mapper, posterior='softmax', **self.decode_mbr)
                     texts = [m.text for m in chosen]

@@ -23,7 +23,8 @@
  *   - return 0 on success, a negative value for an argument error, a positive
  *     hipError_t for a HIP failure.
  *
- * ABI history.  Added under 16 without changing anything older (the version number stays): ssasr_gemm_tile_choice; beam search --
+ * ABI history.  Added under 16 without changing anything older (the version number stays): ssasr_gemm_tile_choice; the encoder's
+ * launch-form query -- ssasr_bilstm_forms; beam search --
  * ssasr_beam, ssasr_decode_beam_ws_bytes, ssasr_decode_beam; joint CTC / attention decoding -- ssasr_ctc_prefix,
  * ssasr_decode_beam_ctc_ws_bytes, ssasr_decode_beam_ctc; length bonus, coverage term and end detection in the beam
  * search -- ssasr_beam_terms, ssasr_decode_beam_ex_ws_bytes, ssasr_decode_beam_ex; SpecAugment in batch assembly and label smoothing in the
@@ -132,6 +133,15 @@ int ssasr_gemm_tile_choice(int ta, int tb, int64_t M, int64_t N, int64_t K, int6
  * cs is not touched and may be NULL.  The same pointer must be passed to the backward call.
  * Replaces: pBLSTM.forward / nn.LSTM, src/asr.py:406-427, :262. */
 int64_t ssasr_bilstm_tsave_floats(int64_t S, int64_t N, int64_t H);
+/* Which launch forms ssasr_bilstm_fwd and ssasr_bilstm_bwd take for column window `window` (0 .. ceil(N / 128) - 1) of
+ * a layer under the current switches, given both sets of workspaces, contiguous 16-byte aligned buffers and all four
+ * biases; answered by the decision functions the launches themselves call (occupancy answers are cached per kernel).
+ * *fwd: 0 = one launch per step; 100 + c = the persistent recurrence, 200 + c = the persistent recurrence with the
+ * fused input projection (I = 80, H = 256), c = 16 | 32 columns per workgroup in that window's launch.
+ * *bwd, for a launch over the whole layer (iterations 0 .. S): 0 = one launch per step, 1 = the K-split persistent
+ * BPTT, 2 = K-split with two workgroups per (unit tile, chunk) ("halves").  A forward that is persistent saves
+ * tile-major exactly when ssasr_bilstm_tsave_floats is non-zero.  Returns 0, or negative for an argument error. */
+int ssasr_bilstm_forms(int64_t S, int64_t N, int64_t I, int64_t H, int64_t window, int* fwd, int* bwd);
 int64_t ssasr_bilstm_fwd_hx_floats(int64_t S, int64_t N, int64_t H);      /* 0: no persistent form for the shape */
 int ssasr_bilstm_fwd(const float* x, int64_t xs_s, int64_t xs_n, int64_t S, int64_t N, int64_t I,
                      int64_t H, const int32_t* lens, const float* w_ih_f, const float* w_hh_f,

@@ -108,6 +108,20 @@ static bool fwd_windows_fit(int64_t S, int64_t N, int64_t H, bool plain, bool fu
   return true;
 }
 
+// THE decision between the forward's forms: ssasr_bilstm_fwd launches what this says and ssasr_bilstm_forms reports
+// it.  ws_ok: the caller gave both workspaces and every buffer the persistent kernel touches with 16-byte accesses
+// is aligned; in_ok: all four biases are there and the input side (x, W_ih, the x strides) is aligned for the fused
+// input projection.  Every window's grid must be resident for the instance that is launched.
+struct FwdForm { bool persistent, fused; };
+static FwdForm fwd_form(int64_t S, int64_t N, int64_t I, int64_t H, bool ws_ok, bool in_ok) {
+  FwdForm f{ws_ok, false};
+  // narrow input (the 80 mel bins of the first layer): the recurrence waves form the
+  // pre-activations themselves; no input projection GEMM (rnn_kernels.h, KI)
+  f.fused = f.persistent && H / 64 == 4 && I == 80 && in_ok && !ssasr_options().no_fused_input;
+  if (!(f.persistent && fwd_windows_fit(S, N, H, !f.fused, f.fused))) f.persistent = f.fused = false;
+  return f;
+}
+
 // Floats of the forward recurrence's exchange images, one [2][S][H/4][Np][4] per column window back to back,
 // Np = the window's columns rounded up to whole 128-byte lines (0: the shape has no persistent form).
 extern "C" int64_t ssasr_bilstm_fwd_hx_floats(int64_t S, int64_t N, int64_t H) {
@@ -171,16 +185,13 @@ extern "C" int ssasr_bilstm_fwd(const float* x, int64_t xs_s, int64_t xs_n, int6
   {
     const int kpw = (int)(H / 64);
     const int64_t nwin = window_count(N);
-    bool fits = hx && sync_ws && aligned16(hx) && aligned16(gates) && aligned16(cs) && aligned16(y) && ys_s % 4 == 0 &&
-                ys_n % 4 == 0;
     // status words are zero on entry (caller's contract)
-    // narrow input (the 80 mel bins of the first layer): the recurrence waves form the
-    // pre-activations themselves; no input projection GEMM (rnn_kernels.h, KI)
-    bool fuse_in = fits && kpw == 4 && I == 80 && bih[0] && bhh[0] && bih[1] && bhh[1] &&
-                   aligned16(x) && aligned16(w_ih_f) && aligned16(w_ih_r) && xs_s % 4 == 0 && xs_n % 4 == 0 &&
-                   !opt.no_fused_input;
-    // every window's grid must be resident for the instance that is launched
-    if (!(fits && fwd_windows_fit(S, N, H, !fuse_in, fuse_in))) fits = fuse_in = false;
+    const bool ws_ok = hx && sync_ws && aligned16(hx) && aligned16(gates) && aligned16(cs) && aligned16(y) &&
+                       ys_s % 4 == 0 && ys_n % 4 == 0;
+    const bool in_ok = bih[0] && bhh[0] && bih[1] && bhh[1] && aligned16(x) && aligned16(w_ih_f) && aligned16(w_ih_r) &&
+                       xs_s % 4 == 0 && xs_n % 4 == 0;
+    const FwdForm form = fwd_form(S, N, I, H, ws_ok, in_ok);
+    const bool fits = form.persistent, fuse_in = form.fused;
     // tile-major saves exist in the persistent form only: a caller that passes the buffer was told
     // by ssasr_bilstm_tsave_floats that this shape takes it
     if (tsave && !fits) return SSASR_EARG;
@@ -284,6 +295,27 @@ static int bptt_reserve_bytes(BpttKernel kernel) {
   return reserve;
 }
 
+// THE decision between the K-split forms of one window's launch over `steps` iterations (Nw columns): launch_bptt_window
+// launches what this says and ssasr_bilstm_forms reports it.  ok = false: neither grid is resident (one launch per step).
+struct BpttForm { bool ok, halves; BpttKernel kernel; int reserve; };
+static BpttForm bptt_window_form(int64_t Nw, int64_t H, int dirs, int64_t steps) {
+  const int kpw = (int)(H / 16);
+  const int64_t workgroups = bptt_workgroups(Nw, H, dirs);
+  BpttForm f{};
+  // two workgroups per (unit tile, chunk) halve the product on the critical path (H >= 128)
+  // (not for launches of fewer than three steps: see the note on in-place rows in rnn_kernels.h)
+  f.halves = kpw >= 8 && workgroups * 2 <= 256 && steps >= 3 && !ssasr_options().bptt_halves_off;
+  f.kernel = bptt_kernel(kpw, f.halves);
+  f.reserve = bptt_reserve_bytes(f.kernel);
+  if (f.halves && !grid_fits(f.kernel, 320, (size_t)f.reserve, workgroups * 2)) {
+    f.halves = false;
+    f.kernel = bptt_kernel(kpw, false);
+    f.reserve = bptt_reserve_bytes(f.kernel);
+  }
+  f.ok = f.halves || grid_fits(f.kernel, 320, (size_t)f.reserve, workgroups);
+  return f;
+}
+
 // Floats of the tile-major save buffer of a layer, 0 when the shape does not take BOTH persistent
 // forms (the forward kernel that writes it and the K-split BPTT that reads it).
 extern "C" int64_t ssasr_bilstm_tsave_floats(int64_t S, int64_t N, int64_t H) {
@@ -307,20 +339,12 @@ struct BpttProgress { unsigned* words; int n; int bound[7]; };
 // One column window of a layer: p holds the window's pointers, its width p.N and the layer's width p.nt (0: the
 // launch covers the layer), and iterations [p.i0, p.i1) of the p.S steps.
 static int launch_bptt_window(const EncPersistBwd& p, int dirs, hipStream_t st, void* stop_event) {
-  const int kpw = p.H / 16;
-  const int64_t workgroups = bptt_workgroups(p.N, p.H, dirs);
   const bool ranged = p.i0 != 0 || p.i1 != p.S;
-  // two workgroups per (unit tile, chunk) halve the product on the critical path (H >= 128)
-  // (not for launches of fewer than three steps: see the note on in-place rows in rnn_kernels.h)
-  bool halves = kpw >= 8 && workgroups * 2 <= 256 && p.i1 - p.i0 >= 3 && !ssasr_options().bptt_halves_off;
-  BpttKernel kernel = bptt_kernel(kpw, halves);
-  int reserve = bptt_reserve_bytes(kernel);
-  if (halves && !grid_fits(kernel, 320, (size_t)reserve, workgroups * 2)) {
-    halves = false;
-    kernel = bptt_kernel(kpw, false);
-    reserve = bptt_reserve_bytes(kernel);
-  }
-  if (!halves && !grid_fits(kernel, 320, (size_t)reserve, workgroups)) return SSASR_EARG;
+  const BpttForm form = bptt_window_form(p.N, p.H, dirs, p.i1 - p.i0);
+  if (!form.ok) return SSASR_EARG;
+  const bool halves = form.halves;
+  const BpttKernel kernel = form.kernel;
+  const int reserve = form.reserve;
   // (a range shorter than the hand-off distance between the two halves could rewrite dc_state early)
   if (halves && ranged && p.i1 < p.S && p.i1 - p.i0 < 4) return SSASR_EARG;
   // Placement: the weight-gradient GEMMs of the previous range / layer run beside this kernel on
@@ -381,6 +405,21 @@ int ssasr_launch_bptt_persistent(const float* whhT, float* gates, const float* c
     const int rc = launch_bptt_window(p, dirs, st, w == nwin - 1 ? stop_event : nullptr);
     if (rc) return rc;
   }
+  return SSASR_OK;
+}
+
+// Which forms a layer's launches take for column window `window` under the current switches (include/ssasr.h):
+// answered by fwd_form / ssasr_bptt_ksplit_ok / bptt_window_form, the functions the launches themselves ask.
+extern "C" int ssasr_bilstm_forms(int64_t S, int64_t N, int64_t I, int64_t H, int64_t window, int* fwd, int* bwd) {
+  if (S <= 0 || N <= 0 || I <= 0 || H <= 0 || H % 16 != 0 || window < 0 || window >= window_count(N) || !fwd || !bwd)
+    return SSASR_EARG;
+  const FwdForm f = fwd_form(S, N, I, H, true, true);
+  *fwd = f.persistent ? (f.fused ? 200 : 100) + 16 * fwd_window(N, H, window).nb : 0;
+  // a layer's BPTT is persistent when every window's launch is (ssasr_launch_bptt_persistent stops at the first
+  // window that is not; the first is the widest)
+  bool ksplit = ssasr_bptt_ksplit_ok(S, N, H, 2);
+  for (int64_t w = 0; ksplit && w < window_count(N); ++w) ksplit = bptt_window_form(window_width(N, w), H, 2, S).ok;
+  *bwd = !ksplit ? 0 : bptt_window_form(window_width(N, window), H, 2, S).halves ? 2 : 1;
   return SSASR_OK;
 }
 

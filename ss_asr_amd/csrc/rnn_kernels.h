@@ -1391,9 +1391,19 @@ __global__ __launch_bounds__(320) void lstm_enc_bwd_rs_kernel(EncPersistBwd e) {
       }
       SSASR_PTRACE(i, 10);
       const unsigned base = (unsigned)(i % BWD_RS_RING) * SLOT_B + (unsigned)tile * TILE_B;   // source = this tile
+      // Every tile's sum is in registers of ITS OWN before the first store is issued.  Left to itself the compiler gave
+      // the <2, 1> instance ONE register quad for both tiles -- store, two v_pk_add_f32 into the same quad in the very
+      // next cycles, store -- and the first tile reached the ring with columns 12 .. 15 of every unit quad already holding
+      // the second tile's sums (a 16-byte store still reads its data when the next vector instructions run; no wait
+      // state is inserted for a store with a register soffset).  No other instance had that schedule; DESIGN.md 4.2.1.
+      f32x4 out[OT];
+#pragma unroll
+      for (int t = 0; t < OT; ++t) out[t] = acc[t] + acc2[t];
+#pragma unroll
+      for (int t = 0; t < OT; ++t) asm volatile("" : "+v"(out[t]));
 #pragma unroll
       for (int t = 0; t < OT; ++t) {
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[t] + acc2[t]), xrs,
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, out[t]), xrs,
                                                (int)((otile0 + t) * T * TILE_B + lane * 16), (int)base, 16);
       }
       SSASR_PTRACE(i, 7);

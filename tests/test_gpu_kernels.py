@@ -218,7 +218,8 @@ def lstm_weights(I, H, seed):
     (3, 10, 80, 256, [10, 8, 5]),             # production widths (vector path)
     # 48 / 64 columns at H = 256: the forward takes two 32-column chunks of 256 workgroups in all,
     # the second chunk of N = 48 half empty (its padded lanes once aliased chunk 0's column, which is
-    # what timed out under an exchange ring: DESIGN.md 4.2); the BPTT runs 3 / 4 chunks without halves
+    # what timed out under an exchange ring: DESIGN.md 4.2); the BPTT runs 3 / 4 chunks WITH halves (16 x 2 x 3 x 2 = 192
+    # and 16 x 2 x 4 x 2 = 256 workgroups fit: ssasr_bilstm_forms says 2 for both, pinned in test_gpu_bilstm_forms.py)
     (48, 40, 64, 256, [40] * 10 + [33] * 20 + [9] * 18),
     (64, 24, 64, 256, [24] * 30 + [11] * 34),
     # H = 256, N <= 32: full chunks with ragged lengths; a last chunk of 13 live columns; the fused 80-bin input

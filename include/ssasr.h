@@ -647,6 +647,55 @@ int ssasr_mwer_pack(const int32_t* chars, const int32_t* n_chars, const int32_t*
 int ssasr_rows_repeat_fwd(const void* src, int64_t G, int64_t M, int64_t n, void* dst, void* stream);
 int ssasr_rows_repeat_bwd(const float* ddst, int64_t G, int64_t M, int64_t n, float* dsrc, void* stream);
 
+/* ---- n-best rescoring (added under ABI 16) -----------------------------------------------------------------------
+ * BUILD-DEFINED: the reference has no n-best list.  The second pass of two-pass decoding: the K texts that a first
+ * pass left for each of G utterances (ssasr_ctc_decode's, ssasr_decode_beam's or ssasr_decode_sample's chars, n_chars,
+ * n_hyps and scores) are teacher-forced through the Speller (and the CharLM) by the caller, and ONE launch, one
+ * workgroup per utterance, scores every text under those logits, forms the weighted total, ranks the list and writes
+ * it out in rank order.
+ *   logits float [R][U][V], R = G * M, row r = g * M + k being candidate k of group g: ssasr_mwer_loss_fwd's layout
+ *   (ssasr_mwer_pack with ref_cols = 0 gives M = K + 1, the group's last row idle).
+ *   lm_logits float or NULL (no LM term): step t of row r starts at lm_logits + r * lm_row_stride + t *
+ *   lm_step_stride, its V entries at unit stride ([U][R][V] as ssasr_charlm_train_fwd leaves them: strides V and R V).
+ *   y int32 [R][y_cols], row stride y_ld: labels and masking are ssasr_mwer_loss_fwd's -- the label of step t is
+ *   y[r][t + 1]; 0, an id outside 1 .. V - 1 and a column past y_cols are unlabelled; nothing is read out of bounds.
+ *   n_hyps int32 [G]: the candidates of group g are the rows k < n_g = clamp(n_hyps[g], 0, K), K <= M.
+ *   first float [G][K]: the first pass's scores.  chars int32 [G][K][steps], n_chars int32 [G][K]: the list.
+ * Definition, every sequence-level quantity in double:
+ *   att_k   = sum over labelled t of (z[t][lab] - lse_t): the logP_r of the MWER section above, formed by the same
+ *             device function (csrc/seq_logp.h), the steps added in ascending t
+ *   lm_k    = the same sum over lm_logits; 0 when lm_logits is NULL
+ *   len_k   = clamp(n_chars[g][k], 0, steps)
+ *   total_k = att_weight att_k + lm_weight lm_k + first_weight first_k + length_bonus len_k: each product rounded on
+ *             its own (no fused multiply-add), added in this order, rounded ONCE to float.  A term whose weight is
+ *             exactly 0 is left out, not multiplied: a -inf or NaN first-pass score does not poison the total when
+ *             first_weight == 0.
+ *   rank:     non-increasing float total, equal totals in input-slot order, a NaN total counting as -inf (it is
+ *             written as it is): rank(k) = #{j < n_g: total_j > total_k or (total_j == total_k and j < k)}.
+ * Outputs, every element written; none may overlap an input:
+ *   order int32 [G][K]: the input slot at each rank.  total float [G][K] and parts float [G][K][3] = (att, lm, first),
+ *   each rounded once, in rank order.  chars_out [G][K][steps], n_chars_out [G][K] (= len), n_hyps_out [G] (= n_g): the
+ *   list in rank order, in the layout of the inputs; characters from a text's length on are 0.
+ *   Ranks from n_g on: order -1, length 0, characters 0, parts 0 and total 0 -- what ssasr_decode_beam leaves in the
+ *   slots it does not use (ssasr_ctc_decode leaves -inf there; readers go by n_hyps).
+ * An utterance's results depend on its own rows alone: the same bits in any group, with or without the workspace.
+ * Accepted: V > 0, U > 0, 1 <= K <= M <= 33, K <= 32, G * M <= 65535, y_cols >= U + 1, y_ld >= y_cols, steps >= 1,
+ * lm strides >= V, finite weights, ws 8-byte aligned with ws_bytes >= ssasr_rescore_ws_bytes(G, K, U) when that is
+ * > 0.  G == 0 launches nothing.  Argument errors return a negative code before any HIP call.
+ * 256 threads per utterance: a wave per (k, t) step of the candidates, strided, the step's logits in registers as in
+ * ssasr_mwer_loss_fwd (V <= 256 is read once; V <= 64 is one value per lane); the per-step terms (2 K U doubles) wait
+ * in LDS when they fit 32 KB, else in the utterance's slice of ws; then a lane per candidate adds its terms, the first
+ * wave ranks by counting, and all waves copy the texts.  No exchange between workgroups, no spins, no atomics; every
+ * loop is bounded by K, U, V or steps. */
+/* Bytes of `ws`: 0 when LDS holds the terms (2 K U <= 4096), else 16 G K U; -1 for sizes that are not accepted. */
+int64_t ssasr_rescore_ws_bytes(int64_t G, int64_t K, int64_t U);
+int ssasr_rescore(const float* logits, const float* lm_logits, int64_t lm_row_stride, int64_t lm_step_stride,
+                  const int32_t* y, int64_t y_ld, int64_t y_cols, const int32_t* n_hyps, const float* first,
+                  const int32_t* chars, const int32_t* n_chars, int64_t G, int64_t M, int64_t K, int64_t U, int64_t V,
+                  int64_t steps, float att_weight, float lm_weight, float first_weight, float length_bonus,
+                  void* ws, int64_t ws_bytes, int32_t* order, float* total, float* parts, int32_t* chars_out,
+                  int32_t* n_chars_out, int32_t* n_hyps_out, void* stream);
+
 /* Solver.step (src/trainer.py:131-148) with torch.optim.Adadelta
  * (src/trainer.py:401-403) on flat buffers of n floats: total L2 norm of
  * grad * grad_scale, NaN guard, clip to max_norm, Adadelta update.

@@ -155,6 +155,9 @@ SIGNATURES = {
     'ssasr_mwer_pack': (I32, [P, P, P, P, I64, I64, I64, I64, I64, I32, I64, P, P, P]),
     'ssasr_rows_repeat_fwd': (I32, [P, I64, I64, I64, P, P]),
     'ssasr_rows_repeat_bwd': (I32, [P, I64, I64, I64, P, P]),
+    'ssasr_rescore_ws_bytes': (I64, [I64, I64, I64]),
+    'ssasr_rescore': (I32, [P, P, I64, I64, P, I64, I64, P, P, P, P, I64, I64, I64, I64, I64, I64, F32, F32, F32, F32,
+                            P, I64, P, P, P, P, P, P, P]),
     'ssasr_clip_adadelta_ws': (I64, [I64]),
     'ssasr_clip_adadelta': (I32, [P, P, P, P, I64, F32, F32, F32, F32, F32, P, P, I32, P]),
     'ssasr_adam_ws': (I64, [I64]),

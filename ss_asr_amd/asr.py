@@ -307,6 +307,8 @@ class ASR(nn.Module):
         # decode_ctc's device results: (chars [N, Kr, T'] int32, n_chars [N, Kr] int32, scores [N, Kr], n_hyps [N] int32,
         # logits [N, T', V])
         self.last_ctc_decode = None
+        # rescore's device results: (order [N, K] int32, total [N, K], parts [N, K, 3] = (att, lm, first)), in rank order
+        self.last_rescore = None
         self.init_parameters()
 
     def init_parameters(self):
@@ -719,6 +721,53 @@ class ASR(nn.Module):
             chars, n_chars, scores, n_hyps, _ = self.last_ctc_decode
             self._keep_hyps(chars, n_chars, n_hyps, scores, sampled=False)
         return self._texts(chars, n_chars, n_hyps, scores, mapper)
+
+    def rescore(self, mapper, *, rnn_lm=None, lm_weight=0.0, att_weight=1.0, first_weight=0.0, length_bonus=0.0):
+        """BUILD-DEFINED: attention rescoring of the list that the last decode_nbest / decode_ctc / sample call left on
+        the device (last_hyps, last_hyp_scores), on that call's encoder output (last_encoded_packed: no second encode).
+        The K texts of every utterance are teacher-forced through the Speller (and, with rnn_lm and lm_weight != 0,
+        the CharLM), and one launch scores, ranks and reorders each list (ops.rescore; ssasr_rescore, include/ssasr.h):
+          total = att_weight * log P_speller(text, <EOS>) + lm_weight * log P_lm(text, <EOS>)
+                  + first_weight * (the first pass's score) + length_bonus * len(text).
+        Returns per utterance the list of (text, total), best first.  last_rescore keeps (order, total, parts) on the
+        device; the list is re-kept in rank order with `total` as its scores (the sampled flag unchanged), so score(),
+        mbr() and align() follow it.  A call before any decode, a non-finite weight, or all four weights zero is a
+        ValueError."""
+        if self.last_hyps is None or self.last_hyp_scores is None or self.last_encoded_packed is None:
+            raise ValueError('rescore: nothing decoded yet (decode_nbest / decode_ctc / sample leave the hypotheses)')
+        weights = dict(att_weight=att_weight, lm_weight=lm_weight, first_weight=first_weight, length_bonus=length_bonus)
+        for name, value in weights.items():
+            weights[name] = float(value)
+            if not math.isfinite(weights[name]):
+                raise ValueError('rescore: %s must be finite, got %r' % (name, value))
+        if not any(weights.values()):
+            raise ValueError('rescore: att_weight, lm_weight, first_weight and length_bonus are all zero')
+        chars, n_chars, n_hyps = self.last_hyps
+        packed, enc_lens = self.last_encoded_packed
+        if packed.shape[0] != chars.shape[0]:
+            raise ValueError('rescore: the encoded group holds %d utterances, the list %d'
+                             % (packed.shape[0], chars.shape[0]))
+        with torch.no_grad():
+            order, total, parts, chars, n_chars, n_hyps = ops.rescore(
+                packed, enc_lens, self._decoder_params(), (self.attention.psi.weight, self.attention.psi.bias),
+                chars, n_chars, n_hyps, self.last_hyp_scores, int(mapper.char_to_ind(EOS_TKN)), rnn_lm, **weights)
+        self.last_rescore = (order, total, parts)
+        self._keep_hyps(chars, n_chars, n_hyps, total, sampled=self.last_hyps_sampled)
+        return self._texts(chars, n_chars, n_hyps, total, mapper)
+
+    def decode_two_pass(self, xs, x_lens, rnn_lm, mapper, lm_weight, *, beam_size=8, ctc_weight=0.3, length_bonus=0.0):
+        """BUILD-DEFINED: two-pass decoding on a model with a ctc_head: decode_ctc(beam_size >= 1), the CTC prefix beam
+        search with no Speller step, then rescore() of its list with att_weight = 1 - ctc_weight, first_weight =
+        ctc_weight and the CharLM at lm_weight -- decode_nbest's joint weighting applied to whole texts.  ctc_weight in
+        [0, 1].  Returns per utterance the list of (text, total), best first; last_ctc_decode keeps the first pass,
+        last_rescore the second."""
+        if isinstance(ctc_weight, bool) or not isinstance(ctc_weight, (int, float)) or not 0.0 <= ctc_weight <= 1.0:
+            raise ValueError('ctc_weight must be a number in [0, 1], got %r' % (ctc_weight,))
+        if isinstance(beam_size, bool) or not isinstance(beam_size, int) or not 1 <= beam_size <= ops.CTC_DECODE_MAX_BEAM:
+            raise ValueError('beam_size must be an integer in 1..%d, got %r' % (ops.CTC_DECODE_MAX_BEAM, beam_size))
+        self.decode_ctc(xs, x_lens, mapper, beam_size=beam_size)
+        return self.rescore(mapper, rnn_lm=rnn_lm, lm_weight=lm_weight, att_weight=1.0 - float(ctc_weight),
+                            first_weight=float(ctc_weight), length_bonus=length_bonus)
 
     def sample(self, xs, x_lens, mapper, n_samples, *, temperature=1.0, rnn_lm=None, lm_weight=0.0,
                max_decoding_steps=200, generator=None, uniforms=None):

@@ -14,14 +14,13 @@
 //      block sums the groups' contributions: thread t takes groups t, t + 256, ... in order, the 256 partial sums are
 //      added in index order by thread 0.  No atomics: the same bits every run.
 // Backward: mwer_bwd_kernel, a wave per (r, t) step: unlabelled steps are stored as zeros without a load.
-#include "common.h"
+#include "seq_logp.h"
 #include "../../include/ssasr.h"
 
 namespace {
 
 constexpr int MWER_G = 8;          // blocks per row: steps t = g, g + MWER_G, ... (four waves each)
 constexpr int MWER_MAX_M = 33;     // candidates per group: a beam of 32 and the reference row
-constexpr int MWER_REG = 4;        // logits a lane keeps in registers: rows of V <= 256 are read once
 
 // The workspace: doubles first -- logP [R], p [R], w [R], Rbar [G], the groups' CE terms [G], per-block shares
 // [R][MWER_G], the log-sum-exp [R][U] as the backward reads it -- then lse [R][U] as float.
@@ -50,24 +49,6 @@ __host__ __device__ inline MwerWs mwer_ws(void* ws, int64_t G, int64_t M, int64_
   return w;
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-// the label of step t of a row, 0 (unlabelled) for a column past y_cols and for an id that names no class
-__device__ __forceinline__ int mwer_label(const int32_t* yr, int t, int y_cols, int V) {
-  const int lab = t + 1 < y_cols ? yr[t + 1] : 0;
-  return lab > 0 && lab < V ? lab : 0;
-}
-
 __global__ __launch_bounds__(256) void mwer_rows_kernel(const float* logits, const int32_t* y, int64_t y_ld,
                                                         int y_cols, int U, int V, float* lse, double* lse64,
                                                         double* part) {
@@ -77,28 +58,12 @@ __global__ __launch_bounds__(256) void mwer_rows_kernel(const float* logits, con
   double acc = 0.0;                    // lane 0: sum over this wave's labelled steps of z[lab] - lse
   for (int t = g + MWER_G * wave; t < U; t += 4 * MWER_G) {
     const float* row = logits + ((int64_t)r * U + t) * V;
-    float z[MWER_REG];
-    float m = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < MWER_REG; ++i) {
-      const int v = lane + 64 * i;
-      z[i] = v < V ? row[v] : -INFINITY;
-      m = fmaxf(m, z[i]);
-    }
-    for (int v = lane + 64 * MWER_REG; v < V; v += 64) m = fmaxf(m, row[v]);
-    m = wave_max(m);
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < MWER_REG; ++i)
-      if (lane + 64 * i < V) s += exp((double)z[i] - (double)m);
-    for (int v = lane + 64 * MWER_REG; v < V; v += 64) s += exp((double)row[v] - (double)m);
-    s = wave_sum_f64(s);
-    const double ld = (double)m + log(s);
-    const int lab = mwer_label(yr, t, y_cols, V);
+    const double ld = seq_step_lse(row, V, lane);
+    const int lab = seq_label(yr, t, y_cols, V);
     if (lane == 0) {
       lse[(int64_t)r * U + t] = (float)ld;          // the correctly rounded value, as the LS kernel saves it
       lse64[(int64_t)r * U + t] = ld;               // what the backward normalises by: a step's dlogits then sum to 0
-      if (lab != 0) acc += (double)row[lab] - ld;
+      if (lab != 0) acc += seq_step_term(row, lab, ld);
     }
   }
   if (lane == 0) sm[wave] = acc;
@@ -170,7 +135,7 @@ __global__ __launch_bounds__(256) void mwer_bwd_kernel(const float* logits, cons
   if (s >= steps) return;
   const int64_t r = s / U;
   const int t = (int)(s - r * U);
-  const int lab = mwer_label(y + r * y_ld, t, y_cols, V);
+  const int lab = seq_label(y + r * y_ld, t, y_cols, V);
   float* out = dlogits + s * V;
   if (lab == 0) {
     for (int v = lane; v < V; v += 64) out[v] = 0.f;

@@ -1346,6 +1346,124 @@ def rows_repeat(t, M):
 
 
 # ---------------------------------------------------------------------------
+# n-best rescoring (build-defined; include/ssasr.h, "n-best rescoring")
+# ---------------------------------------------------------------------------
+RESCORE_MAX_ROWS = 33          # ssasr_rescore's limit on the rows of a group
+RESCORE_LOOP_ROWS = 32         # rows of one teacher-forced decoder_loop call: the persistent loop's limit (B <= 32)
+RESCORE_MAX_CALLS = 5          # more persistent calls than this are slower than one call over all rows
+
+
+def rescore_launch(logits, lm_logits, rows, n_hyps, first, chars, n_chars, *, att_weight=1.0, lm_weight=0.0,
+                   first_weight=0.0, length_bonus=0.0):
+    """ssasr_rescore: scores, ranks and reorders each utterance's list in one launch (include/ssasr.h;
+    postprocess.rescore_reference is its float64 restatement).  logits [R, U, V] float32 of R = G * M teacher-forced
+    rows (row g * M + k: candidate k of group g); lm_logits None or a float32 tensor indexed [R, U, V] with unit
+    stride over V and any row / step strides (charlm_chunk's [U, R, V] as .permute(1, 0, 2)); rows int32 [R, >= U + 1],
+    the rows' label matrix; n_hyps int32 [G]; first float32 [G, K]; chars int32 [G, K, steps]; n_chars int32 [G, K];
+    K <= M.  -> (order int32 [G, K], total [G, K], parts [G, K, 3] = (att, lm, first), chars [G, K, steps],
+    n_chars [G, K], n_hyps [G]) on the device, the list in rank order.  No autograd."""
+    lib = _lib.load()
+    _need_gpu(logits, lm_logits, rows, n_hyps, first, chars, n_chars)
+    weights = [float(w) for w in (att_weight, lm_weight, first_weight, length_bonus)]
+    if not all(math.isfinite(w) for w in weights):
+        raise ValueError('rescore: the weights must be finite, got %r' % (weights,))
+    logits = _f32c(logits.detach())
+    if logits.dim() != 3:
+        raise ValueError('rescore: logits must be [rows, steps, classes]')
+    R, U, V = logits.shape
+    if rows.dtype != torch.int32 or rows.dim() != 2 or rows.stride(1) != 1 or rows.shape[0] != R or rows.shape[1] < U + 1:
+        raise TypeError('rescore: rows must be int32 [%d, >= %d] with unit column stride' % (R, U + 1))
+    if chars.dtype != torch.int32 or chars.dim() != 3 or not chars.is_contiguous():
+        raise TypeError('rescore: chars must be a contiguous int32 tensor [G, K, steps]')
+    G, K, steps = chars.shape
+    for name, t, shape in (('n_chars', n_chars, (G, K)), ('n_hyps', n_hyps, (G,))):
+        if t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise TypeError('rescore: %s must be a contiguous int32 tensor of shape %r' % (name, shape))
+    first = _f32c(first.detach())
+    if tuple(first.shape) != (G, K):
+        raise ValueError('rescore: first must be %r, got %r' % ((G, K), tuple(first.shape)))
+    if (G == 0) != (R == 0) or (G and R % G):
+        raise ValueError('rescore: %d rows do not form %d equal groups' % (R, G))
+    M = R // G if G else K
+    need = int(lib.ssasr_rescore_ws_bytes(G, K, U))
+    if need < 0 or not K <= M <= RESCORE_MAX_ROWS or steps < 1:
+        raise ValueError('rescore: no kernel for %d groups of %d rows, %d candidates, %d steps (1 <= candidates <= %d, '
+                         'candidates <= rows <= %d)' % (G, M, K, U, MAX_BEAM, RESCORE_MAX_ROWS))
+    lm_row = lm_step = 0
+    if lm_logits is not None:
+        if lm_logits.dtype != torch.float32 or tuple(lm_logits.shape) != (R, U, V) or (V > 1 and lm_logits.stride(2) != 1):
+            raise TypeError('rescore: lm_logits must be float32, indexed %r with unit stride over the classes'
+                            % ((R, U, V),))
+        lm_logits = lm_logits.detach()
+        lm_row, lm_step = max(lm_logits.stride(0), V), max(lm_logits.stride(1), V)
+    dev = logits.device
+    ws = torch.empty(need // 8, device=dev, dtype=torch.float64) if need else None
+    order = torch.empty(G, K, device=dev, dtype=torch.int32)
+    total = torch.empty(G, K, device=dev, dtype=torch.float32)
+    parts = torch.empty(G, K, 3, device=dev, dtype=torch.float32)
+    chars_out, n_chars_out, n_hyps_out = torch.empty_like(chars), torch.empty_like(n_chars), torch.empty_like(n_hyps)
+    check(lib.ssasr_rescore(_p(logits), _p(lm_logits), lm_row, lm_step, _p(rows), rows.stride(0), rows.shape[1],
+                            _p(n_hyps), _p(first), _p(chars), _p(n_chars), G, M, K, U, V, steps, *weights, _p(ws), need,
+                            _p(order), _p(total), _p(parts), _p(chars_out), _p(n_chars_out), _p(n_hyps_out), _stream()),
+          'ssasr_rescore')
+    return order, total, parts, chars_out, n_chars_out, n_hyps_out
+
+
+def rescore_loop_rows(T):
+    """Rows per teacher-forced call that keep the decode loop in its single-launch persistent form: 32 up to 128
+    encoder frames, beyond that what the long form's B * ceil(T' / 64) <= 192 leaves."""
+    return RESCORE_LOOP_ROWS if T <= 128 else max(1, min(RESCORE_LOOP_ROWS, 192 // ((T + 63) // 64)))
+
+
+def rescore_logits(feat, enc_len, params, psi, rows, M, U, *, loop_rows=None):
+    """The teacher-forced pass of rescore(): feat [N, T', E] and enc_len int32 [N] repeated M times, the decode loop
+    over the N * M rows of `rows` for U steps, every step in mode 0, without grad.  loop_rows: rows per decoder_loop
+    call; 0: ONE call over all rows (past 32 rows one launch per stage and step); None: the faster of the two as
+    measured -- calls of rescore_loop_rows(T') rows, each the single-launch persistent loop, up to
+    RESCORE_MAX_CALLS of them (0.55 ms each at 68 steps: 2.8 ms for 160 rows beside 3.0 ms), one call beyond (3.3 ms
+    for 256 rows beside 4.2 ms).
+    -> logits [N * M, U, V]."""
+    with torch.no_grad():
+        comp = attn_precompute(_f32c(feat.detach()), psi[0].detach(), psi[1].detach())
+        feat_r, comp_r, len_r = rows_repeat(feat.detach(), M), rows_repeat(comp, M), rows_repeat(enc_len, M)
+        R = rows.shape[0]
+        step = R if loop_rows == 0 else int(loop_rows or rescore_loop_rows(feat.shape[1]))
+        if loop_rows is None and (R + step - 1) // step > RESCORE_MAX_CALLS:
+            step = R
+        modes = [0] * U
+        modes_dev = torch.zeros(U, device=feat.device, dtype=torch.int32)
+        out = [decoder_loop(feat_r[lo:lo + step], comp_r[lo:lo + step], len_r[lo:lo + step], rows[lo:lo + step], modes,
+                            None, params, modes_dev=modes_dev)[0] for lo in range(0, R, step)]
+        return out[0] if len(out) == 1 else torch.cat(out, 0)
+
+
+def rescore(feat, enc_len, params, psi, chars, n_chars, n_hyps, first, eos, lm=None, *, att_weight=1.0, lm_weight=0.0,
+            first_weight=0.0, length_bonus=0.0, loop_rows=None, drop_idle=True):
+    """Attention rescoring of an n-best list (include/ssasr.h, "n-best rescoring"): the K texts per utterance in
+    chars [N, K, steps] / n_chars [N, K] / n_hyps [N] (int32, as the decoders leave them) with their first-pass scores
+    first [N, K] are packed into teacher rows (mwer_pack with an empty reference), teacher-forced through the Speller
+    on the encoder output feat [N, T', E] (rescore_logits) and, with lm and lm_weight != 0, through the CharLM
+    (charlm_chunk), then scored, ranked and reordered by one rescore_launch.  The one integer the host reads is the
+    longest text's length.  drop_idle: the empty reference row of each packed group is left out of the loop (M = K
+    rows per utterance instead of K + 1).  -> rescore_launch's six tensors."""
+    _need_gpu(feat, enc_len, chars, n_chars, n_hyps, first)
+    chars, n_chars, n_hyps = [t.to(torch.int32).contiguous() for t in (chars, n_chars, n_hyps)]
+    N, K, steps = chars.shape
+    with torch.no_grad():
+        rows, hyp_lens = mwer_pack(chars, n_chars, n_hyps, torch.empty(N, 0, device=chars.device, dtype=torch.int32), eos)
+        U = int(hyp_lens.max()) + 1
+        M = K + 1
+        if drop_idle:
+            rows, M = rows.view(N, K + 1, -1)[:, :K].reshape(N * K, -1), K
+        logits = rescore_logits(feat, enc_len, params, psi, rows, M, U, loop_rows=loop_rows)
+        lm_logits = None
+        if lm is not None and float(lm_weight) != 0.0:
+            lm_logits = charlm_chunk(lm, rows[:, 1:U + 1].contiguous(), want_logits=True).logits.permute(1, 0, 2)
+        return rescore_launch(logits, lm_logits, rows, n_hyps, first, chars, n_chars, att_weight=att_weight,
+                              lm_weight=lm_weight, first_weight=first_weight, length_bonus=length_bonus)
+
+
+# ---------------------------------------------------------------------------
 # misc
 # ---------------------------------------------------------------------------
 def frame_lengths(x):

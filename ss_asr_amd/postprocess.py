@@ -189,6 +189,63 @@ def mbr_reference(hyps, n_hyps, scores, space, first_char=2, unit='word', poster
     return best, risks, pairs
 
 
+def rescore_reference(logits, lm_logits, rows, n_hyps, first, n_chars, steps, *, att_weight=1.0, lm_weight=0.0,
+                      first_weight=0.0, length_bonus=0.0, dtype=np.float64):
+    """BUILD-DEFINED: n-best rescoring, ssasr_rescore (include/ssasr.h) restated over numpy rows and Python lists --
+    what the kernel is defined and tested against.  logits [R, U, V] of R = G * M teacher-forced rows (row g * M + k:
+    candidate k of group g); lm_logits the same shape or None; rows [R, cols] integer labels (the label of step t is
+    rows[r][t + 1]; 0, an id outside 1 .. V - 1 and a column past cols are unlabelled); n_hyps [G]; first [G][K]
+    first-pass scores and n_chars [G][K], K <= M; steps: the list's row length, which caps a length.  Every sum runs
+    in `dtype` (float64; float32 measures the arithmetic's noise).
+      att_k = sum over labelled t of log_softmax(logits[r, t])[label], in ascending t; lm_k the same over lm_logits
+      (0 without); len_k = clamp(n_chars, 0, steps); total_k = att_weight att_k + lm_weight lm_k + first_weight
+      first_k + length_bonus len_k, a term whose weight is exactly 0 being left out; the weights and first are taken
+      as float32 values.  Rank: non-increasing total as rounded to float32, equal values in slot order, NaN as -inf.
+    -> (order [G][K], total [G][K], parts [G][K][3] = (att, lm, first)) as lists in rank order, unrounded; ranks from
+    clamp(n_hyps[g], 0, K) on hold -1, 0.0 and zeros."""
+    z = np.asarray(logits, dtype=dtype)
+    zl = None if lm_logits is None else np.asarray(lm_logits, dtype=dtype)
+    rows = np.asarray(rows)
+    R, U, V = z.shape
+    G = len(n_hyps)
+    M = R // G if G else 1
+    K = len(first[0]) if G else 0
+    w = [dtype(np.float32(v)) for v in (att_weight, lm_weight, first_weight, length_bonus)]
+
+    def seq_logp(zr, r):
+        acc = dtype(0)
+        for t in range(U):
+            lab = int(rows[r][t + 1]) if t + 1 < rows.shape[1] else 0
+            if not 0 < lab < V:
+                continue
+            m = zr[t].max()
+            acc = acc + (zr[t][lab] - (m + np.log(np.exp(zr[t] - m).sum(dtype=dtype))))
+        return acc
+
+    orders, totals, parts = [], [], []
+    with np.errstate(all='ignore'):
+        for g in range(G):
+            n = min(max(int(n_hyps[g]), 0), K)
+            cand = []
+            for k in range(n):
+                r = g * M + k
+                att = seq_logp(z[r], r)
+                lm = seq_logp(zl[r], r) if zl is not None else dtype(0)
+                f = dtype(np.float32(first[g][k]))
+                length = min(max(int(n_chars[g][k]), 0), int(steps))
+                total = dtype(0)
+                for weight, term in zip(w, (att, lm, f, dtype(length))):
+                    if weight != 0:
+                        total = total + weight * term
+                key = np.float32(total)
+                cand.append((-math.inf if np.isnan(key) else float(key), k, float(total), [float(att), float(lm), float(f)]))
+            ranked = sorted(cand, key=lambda c: (-c[0], c[1]))
+            orders.append([c[1] for c in ranked] + [-1] * (K - n))
+            totals.append([c[2] for c in ranked] + [0.0] * (K - n))
+            parts.append([c[3] for c in ranked] + [[0.0, 0.0, 0.0] for _ in range(K - n)])
+    return orders, totals, parts
+
+
 def ctc_prefix_beam_reference(lp, K, blank=0, dtype=np.float64, trace=None):
     """BUILD-DEFINED: CTC-only decoding, ssasr_ctc_decode (include/ssasr.h) restated over Python tuples as texts --
     what the kernel is defined and tested against.  lp [T, V]: one utterance's log-probabilities, already cut to its

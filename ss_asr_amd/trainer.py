@@ -677,7 +677,13 @@ class ASRTester(Solver):
     with no Speller step (ASR.decode_ctc, ssasr_ctc_decode); asr.decode_beam_size, the language model and
     max_decode_step_ratio then play no part, and `decode_file` gains `_ctconly<beam_size>`.  It composes with
     decode_score, decode_mbr (which then needs THIS beam_size >= 2) and decode_align; together with a positive
-    asr.decode_ctc_weight or any of the beam search's terms it is an error."""
+    asr.decode_ctc_weight or any of the beam search's terms it is an error.
+    asr.decode_rescore: {ctc_weight: 0.3, length_bonus: 0.0} (absent: off; ctc_weight a number in [0, 1], length_bonus
+    finite, both optional; valid only together with asr.decode_ctc_only at beam_size >= 1, else set_model raises):
+    two-pass decoding -- every group's CTC list is teacher-forced through the Speller and re-ranked by (1 - ctc_weight)
+    log P_speller + ctc_weight * the CTC score + asr.decode_lm_weight * log P_lm + length_bonus * length
+    (ASR.decode_two_pass, ssasr_rescore) with the tester's language model; `decode_file` gains `_rescore<ctc_weight>`.
+    decode_score, decode_mbr and decode_align then see the re-ranked list."""
     decode_group = 32
     TERM_KEYS = ('decode_length_bonus', 'decode_coverage_weight', 'decode_coverage_threshold', 'decode_end_margin')
 
@@ -748,6 +754,30 @@ class ASRTester(Solver):
             raise ValueError('asr.decode_ctc_only.beam_size must be an integer in 0..32, got {!r}'.format(beam))
         return beam
 
+    @staticmethod
+    def rescore_args(asr_config):
+        """ASR.decode_two_pass's keywords from asr.decode_rescore, validated; None when the key is absent (or false)."""
+        import math
+        conf = asr_config.get('decode_rescore')
+        if conf is None or conf is False:
+            return None
+        if conf is True:
+            conf = {}
+        if not isinstance(conf, dict) or set(conf) - {'ctc_weight', 'length_bonus'}:
+            raise ValueError('asr.decode_rescore must be a mapping with the keys ctc_weight and length_bonus, '
+                             'got {!r}'.format(conf))
+        ctc_weight, bonus = conf.get('ctc_weight', 0.3), conf.get('length_bonus', 0.0)
+        if (isinstance(ctc_weight, bool) or not isinstance(ctc_weight, (int, float)) or not math.isfinite(ctc_weight)
+                or not 0 <= ctc_weight <= 1):
+            raise ValueError('asr.decode_rescore.ctc_weight must be a number in [0, 1], got {!r}'.format(ctc_weight))
+        if isinstance(bonus, bool) or not isinstance(bonus, (int, float)) or not math.isfinite(bonus):
+            raise ValueError('asr.decode_rescore.length_bonus must be a finite number, got {!r}'.format(bonus))
+        ctc_only = ASRTester.ctc_only_beam(asr_config)
+        if ctc_only is None or ctc_only < 1:
+            raise ValueError('asr.decode_rescore re-ranks the CTC prefix search\'s list: it needs '
+                             'asr.decode_ctc_only with beam_size >= 1, got {!r}'.format(asr_config.get('decode_ctc_only')))
+        return {'ctc_weight': ctc_weight, 'length_bonus': float(bonus)}
+
     def __init__(self, config, paras):
         super().__init__(config, paras, 'asr')
         self.decode_file = "_".join(
@@ -766,6 +796,7 @@ class ASRTester(Solver):
             raise ValueError('asr.decode_align needs a model with a ctc_head: set asr.mdl.ctc_weight '
                              '(ctc.JointCTCASR)')
         self.decode_ctc_only = self.ctc_only_beam(self.config['asr'])
+        self.decode_rescore = self.rescore_args(self.config['asr'])
         if self.decode_ctc_only is not None:
             if 'ctc_weight' not in self.config['asr']['mdl']:
                 raise ValueError('asr.decode_ctc_only needs a model with a ctc_head: set asr.mdl.ctc_weight '
@@ -802,6 +833,8 @@ class ASRTester(Solver):
             self.decode_file += '_ctc{:}'.format(self.decode_ctc_weight)
         if self.decode_ctc_only is not None:
             self.decode_file += '_ctconly{:}'.format(self.decode_ctc_only)
+        if self.decode_rescore is not None:
+            self.decode_file += '_rescore{:}'.format(self.decode_rescore['ctc_weight'])
         self.decode_term_args, suffix = self.decode_terms(self.config['asr'])
         self.decode_file += suffix
         if self.decode_align:
@@ -840,7 +873,11 @@ class ASRTester(Solver):
 
         def flush():
             if xs:
-                if ctc_only is not None:
+                if self.decode_rescore is not None:
+                    texts = [hyps[0][0] for hyps in
+                             self.asr_model.decode_two_pass(xs, x_lens, self.lm, self.mapper, lm_weight,
+                                                            beam_size=ctc_only, **self.decode_rescore)]
+                elif ctc_only is not None:
                     texts = [hyps[0][0] for hyps in
                              self.asr_model.decode_ctc(xs, x_lens, self.mapper, beam_size=ctc_only)]
                 else:

@@ -911,6 +911,43 @@ typedef struct ssasr_charlm {
 int ssasr_charlm_step(const ssasr_charlm* lm, const int32_t* x, const float* h1, const float* h2, int64_t B,
                       float* out, float* h1_out, float* h2_out, void* stream);
 
+/* ---- CTC decoding with an LM: CharLM shallow fusion inside the prefix search (added under ABI 16) ---------------
+ * BUILD-DEFINED.  ssasr_ctc_decode's prefix beam search (above: the same candidates, the same g_b' / g_n', the same
+ * identity of texts) with the CharLM in the RANKING, as Hannun et al. 2014, alg. 1 places a language model.  The LM
+ * score is a function of the TEXT alone, so g_b and g_n stay pure CTC masses and only the order changes.
+ *   L(w) of a text w = c_1 .. c_n: sum_i log_softmax(lm_out(<SOS> = 0, c_1 .. c_{i-1}))[c_i]: the CharLM is fed class 0
+ *   from zero states and then each character, as ssasr_decode_beam feeds it; the softmax runs over all V classes, blank
+ *   included; a row's log-softmax is formed in float (y - max - logf(sum expf(y - max))), L is accumulated in double.
+ *   Frame t: a candidate's key is logaddexp(g_b', g_n') + lm_weight L(w) + length_bonus |w| in double, the terms added
+ *   in that order; B_t is the min(K, number of finite candidates) candidates with the largest keys, ties as in
+ *   ssasr_ctc_decode (a kept text first, then the lower slot, then the lower character).  L(u.c) = L(u) +
+ *   lmrow(u)[c], lmrow(u) being the LM's log-softmax row after u, computed ONCE, when u enters a beam: only a frame's
+ *   winners that are new extensions take a CharLM step (at most K, run together, the weights streamed once per 8 of
+ *   them); a kept member keeps its state and its row.
+ *   After the last frame, with eos >= 0: final(w) = key(w) + lm_weight lmrow(w)[eos]; the members are ranked by
+ *   counting as ssasr_rescore ranks (non-increasing total as rounded to float, equal totals in slot order).  With
+ *   eos < 0 no end term is added and the order is the last frame's.
+ *   A term whose weight is exactly 0 is left out of every sum.  At lm_weight == 0 no LM step runs and lm is unread
+ *   (it may be NULL); at lm_weight == 0 && length_bonus == 0 the outputs are ssasr_ctc_decode's, bit for bit.
+ * Outputs in ssasr_ctc_decode's layout (chars [B][K][T], n_chars [B][K], n_hyps [B]) and three score rows [B][K]:
+ * scores the fused total, ctc_scores logaddexp(g_b, g_n), lm_scores L plus the end term.  Every element is written:
+ * slots from n_hyps on get length 0, scores and ctc_scores -inf, lm_scores 0.
+ * Accepted: B, T, V and blank as ssasr_ctc_decode takes them for K >= 1; 1 <= K <= 32 (the best path has no LM form);
+ * lm a HOST pointer to a block ssasr_charlm_step accepts (H % 4 == 0, H <= 4096, 16-byte aligned pointers) with
+ * lm->V == V, required when lm_weight != 0; finite lm_weight and length_bonus; eos < V; ws 16-byte aligned with
+ * ws_bytes >= ssasr_ctc_decode_lm_ws_bytes(B, T, V, K, H), H = lm->H when lm_weight != 0 and 0 otherwise (0: no kernel
+ * for the shape).  Argument errors return before any HIP call.
+ * One launch of 512 threads per utterance, no exchange between workgroups, no spins, no atomics; every loop is bounded
+ * by len, K, V, H or T.  LDS (32 KB, static) holds ssasr_ctc_decode's 20 KB, the K rows lmrow [K][64] and L; the
+ * workspace holds, per utterance, the GRU states of K slots and of the frame's up to K new members ([2][K][2H]
+ * floats), the embeddings, gate pre-activations and output rows of the 8 hypotheses in flight, the two beams' texts
+ * [2][K][T] int32 and, in its last B words, the number of frames that ran an LM step (tools/ctc_lm_time.py). */
+int64_t ssasr_ctc_decode_lm_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K, int64_t H);
+int ssasr_ctc_decode_lm(const float* logits, const int32_t* frame_lens, int64_t B, int64_t T, int64_t V, int64_t K,
+                        int blank, void* ws, int64_t ws_bytes, int32_t* chars, int32_t* n_chars, float* scores,
+                        int32_t* n_hyps, const ssasr_charlm* lm, float lm_weight, float length_bonus, int eos,
+                        float* ctc_scores, float* lm_scores, void* stream);
+
 /* The greedy decode loop of ASR.decode (src/asr.py:112-173, driven by ASRTester.exec, src/trainer.py:578-592)
  * for N encoded utterances as ONE launch: per utterance and step the attention (src/asr.py:383-390), both
  * Speller cells, char_trans and log_softmax (:149-153), one CharLM step fed with the previously emitted

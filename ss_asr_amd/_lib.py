@@ -146,6 +146,9 @@ SIGNATURES = {
     'ssasr_ctc_align': (I32, [P, P, P, I64, P, I64, I64, I64, I64, I32, P, I64, P, P, P, P, P, P]),
     'ssasr_ctc_decode_ws_bytes': (I64, [I64, I64, I64, I64]),
     'ssasr_ctc_decode': (I32, [P, P, I64, I64, I64, I64, I32, P, I64, P, P, P, P, P]),
+    'ssasr_ctc_decode_lm_ws_bytes': (I64, [I64, I64, I64, I64, I64]),
+    'ssasr_ctc_decode_lm': (I32, [P, P, I64, I64, I64, I64, I32, P, I64, P, P, P, P, C.POINTER(CharLM), F32, F32, I32,
+                                  P, P, P]),
     'ssasr_edit_score': (I32, [P, I64, P, P, I64, P, P, I64, I64, I64, I32, I32, P, P]),
     'ssasr_mbr_select': (I32, [P, I64, P, P, P, I64, I64, I64, I32, I32, I32, I32, F32, P, P, P, P]),
     'ssasr_mwer_ws_bytes': (I64, [I64, I64, I64]),

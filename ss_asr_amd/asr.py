@@ -699,14 +699,19 @@ class ASR(nn.Module):
             self._keep_hyps(*hyps, sampled=False)
         return self._texts(*hyps, mapper)
 
-    def decode_ctc(self, xs, x_lens, mapper, *, beam_size=8):
+    def decode_ctc(self, xs, x_lens, mapper, *, beam_size=8, rnn_lm=None, lm_weight=0.0, length_bonus=0.0):
         """BUILD-DEFINED: transcripts from the ctc_head's posteriors alone, for a list of single utterances in ONE
         launch with no Speller step (ssasr_ctc_decode, include/ssasr.h): per utterance the list of (text, score), best
         first.  beam_size 0: the best path (per frame the most probable class, repeats merged, blanks removed; score =
         the path's log-probability); 1 .. 32: CTC prefix beam search of that width, score = the log-probability that
         the search found for the text.  Each utterance is encoded alone, as in decode_nbest.  last_ctc_decode keeps
         (chars [N, Kr, T'], n_chars [N, Kr], scores [N, Kr], n_hyps [N], logits [N, T', V]) on the device, Kr =
-        max(beam_size, 1); last_hyps is set, so score(), mbr() and align() follow it as they follow decode_nbest."""
+        max(beam_size, 1); last_hyps is set, so score(), mbr() and align() follow it as they follow decode_nbest.
+        rnn_lm / lm_weight / length_bonus: CharLM shallow fusion INSIDE the prefix search (ssasr_ctc_decode_lm,
+        include/ssasr.h; beam_size >= 1): a text is ranked by its CTC score + lm_weight * log P_lm(text) + length_bonus
+        * len(text) at every frame, and by that + lm_weight * log P_lm(<EOS> | text) at the end.  The score returned
+        (and last_hyp_scores) is then the fused total, and last_ctc_decode gains two tensors [N, K] after the logits:
+        the CTC part and the LM part.  With both weights 0 (the default) the call is the one above exactly."""
         head = getattr(self, 'ctc_head', None)
         if head is None:
             raise ValueError(self._NO_CTC_HEAD % type(self).__name__)
@@ -714,13 +719,37 @@ class ASR(nn.Module):
             raise ValueError('beam_size must be an integer in 0..%d, got %r' % (ops.CTC_DECODE_MAX_BEAM, beam_size))
         if len(xs) != len(x_lens) or not len(xs):
             raise ValueError('decode_ctc: %d utterances, %d lengths' % (len(xs), len(x_lens)))
+        fused = self._ctc_lm_terms(rnn_lm, lm_weight, length_bonus, beam_size)
         with torch.no_grad():
             packed, enc_lens = self._encode_packed(xs, x_lens)
-            self.last_ctc_decode = ops.ctc_head_decode(packed, head.weight, head.bias, enc_lens, beam_size,
-                                                       ops.CTC_BLANK)
-            chars, n_chars, scores, n_hyps, _ = self.last_ctc_decode
+            if fused is None:
+                self.last_ctc_decode = ops.ctc_head_decode(packed, head.weight, head.bias, enc_lens, beam_size,
+                                                           ops.CTC_BLANK)
+            else:
+                out = ops.ctc_head_decode_lm(packed, head.weight, head.bias, enc_lens, beam_size, rnn_lm, *fused,
+                                             int(mapper.char_to_ind(EOS_TKN)), ops.CTC_BLANK)
+                self.last_ctc_decode = tuple(out[k] for k in ('chars', 'n_chars', 'scores', 'n_hyps', 'logits',
+                                                              'ctc_scores', 'lm_scores'))
+            chars, n_chars, scores, n_hyps = self.last_ctc_decode[:4]
             self._keep_hyps(chars, n_chars, n_hyps, scores, sampled=False)
         return self._texts(chars, n_chars, n_hyps, scores, mapper)
+
+    @staticmethod
+    def _ctc_lm_terms(rnn_lm, lm_weight, length_bonus, beam_size):
+        """decode_ctc's fusion keywords checked: None when both weights are 0 (the plain search), else (lm_weight,
+        length_bonus) as floats."""
+        terms = []
+        for name, value in (('lm_weight', lm_weight), ('length_bonus', length_bonus)):
+            if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value):
+                raise ValueError('decode_ctc: %s must be a finite number, got %r' % (name, value))
+            terms.append(float(value))
+        if terms == [0.0, 0.0]:
+            return None
+        if terms[0] != 0.0 and rnn_lm is None:
+            raise ValueError('decode_ctc: lm_weight %g needs rnn_lm' % terms[0])
+        if beam_size < 1:
+            raise ValueError('decode_ctc: beam_size 0, the best path, has no LM term or length bonus; use beam_size >= 1')
+        return tuple(terms)
 
     def rescore(self, mapper, *, rnn_lm=None, lm_weight=0.0, att_weight=1.0, first_weight=0.0, length_bonus=0.0):
         """BUILD-DEFINED: attention rescoring of the list that the last decode_nbest / decode_ctc / sample call left on
@@ -755,17 +784,28 @@ class ASR(nn.Module):
         self._keep_hyps(chars, n_chars, n_hyps, total, sampled=self.last_hyps_sampled)
         return self._texts(chars, n_chars, n_hyps, total, mapper)
 
-    def decode_two_pass(self, xs, x_lens, rnn_lm, mapper, lm_weight, *, beam_size=8, ctc_weight=0.3, length_bonus=0.0):
+    def decode_two_pass(self, xs, x_lens, rnn_lm, mapper, lm_weight, *, beam_size=8, ctc_weight=0.3, length_bonus=0.0,
+                        first_lm_weight=0.0):
         """BUILD-DEFINED: two-pass decoding on a model with a ctc_head: decode_ctc(beam_size >= 1), the CTC prefix beam
         search with no Speller step, then rescore() of its list with att_weight = 1 - ctc_weight, first_weight =
         ctc_weight and the CharLM at lm_weight -- decode_nbest's joint weighting applied to whole texts.  ctc_weight in
         [0, 1].  Returns per utterance the list of (text, total), best first; last_ctc_decode keeps the first pass,
-        last_rescore the second."""
+        last_rescore the second.  first_lm_weight > 0: the first pass searches with the CharLM at that weight
+        (decode_ctc's rnn_lm / lm_weight), so a text the LM favours is still in the list; rescore() then takes the
+        first pass's pure CTC part as its `first` score, and the final total counts the LM once."""
         if isinstance(ctc_weight, bool) or not isinstance(ctc_weight, (int, float)) or not 0.0 <= ctc_weight <= 1.0:
             raise ValueError('ctc_weight must be a number in [0, 1], got %r' % (ctc_weight,))
         if isinstance(beam_size, bool) or not isinstance(beam_size, int) or not 1 <= beam_size <= ops.CTC_DECODE_MAX_BEAM:
             raise ValueError('beam_size must be an integer in 1..%d, got %r' % (ops.CTC_DECODE_MAX_BEAM, beam_size))
-        self.decode_ctc(xs, x_lens, mapper, beam_size=beam_size)
+        if isinstance(first_lm_weight, bool) or not isinstance(first_lm_weight, (int, float)) or \
+                not (math.isfinite(first_lm_weight) and first_lm_weight >= 0.0):
+            raise ValueError('first_lm_weight must be a finite number >= 0, got %r' % (first_lm_weight,))
+        if first_lm_weight > 0.0 and rnn_lm is None:
+            raise ValueError('first_lm_weight %g needs rnn_lm' % first_lm_weight)
+        self.decode_ctc(xs, x_lens, mapper, beam_size=beam_size, rnn_lm=rnn_lm if first_lm_weight > 0.0 else None,
+                        lm_weight=float(first_lm_weight))
+        if first_lm_weight > 0.0:
+            self.last_hyp_scores = self.last_ctc_decode[5]      # the CTC part: the LM enters the total in rescore()
         return self.rescore(mapper, rnn_lm=rnn_lm, lm_weight=lm_weight, att_weight=1.0 - float(ctc_weight),
                             first_weight=float(ctc_weight), length_bonus=length_bonus)
 

@@ -1080,7 +1080,69 @@ def ctc_head_decode(feat, weight, bias, frame_lens, beam_size, blank=0):
     return ctc_decode(logits, frame_lens, beam_size, blank) + (logits,)
 
 
-EDIT_SCORE_MAX_HYP = 8191      # ssasr_edit_score's limits on a row's tokens, counted before dropping
+def ctc_decode_lm(logits, frame_lens, beam_size, lm, lm_weight=0.0, length_bonus=0.0, eos=1, blank=0):
+    """ssasr_ctc_decode_lm: ctc_decode's prefix beam search with the CharLM in the ranking, in one launch
+    (include/ssasr.h).  logits [B, T, V], frame_lens int32 [B] on the device; beam_size 1 .. 32; lm a charlm.CharLM
+    with input_size == V (None is allowed at lm_weight 0); eos < 0: no end term.  -> a dict: chars [B, K, T] int32,
+    n_chars [B, K] int32, scores / ctc_scores / lm_scores [B, K] float32 (the fused total, the CTC part, the LM part
+    with the end term), n_hyps [B] int32, lm_frames [B] int32 (frames that ran an LM step), best first.  At zero
+    weights the first four are ctc_decode's bits.  No autograd."""
+    lib = _lib.load()
+    blank, eos, lm_weight, length_bonus = int(blank), int(eos), float(lm_weight), float(length_bonus)
+    if isinstance(beam_size, bool) or not isinstance(beam_size, int) or not 1 <= beam_size <= CTC_DECODE_MAX_BEAM:
+        raise ValueError('ctc_decode_lm: beam_size must be an int in 1..%d (the best path has no LM form), got %r'
+                         % (CTC_DECODE_MAX_BEAM, beam_size))
+    if not (math.isfinite(lm_weight) and math.isfinite(length_bonus)):
+        raise ValueError('ctc_decode_lm: lm_weight and length_bonus must be finite, got %r, %r'
+                         % (lm_weight, length_bonus))
+    if lm is None and lm_weight != 0.0:
+        raise ValueError('ctc_decode_lm: lm_weight %g needs a language model' % lm_weight)
+    if logits.dim() != 3:
+        raise ValueError('ctc_decode_lm: logits must be [B, T, V], got %r' % (tuple(logits.shape),))
+    if frame_lens.dtype != torch.int32 or frame_lens.numel() != logits.shape[0]:
+        raise TypeError('ctc_decode_lm: frame_lens must be int32 [B]')
+    B, T, V = logits.shape
+    if not 0 <= blank < V:
+        raise ValueError('ctc_decode_lm: blank %d is no class of V=%d' % (blank, V))
+    if eos >= V:
+        raise ValueError('ctc_decode_lm: eos %d is no class of V=%d' % (eos, V))
+    if lm is not None and lm.input_size != V:
+        raise ValueError('ctc_decode_lm: the language model has %d classes, the logits %d' % (lm.input_size, V))
+    _need_gpu(logits, frame_lens)
+    logits = _f32c(logits.detach())
+    s, keep = _charlm_struct(lm) if lm is not None else (None, None)
+    H = lm.hidden_size if lm_weight != 0.0 else 0
+    need = int(lib.ssasr_ctc_decode_lm_ws_bytes(B, T, V, beam_size, H))
+    if need <= 0:
+        raise ValueError('ctc_decode_lm: shape B=%d T=%d V=%d beam_size=%d H=%d has no kernel' % (B, T, V, beam_size, H))
+    dev = logits.device
+    ws = torch.empty((need + 15) // 16 * 2, device=dev, dtype=torch.int64)
+    out = {'chars': torch.empty(B, beam_size, T, device=dev, dtype=torch.int32),
+           'n_chars': torch.empty(B, beam_size, device=dev, dtype=torch.int32),
+           'n_hyps': torch.empty(B, device=dev, dtype=torch.int32)}
+    for name in ('scores', 'ctc_scores', 'lm_scores'):
+        out[name] = torch.empty(B, beam_size, device=dev, dtype=torch.float32)
+    check(lib.ssasr_ctc_decode_lm(_p(logits), _p(frame_lens.contiguous()), B, T, V, beam_size, blank, _p(ws),
+                                  ws.numel() * 8, _p(out['chars']), _p(out['n_chars']), _p(out['scores']),
+                                  _p(out['n_hyps']), C.byref(s) if s is not None else None, lm_weight, length_bonus,
+                                  eos, _p(out['ctc_scores']), _p(out['lm_scores']), _stream()), 'ssasr_ctc_decode_lm')
+    out['lm_frames'] = ws.view(torch.int32)[need // 4 - B:need // 4]
+    return out
+
+
+def ctc_head_decode_lm(feat, weight, bias, frame_lens, beam_size, lm, lm_weight=0.0, length_bonus=0.0, eos=1, blank=0):
+    """ctc_decode_lm on the head's logits, the product issued as ctc_head_decode issues it.  -> ctc_decode_lm's dict
+    with the logits [B, T, V] they were decoded from under 'logits'.  No autograd."""
+    _need_gpu(feat, weight, bias)
+    feat, w, b = _f32c(feat.detach()), _f32c(weight.detach()), _f32c(bias.detach())
+    B, T, E = feat.shape
+    logits = gemm(feat.view(B * T, E), w, bias=b).view(B, T, w.shape[0])
+    out = ctc_decode_lm(logits, frame_lens, beam_size, lm, lm_weight, length_bonus, eos, blank)
+    out['logits'] = logits
+    return out
+
+
+EDIT_SCORE_MAX_HYP = 8191     # ssasr_edit_score's limits on a row's tokens, counted before dropping
 EDIT_SCORE_MAX_REF = 1023
 
 

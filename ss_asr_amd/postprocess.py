@@ -312,6 +312,139 @@ def ctc_prefix_beam_reference(lp, K, blank=0, dtype=np.float64, trace=None):
     return sorted(((w, float(lae(g[0], g[1]))) for w, g in beam.items()), key=lambda e: (-e[1], e[0])), gap
 
 
+CHARLM_FIELDS = ('emb', 'w_ih1', 'w_hh1', 'b_ih1', 'b_hh1', 'w_ih2', 'w_hh2', 'b_ih2', 'b_hh2', 'w_out', 'b_out')
+
+
+def ctc_prefix_beam_lm_reference(lp, K, lm, lm_weight=0.0, length_bonus=0.0, eos=-1, blank=0, dtype=np.float64,
+                                 trace=None, parts=None):
+    """BUILD-DEFINED: CTC prefix beam search with the CharLM in the ranking, ssasr_ctc_decode_lm (include/ssasr.h)
+    restated over Python tuples as texts -- what the kernel is defined and tested against.  lp, K, blank, dtype and
+    trace as ctc_prefix_beam_reference takes them (K >= 1); lm: the CharLM's eleven arrays in struct ssasr_charlm's
+    field order (CHARLM_FIELDS; a dict by those names or a sequence; None at lm_weight 0), evaluated here in `dtype`.
+      L(w) = sum_i log_softmax(lm_out(0, c_1 .. c_{i-1}))[c_i]: class 0 is fed from zero states, then each character;
+      two GRU cells (r, z, n) and the output layer; a row is y - max - log(sum exp(y - max)) over all V classes.
+      Frame t: the candidates and their g_b', g_n' are ctc_prefix_beam_reference's; a candidate's key is
+      logaddexp(g_b', g_n') + lm_weight L(w) + length_bonus len(w), a term whose weight is exactly 0 left out (the
+      weights are taken as float32 values); the K finite candidates with the largest keys are the next members.
+      L(u + (c,)) = L(u) + row(u)[c]: only members are ever fed to the LM.
+      After the last frame, with eos >= 0 and lm_weight != 0: total = key + lm_weight row(w)[eos].
+    -> ([(text, total)] best first, gap): gap is the smallest difference that any frame left between the lowest kept
+    and the highest dropped key, or that the final order left between adjacent totals (inf when neither occurred).
+    parts: a list that receives (CTC part, LM part with the end term) per returned entry."""
+    lp = np.asarray(lp, dtype=dtype)
+    K, blank, eos = int(K), int(blank), int(eos)
+    if lp.ndim != 2:
+        raise ValueError('ctc_prefix_beam_lm_reference: lp must be [T, V], got %r' % (lp.shape,))
+    if K < 1:
+        raise ValueError('ctc_prefix_beam_lm_reference: K must be >= 1, got %d' % K)
+    V = lp.shape[1]
+    if eos >= V:
+        raise ValueError('ctc_prefix_beam_lm_reference: eos %d is no class of V=%d' % (eos, V))
+    f64 = np.dtype(dtype) == np.float64
+    alpha, beta = float(np.float32(lm_weight)), float(np.float32(length_bonus))
+    if not (math.isfinite(alpha) and math.isfinite(beta)):
+        raise ValueError('ctc_prefix_beam_lm_reference: the weights must be finite')
+    use_lm = alpha != 0.0
+    if f64:                                                     # Python floats ARE float64, and ten times faster
+        rows, zero, neg = lp.tolist(), 0.0, -math.inf
+
+        def lae(a, b):
+            if a < b:
+                a, b = b, a
+            return a if b == -math.inf else a + math.log1p(math.exp(b - a))
+    else:
+        rows, zero, neg, lae = [list(row) for row in lp], dtype(0), dtype(-np.inf), np.logaddexp
+        alpha, beta = dtype(alpha), dtype(beta)
+    states, L = {}, {(): zero}
+    if use_lm:
+        if lm is None:
+            raise ValueError('ctc_prefix_beam_lm_reference: lm_weight %g needs a language model' % alpha)
+        arrs = [np.asarray(lm[n] if isinstance(lm, dict) else lm[i], dtype=dtype) for i, n in enumerate(CHARLM_FIELDS)]
+        emb, w_ih1, w_hh1, b_ih1, b_hh1, w_ih2, w_hh2, b_ih2, b_hh2, w_out, b_out = arrs
+        H = emb.shape[1]
+        if emb.shape[0] != V:
+            raise ValueError('ctc_prefix_beam_lm_reference: the language model has %d classes, lp %d' % (emb.shape[0], V))
+        one = dtype(1)
+
+        def gru(x, h, w_ih, w_hh, b_ih, b_hh):
+            gi, gh = w_ih @ x + b_ih, w_hh @ h + b_hh
+            r = one / (one + np.exp(-(gi[:H] + gh[:H])))
+            z = one / (one + np.exp(-(gi[H:2 * H] + gh[H:2 * H])))
+            n = np.tanh(gi[2 * H:] + r * gh[2 * H:])
+            return (one - z) * n + z * h
+
+        def lm_state(w):
+            """(h1, h2, the log-softmax row) after <SOS> and the characters of w"""
+            if w not in states:
+                if w:
+                    h1, h2, _ = lm_state(w[:-1])
+                    x = emb[w[-1]]
+                else:
+                    h1 = h2 = np.zeros(H, dtype=dtype)
+                    x = emb[0]
+                h1 = gru(x, h1, w_ih1, w_hh1, b_ih1, b_hh1)
+                h2 = gru(h1, h2, w_ih2, w_hh2, b_ih2, b_hh2)
+                y = w_out @ h2 + b_out
+                m = y.max()
+                row = y - m - np.log(np.exp(y - m).sum(dtype=dtype))
+                states[w] = (h1, h2, row.tolist() if f64 else row)
+            return states[w]
+
+    def lm_logp(w):
+        if w not in L:
+            L[w] = lm_logp(w[:-1]) + lm_state(w[:-1])[2][w[-1]]
+        return L[w]
+
+    def key_of(w, total):
+        if not total > neg:
+            return neg
+        if use_lm:
+            total = total + alpha * lm_logp(w)
+        if beta != 0:
+            total = total + beta * len(w)
+        return total
+
+    beam = {(): (zero, neg)}
+    gap = math.inf
+    classes = [c for c in range(V) if c != blank]
+    with np.errstate(all='ignore'):
+        for row in rows:
+            either = {u: lae(g[0], g[1]) for u, g in beam.items()}
+            new, key = {}, {}
+            for w in set(beam) | {u + (c,) for u in beam for c in classes}:
+                g_b = row[blank] + either[w] if w in beam else neg
+                g_n = neg
+                if w:
+                    p, c = w[:-1], w[-1]
+                    stay = beam[w][1] if w in beam else neg
+                    grow = neg
+                    if p in beam:
+                        grow = beam[p][0] if p and p[-1] == c else either[p]
+                    g_n = row[c] + lae(stay, grow)
+                new[w] = (g_b, g_n)
+                key[w] = key_of(w, lae(g_b, g_n))
+            ranked = sorted((w for w in new if key[w] > neg), key=lambda w: (-key[w], w))
+            if len(ranked) > K:
+                gap = min(gap, float(key[ranked[K - 1]] - key[ranked[K]]))
+            beam = {w: new[w] for w in ranked[:K]}
+            if trace is not None:
+                trace.append(frozenset(beam))
+        out = []
+        for w, g in beam.items():
+            ctc = lae(g[0], g[1])
+            total, l = key_of(w, ctc), lm_logp(w) if use_lm else zero
+            if use_lm and eos >= 0:
+                e = lm_state(w)[2][eos]
+                l, total = l + e, total + alpha * e
+            out.append((w, float(total), float(ctc), float(l)))
+    out.sort(key=lambda e: (-e[1], e[0]))
+    for a, b in zip(out, out[1:]):
+        gap = min(gap, a[1] - b[1])
+    if parts is not None:
+        parts.extend((e[2], e[3]) for e in out)
+    return [(e[0], e[1]) for e in out], gap
+
+
 class ErrorStats:
     """Corpus-level error rates: sums (S, D, I, N) rows of characters and of words; cer / wer =
     sum(S + D + I) / sum(N), nan when N == 0.  (calc_err below stays the reference's mean of per-utterance ratios.)"""

@@ -675,7 +675,11 @@ class ASRTester(Solver):
     asr.decode_ctc_only: {beam_size: 8} (absent: off; beam_size an integer in 0..32, 0 the best path; needs
     'ctc_weight' in asr.mdl, else set_model raises): every group is transcribed from the ctc_head's posteriors alone,
     with no Speller step (ASR.decode_ctc, ssasr_ctc_decode); asr.decode_beam_size, the language model and
-    max_decode_step_ratio then play no part, and `decode_file` gains `_ctconly<beam_size>`.  It composes with
+    max_decode_step_ratio then play no part, and `decode_file` gains `_ctconly<beam_size>`.  The optional keys
+    lm_weight and length_bonus (finite numbers, absent: 0; beam_size >= 1) put the tester's language model INSIDE the
+    prefix search (ssasr_ctc_decode_lm: a text is ranked by its CTC score + lm_weight log P_lm + length_bonus *
+    length); `decode_file` then gains `_clm<lm_weight>` (and `_clb<length_bonus>`) when lm_weight != 0, and with
+    asr.decode_rescore lm_weight (>= 0) is decode_two_pass's first_lm_weight.  It composes with
     decode_score, decode_mbr (which then needs THIS beam_size >= 2) and decode_align; together with a positive
     asr.decode_ctc_weight or any of the beam search's terms it is an error.
     asr.decode_rescore: {ctc_weight: 0.3, length_bonus: 0.0} (absent: off; ctc_weight a number in [0, 1], length_bonus
@@ -747,12 +751,35 @@ class ASRTester(Solver):
             return None
         if conf is True:
             conf = {}
-        if not isinstance(conf, dict) or set(conf) - {'beam_size'}:
-            raise ValueError('asr.decode_ctc_only must be a mapping with the key beam_size, got {!r}'.format(conf))
+        if not isinstance(conf, dict) or set(conf) - {'beam_size', 'lm_weight', 'length_bonus'}:
+            raise ValueError('asr.decode_ctc_only must be a mapping with the key beam_size (and, optionally, lm_weight '
+                             'and length_bonus), got {!r}'.format(conf))
         beam = conf.get('beam_size', 8)
         if isinstance(beam, bool) or not isinstance(beam, int) or not 0 <= beam <= 32:
             raise ValueError('asr.decode_ctc_only.beam_size must be an integer in 0..32, got {!r}'.format(beam))
         return beam
+
+    @staticmethod
+    def ctc_only_lm(asr_config):
+        """ASR.decode_ctc's lm_weight and length_bonus from asr.decode_ctc_only, validated: {'lm_weight': 0.0,
+        'length_bonus': 0.0} when the keys (or the whole mapping) are absent."""
+        import math
+        beam = ASRTester.ctc_only_beam(asr_config)
+        conf = asr_config.get('decode_ctc_only')
+        conf = conf if isinstance(conf, dict) else {}
+        out = {}
+        for key in ('lm_weight', 'length_bonus'):
+            v = conf.get(key, 0.0)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError('asr.decode_ctc_only.{} must be a finite number, got {!r}'.format(key, v))
+            out[key] = float(v)
+        if beam == 0 and any(out.values()):
+            raise ValueError('asr.decode_ctc_only: beam_size 0, the best path, has no LM term or length bonus; '
+                             'got {!r}'.format(conf))
+        if asr_config.get('decode_rescore') not in (None, False) and (out['lm_weight'] < 0 or out['length_bonus'] != 0):
+            raise ValueError('asr.decode_ctc_only with asr.decode_rescore: the first pass takes lm_weight >= 0 and no '
+                             'length_bonus (asr.decode_rescore.length_bonus is the second pass\'s), got {!r}'.format(conf))
+        return out
 
     @staticmethod
     def rescore_args(asr_config):
@@ -797,6 +824,7 @@ class ASRTester(Solver):
                              '(ctc.JointCTCASR)')
         self.decode_ctc_only = self.ctc_only_beam(self.config['asr'])
         self.decode_rescore = self.rescore_args(self.config['asr'])
+        self.decode_ctc_lm = self.ctc_only_lm(self.config['asr'])
         if self.decode_ctc_only is not None:
             if 'ctc_weight' not in self.config['asr']['mdl']:
                 raise ValueError('asr.decode_ctc_only needs a model with a ctc_head: set asr.mdl.ctc_weight '
@@ -833,6 +861,10 @@ class ASRTester(Solver):
             self.decode_file += '_ctc{:}'.format(self.decode_ctc_weight)
         if self.decode_ctc_only is not None:
             self.decode_file += '_ctconly{:}'.format(self.decode_ctc_only)
+            if self.decode_ctc_lm['lm_weight'] != 0:
+                self.decode_file += '_clm{:}'.format(self.decode_ctc_lm['lm_weight'])
+                if self.decode_ctc_lm['length_bonus'] != 0:
+                    self.decode_file += '_clb{:}'.format(self.decode_ctc_lm['length_bonus'])
         if self.decode_rescore is not None:
             self.decode_file += '_rescore{:}'.format(self.decode_rescore['ctc_weight'])
         self.decode_term_args, suffix = self.decode_terms(self.config['asr'])
@@ -876,10 +908,12 @@ class ASRTester(Solver):
                 if self.decode_rescore is not None:
                     texts = [hyps[0][0] for hyps in
                              self.asr_model.decode_two_pass(xs, x_lens, self.lm, self.mapper, lm_weight,
-                                                            beam_size=ctc_only, **self.decode_rescore)]
+                                                            beam_size=ctc_only, **self.decode_rescore,
+                                                            first_lm_weight=self.decode_ctc_lm['lm_weight'])]
                 elif ctc_only is not None:
                     texts = [hyps[0][0] for hyps in
-                             self.asr_model.decode_ctc(xs, x_lens, self.mapper, beam_size=ctc_only)]
+                             self.asr_model.decode_ctc(xs, x_lens, self.mapper, beam_size=ctc_only, rnn_lm=self.lm,
+                                                       **self.decode_ctc_lm)]
                 else:
                     texts = self.asr_model.decode_many(xs, x_lens, self.lm, self.mapper, lm_weight,
                                                        beam_size=beam, ctc_weight=ctc_weight, **terms)

@@ -948,6 +948,54 @@ int ssasr_ctc_decode_lm(const float* logits, const int32_t* frame_lens, int64_t 
                         int32_t* n_hyps, const ssasr_charlm* lm, float lm_weight, float length_bonus, int eos,
                         float* ctc_scores, float* lm_scores, void* stream);
 
+/* ---- CTC decoding with a character graph: n-gram LM and hotword biasing inside the prefix search (under ABI 16) ----
+ * BUILD-DEFINED.  A character graph over V classes is a complete deterministic weighted automaton: S states, a start
+ * state, next [S][V] int32 (the state after class c), arc [S][V] float (finite, or -inf: the extension is FORBIDDEN)
+ * and fin [S] float (finite).  For a text w = c_1 .. c_n: s_0 = start, s_i = next[s_{i-1}][c_i],
+ *   G(w) = sum_i arc[s_{i-1}][c_i],   state(w) = s_n.
+ * A count-based n-gram LM (states: the seen histories, arcs: log P(c | history), fully backed off), a hotword list
+ * (its Aho-Corasick automaton) and their product are such graphs; ss_asr_amd/char_graph.py builds them.  The blank's
+ * column is never read.
+ * The search is ssasr_ctc_decode's for K >= 1 (the same candidates, the same g_b' / g_n', the same identity of
+ * texts) with G in the RANKING, as ssasr_ctc_decode_lm places the CharLM: G is a function of the text alone, so g_b and
+ * g_n stay pure CTC masses.
+ *   Frame t: a candidate's key is logaddexp(g_b', g_n') + graph_weight G(w) + length_bonus |w| in double, the terms
+ *   added in that order; a candidate whose key is -inf (no CTC mass, or a forbidden arc) is no candidate; B_t is the
+ *   min(K, number of finite candidates) candidates with the largest keys, ties as in ssasr_ctc_decode.  A kept text has
+ *   a finite key, and the kept texts' blank extensions are always finite, so a beam never empties.
+ *   G(u.c) = G(u) + arc[state(u)][c] in double, state(u.c) = next[state(u)][c], both taken when u.c enters a beam.
+ *   After the last frame: total(w) = key(w) + graph_weight fin[state(w)]; the members are ranked by counting as
+ *   ssasr_rescore ranks (non-increasing total as rounded to float, equal totals in slot order).
+ *   A term whose weight is exactly 0 is left out of every sum.  At graph_weight == 0 the tables are unread (graph may
+ *   be NULL); at graph_weight == 0 && length_bonus == 0 the outputs are ssasr_ctc_decode's, bit for bit.
+ * Outputs in ssasr_ctc_decode's layout (chars [B][K][T], n_chars [B][K], n_hyps [B]) and three score rows [B][K]:
+ * scores the fused total, ctc_scores logaddexp(g_b, g_n), graph_scores G + fin.  Every element is written: slots from
+ * n_hyps on get length 0, scores and ctc_scores -inf, graph_scores 0.
+ * Accepted: B, T, V and blank as ssasr_ctc_decode takes them for K >= 1; 1 <= K <= 32; graph a HOST pointer to a
+ * struct of DEVICE tables with graph->V == V, 1 <= S <= 1,048,576 and 0 <= start < S, required when graph_weight != 0;
+ * finite graph_weight >= 0 (a negative weight would turn a forbidden arc into +inf) and finite length_bonus; ws
+ * 8-byte aligned with ws_bytes >= ssasr_ctc_decode_graph_ws_bytes(B, T, V, K) (0: no kernel for the shape).  Argument
+ * errors return before any HIP call.  The tables' CONTENTS cannot be checked here: the kernel clamps every state it
+ * reads to [0, S - 1], so a malformed table gives wrong scores and never a read outside the tables (char_graph.CharGraph
+ * validates them before the upload).
+ * One launch of 256 threads per utterance, no exchange between workgroups, no spins, no atomics; every loop is bounded
+ * by len, K, V or T; an utterance's results depend on its own frames alone.  LDS (40 KB, static) holds
+ * ssasr_ctc_decode's 20 KB, per member its state (int32) and G (double), and per member the two table rows of its
+ * state, next and arc [K][64] each, addressed through a slot that a kept member keeps: the tables are read from memory
+ * only for the members that newly enter a beam (at most K rows a frame), and the frame's candidates read LDS alone.
+ * The workspace holds the two beams' texts [B][2][K][T] int32. */
+typedef struct ssasr_char_graph {
+  const int32_t* next;
+  const float* arc;
+  const float* fin;
+  int32_t S, V, start;
+} ssasr_char_graph;
+int64_t ssasr_ctc_decode_graph_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K);
+int ssasr_ctc_decode_graph(const float* logits, const int32_t* frame_lens, int64_t B, int64_t T, int64_t V, int64_t K,
+                           int blank, void* ws, int64_t ws_bytes, int32_t* chars, int32_t* n_chars, float* scores,
+                           int32_t* n_hyps, const ssasr_char_graph* graph, float graph_weight, float length_bonus,
+                           float* ctc_scores, float* graph_scores, void* stream);
+
 /* The greedy decode loop of ASR.decode (src/asr.py:112-173, driven by ASRTester.exec, src/trainer.py:578-592)
  * for N encoded utterances as ONE launch: per utterance and step the attention (src/asr.py:383-390), both
  * Speller cells, char_trans and log_softmax (:149-153), one CharLM step fed with the previously emitted

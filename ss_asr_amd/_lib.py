@@ -49,6 +49,11 @@ class CharLM(C.Structure):
         'emb', 'w_ih1', 'w_hh1', 'b_ih1', 'b_hh1', 'w_ih2', 'w_hh2', 'b_ih2', 'b_hh2', 'w_out', 'b_out')]
 
 
+class CharGraph(C.Structure):
+    """struct ssasr_char_graph (include/ssasr.h)."""
+    _fields_ = [('next', P), ('arc', P), ('fin', P), ('S', C.c_int32), ('V', C.c_int32), ('start', C.c_int32)]
+
+
 # what struct ssasr_infer and struct ssasr_beam share, around the beam's K and between each one's own tail
 _DECODE_DIMS = ('N', 'T', 'E', 'A', 'D', 'V', 'max_steps')
 _DECODE_COMMON = ([(n, P) for n in ('feat', 'enc_len', 'comp', 'w_psi', 'b_psi', 'w_phi',
@@ -149,6 +154,9 @@ SIGNATURES = {
     'ssasr_ctc_decode_lm_ws_bytes': (I64, [I64, I64, I64, I64, I64]),
     'ssasr_ctc_decode_lm': (I32, [P, P, I64, I64, I64, I64, I32, P, I64, P, P, P, P, C.POINTER(CharLM), F32, F32, I32,
                                   P, P, P]),
+    'ssasr_ctc_decode_graph_ws_bytes': (I64, [I64, I64, I64, I64]),
+    'ssasr_ctc_decode_graph': (I32, [P, P, I64, I64, I64, I64, I32, P, I64, P, P, P, P, C.POINTER(CharGraph), F32, F32,
+                                     P, P, P]),
     'ssasr_edit_score': (I32, [P, I64, P, P, I64, P, P, I64, I64, I64, I32, I32, P, P]),
     'ssasr_mbr_select': (I32, [P, I64, P, P, P, I64, I64, I64, I32, I32, I32, I32, F32, P, P, P, P]),
     'ssasr_mwer_ws_bytes': (I64, [I64, I64, I64]),

@@ -699,7 +699,8 @@ class ASR(nn.Module):
             self._keep_hyps(*hyps, sampled=False)
         return self._texts(*hyps, mapper)
 
-    def decode_ctc(self, xs, x_lens, mapper, *, beam_size=8, rnn_lm=None, lm_weight=0.0, length_bonus=0.0):
+    def decode_ctc(self, xs, x_lens, mapper, *, beam_size=8, rnn_lm=None, lm_weight=0.0, length_bonus=0.0, graph=None,
+                   graph_weight=0.0):
         """BUILD-DEFINED: transcripts from the ctc_head's posteriors alone, for a list of single utterances in ONE
         launch with no Speller step (ssasr_ctc_decode, include/ssasr.h): per utterance the list of (text, score), best
         first.  beam_size 0: the best path (per frame the most probable class, repeats merged, blanks removed; score =
@@ -711,7 +712,13 @@ class ASR(nn.Module):
         include/ssasr.h; beam_size >= 1): a text is ranked by its CTC score + lm_weight * log P_lm(text) + length_bonus
         * len(text) at every frame, and by that + lm_weight * log P_lm(<EOS> | text) at the end.  The score returned
         (and last_hyp_scores) is then the fused total, and last_ctc_decode gains two tensors [N, K] after the logits:
-        the CTC part and the LM part.  With both weights 0 (the default) the call is the one above exactly."""
+        the CTC part and the LM part.  With both weights 0 (the default) the call is the one above exactly.
+        graph / graph_weight: a char_graph.CharGraph (an n-gram LM, hotwords, their product) INSIDE the prefix search
+        (ssasr_ctc_decode_graph, include/ssasr.h; beam_size >= 1, graph_weight finite and >= 0): a text is ranked by its
+        CTC score + graph_weight * G(text) + length_bonus * len(text) at every frame, and by that + graph_weight *
+        fin[state(text)] at the end; last_ctc_decode gains the CTC part and the graph part (G + fin) after the logits.
+        At graph_weight 0 the graph plays no part.  Together with rnn_lm at a non-zero lm_weight it is a ValueError:
+        the two terms in one search are not built."""
         head = getattr(self, 'ctc_head', None)
         if head is None:
             raise ValueError(self._NO_CTC_HEAD % type(self).__name__)
@@ -720,9 +727,18 @@ class ASR(nn.Module):
         if len(xs) != len(x_lens) or not len(xs):
             raise ValueError('decode_ctc: %d utterances, %d lengths' % (len(xs), len(x_lens)))
         fused = self._ctc_lm_terms(rnn_lm, lm_weight, length_bonus, beam_size)
+        graph_weight = self._ctc_graph_weight(graph, graph_weight, fused, beam_size)
+        if graph_weight != 0.0 and graph.n_classes != head.weight.shape[0]:
+            raise ValueError('decode_ctc: the graph has %d classes, the ctc_head %d'
+                             % (graph.n_classes, head.weight.shape[0]))
         with torch.no_grad():
             packed, enc_lens = self._encode_packed(xs, x_lens)
-            if fused is None:
+            if graph_weight != 0.0:
+                out = ops.ctc_head_decode_graph(packed, head.weight, head.bias, enc_lens, beam_size, graph, graph_weight,
+                                                float(length_bonus), ops.CTC_BLANK)
+                self.last_ctc_decode = tuple(out[k] for k in ('chars', 'n_chars', 'scores', 'n_hyps', 'logits',
+                                                              'ctc_scores', 'graph_scores'))
+            elif fused is None:
                 self.last_ctc_decode = ops.ctc_head_decode(packed, head.weight, head.bias, enc_lens, beam_size,
                                                            ops.CTC_BLANK)
             else:
@@ -750,6 +766,27 @@ class ASR(nn.Module):
         if beam_size < 1:
             raise ValueError('decode_ctc: beam_size 0, the best path, has no LM term or length bonus; use beam_size >= 1')
         return tuple(terms)
+
+    @staticmethod
+    def _ctc_graph_weight(graph, graph_weight, fused, beam_size):
+        """decode_ctc's graph keywords checked against the rest (fused: _ctc_lm_terms' result): the weight as a
+        float, 0.0 when no graph term runs."""
+        from .char_graph import CharGraph
+        if isinstance(graph_weight, bool) or not isinstance(graph_weight, (int, float)) or \
+                not (math.isfinite(graph_weight) and graph_weight >= 0.0):
+            raise ValueError('decode_ctc: graph_weight must be a finite number >= 0, got %r' % (graph_weight,))
+        if graph is not None and not isinstance(graph, CharGraph):
+            raise ValueError('decode_ctc: graph must be a char_graph.CharGraph, got %s' % type(graph).__name__)
+        if graph_weight == 0.0:
+            return 0.0
+        if graph is None:
+            raise ValueError('decode_ctc: graph_weight %g needs graph' % graph_weight)
+        if beam_size < 1:
+            raise ValueError('decode_ctc: beam_size 0, the best path, has no graph term; use beam_size >= 1')
+        if fused is not None and fused[0] != 0.0:
+            raise ValueError('decode_ctc: a graph and rnn_lm at lm_weight %g in one search are not built; give one of them'
+                             % fused[0])
+        return float(graph_weight)
 
     def rescore(self, mapper, *, rnn_lm=None, lm_weight=0.0, att_weight=1.0, first_weight=0.0, length_bonus=0.0):
         """BUILD-DEFINED: attention rescoring of the list that the last decode_nbest / decode_ctc / sample call left on

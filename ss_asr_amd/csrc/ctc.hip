@@ -18,6 +18,8 @@
 #include "../../include/ssasr.h"
 #include "common.h"
 
+#include <cmath>
+
 namespace {
 
 // One lattice state (and one class) per thread -- the step is a latency chain, so states are spread
@@ -715,6 +717,280 @@ int decode_check_shape(int64_t B, int64_t T, int64_t V, int64_t K) {
   return SSASR_OK;
 }
 
+
+// ---- the prefix beam search with a character graph in the ranking (include/ssasr.h, ssasr_ctc_decode_graph) --------
+// ctc_prefix_beam_kernel restated, as infer.hip restates it for the CharLM: the same frame body, and beside g_b / g_n
+// every member carries the graph's state after its text (int32) and G, the sum of the arcs taken (double).  The rows
+// next[state][.] and arc[state][.] of a member sit in LDS, [slot][64], from the frame after the member entered a beam
+// until it leaves: a kept member keeps its slot, so the candidate loop and the winners' update read LDS alone.  The
+// only global reads of the tables are the rows of a frame's new members: issued once the winners are known, a wave per
+// member, and stored to LDS as they arrive; the next frame's two barriers lie before their first reader.  (Holding
+// them in registers over the frame boundary and storing after the next frame's parent look-up measured no faster:
+// DESIGN.md 4.22.)  Every state read from the table is clamped to [0, S - 1]: a malformed table gives wrong scores, no
+// stray read.
+
+struct GraphArgs {
+  DecodeArgs d;
+  const int32_t* next;       // [S][V]
+  const float* arc;          // [S][V]
+  const float* fin;          // [S]
+  int S, start;
+  float graph_weight, length_bonus;
+  float *ctc_scores, *graph_scores;   // [B][K]
+};
+
+__global__ __launch_bounds__(DEC_NT) void ctc_prefix_beam_graph_kernel(GraphArgs g) {
+  __shared__ double gb[2][DEC_MAX_K], gn[2][DEC_MAX_K];      // the two beams' members
+  __shared__ double G[2][DEC_MAX_K];                         // the graph's score of the member's text
+  __shared__ unsigned long long hs[2][DEC_MAX_K], hp[2][DEC_MAX_K];   // hash of the text, of the text's parent
+  __shared__ int tlen[2][DEC_MAX_K], tlast[2][DEC_MAX_K];    // length, last character (-1: the empty text)
+  __shared__ int gst[2][DEC_MAX_K], slot[2][DEC_MAX_K];      // the graph's state after the text; the member's row slot
+  __shared__ int par[DEC_MAX_K];                             // the member that is this member's parent, -1: none
+  __shared__ signed char child[DEC_MAX_K * DEC_MAX_V];       // [u][c]: the member that is u.c, -1: none
+  __shared__ double lpd[DEC_MAX_V];                          // the frame's log-softmax
+  __shared__ double sgb[DEC_MAX_K], sgn[DEC_MAX_K];          // g_b', g_n' of the kept texts
+  __shared__ double tot[DEC_MAX_K + DEC_MAX_K * DEC_MAX_V];  // the candidates' keys: [K] kept, then [K][V] extensions
+  __shared__ double wv[2][DEC_WAVES];
+  __shared__ int wi[2][DEC_WAVES], win[DEC_MAX_K];
+  __shared__ float arow[DEC_MAX_K][64];                      // [slot]: arc[state][.]
+  __shared__ int nrow[DEC_MAX_K][64];                        // [slot]: next[state][.]
+  __shared__ int ext[DEC_MAX_K];                             // the frame's winners that are new extensions
+  __shared__ int n_ext_sh;
+  __shared__ float fkey[DEC_MAX_K], ftot[DEC_MAX_K], fctc[DEC_MAX_K], fgr[DEC_MAX_K];
+  __shared__ int fsrc[DEC_MAX_K];
+  const DecodeArgs& a = g.d;
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int len = max(min(a.frame_lens[b], a.T), 0), V = a.V, K = a.K, T = a.T, blank = a.blank;
+  const bool use_g = g.graph_weight != 0.f, use_len = g.length_bonus != 0.f;
+  const double gw = (double)g.graph_weight, beta = (double)g.length_bonus;
+  const int s_max = g.S - 1;
+  const float* logits = a.logits + (int64_t)b * T * V;
+  int32_t* text = a.text + (int64_t)b * 2 * K * T;
+  const int ncand = K + K * V;
+  int n = 1, cur = 0;
+  if (tid == 0) {
+    gb[0][0] = 0.0; gn[0][0] = NEG_INF; G[0][0] = 0.0;
+    hs[0][0] = 0; hp[0][0] = 0;
+    tlen[0][0] = 0; tlast[0][0] = -1;
+    gst[0][0] = use_g ? g.start : 0; slot[0][0] = 0;
+  }
+  if (use_g && wave == 0) {                                  // the empty text's rows: the start state's
+    const int64_t row = (int64_t)g.start * V;
+    arow[0][lane] = lane < V ? g.arc[row + lane] : 0.f;
+    nrow[0][lane] = lane < V ? g.next[row + lane] : 0;
+  }
+  float x_next = (wave == 0 && lane < V && len > 0) ? logits[lane] : -INFINITY;
+  __syncthreads();
+  for (int t = 0; t < len; ++t) {
+    const int32_t* told = text + (int64_t)cur * K * T;
+    int32_t* tnew = text + (int64_t)(cur ^ 1) * K * T;
+    for (int i = tid; i < K * V; i += DEC_NT) child[i] = -1;
+    if (wave == 0) {                                         // the row's log-softmax (ctc_table's normaliser)
+      const float x = x_next;
+      if (t + 1 < len && lane < V) x_next = logits[(int64_t)(t + 1) * V + lane];
+      const float m = wave_max(x);
+      const float s = wave_sum(lane < V ? expf(x - m) : 0.f);
+      const double lse = (double)m + (double)logf(s);
+      if (lane < V) lpd[lane] = (double)x - lse;
+    }
+    __syncthreads();
+    // each member's parent among the members: a lane per possible parent filters, the wave compares the characters
+    for (int w = wave; w < n; w += DEC_WAVES) {
+      const int lw = tlen[cur][w];
+      int found = -1;
+      if (lw >= 1) {
+        unsigned long long mask = __ballot(lane < n && tlen[cur][lane < n ? lane : 0] == lw - 1 &&
+                                           hs[cur][lane < n ? lane : 0] == hp[cur][w]);
+        while (mask != 0 && found < 0) {                     // at most n turns
+          const int u = __ffsll((long long)mask) - 1;
+          mask &= mask - 1;
+          int differ = 0;
+          for (int i = lane; i < lw - 1; i += 64) differ |= told[(int64_t)w * T + i] != told[(int64_t)u * T + i];
+          if (!__any(differ)) found = u;
+        }
+        if (lane == 0 && found >= 0) child[found * V + tlast[cur][w]] = (signed char)w;
+      }
+      if (lane == 0) par[w] = found;
+    }
+    __syncthreads();
+    // the candidates' keys: the CTC total, + graph_weight G(w) + length_bonus |w|; each thread remembers its best
+    const double lpb = lpd[blank];
+    double best = NEG_INF;
+    int bidx = INT32_MAX;
+    for (int idx = tid; idx < ncand; idx += DEC_NT) {
+      double v = NEG_INF;
+      if (idx < K) {
+        const int w = idx;
+        if (w < n) {
+          const double nb = lpb + dec_lae(gb[cur][w], gn[cur][w]);
+          double nn = NEG_INF;
+          const int c = tlast[cur][w];
+          if (c >= 0) {
+            const int p = par[w];
+            double via = NEG_INF;
+            if (p >= 0) via = tlast[cur][p] == c ? gb[cur][p] : dec_lae(gb[cur][p], gn[cur][p]);
+            nn = lpd[c] + dec_lae(gn[cur][w], via);
+          }
+          sgb[w] = nb;
+          sgn[w] = nn;
+          v = dec_lae(nb, nn);
+          if (v > NEG_INF) {
+            if (use_g) v += gw * G[cur][w];
+            if (use_len) v += beta * (double)tlen[cur][w];
+          }
+        }
+      } else {
+        const int u = (idx - K) / V, c = (idx - K) % V;
+        if (u < n && c != blank && child[u * V + c] < 0) {
+          v = lpd[c] + (tlast[cur][u] == c ? gb[cur][u] : dec_lae(gb[cur][u], gn[cur][u]));
+          if (v > NEG_INF) {                                 // a forbidden arc (-inf) leaves no candidate
+            if (use_g) v += gw * (G[cur][u] + (double)arow[slot[cur][u]][c]);
+            if (use_len) v += beta * (double)(tlen[cur][u] + 1);
+          }
+        }
+      }
+      tot[idx] = v;
+      if (v > best) { best = v; bidx = idx; }
+    }
+    // B_t: K rounds of a block-wide argmax (the lowest index among equals), the winner leaving the pool
+    int n_new = 0;
+    for (int r = 0; r < K; ++r) {
+      double m = best;
+      int mi = bidx;
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+        const double om = __shfl_xor(m, off);
+        const int oi = __shfl_xor(mi, off);
+        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+      }
+      if (lane == 0) { wv[r & 1][wave] = m; wi[r & 1][wave] = mi; }
+      __syncthreads();
+      double gm = wv[r & 1][0];
+      int gi = wi[r & 1][0];
+#pragma unroll
+      for (int w = 1; w < DEC_WAVES; ++w) {
+        const double om = wv[r & 1][w];
+        const int oi = wi[r & 1][w];
+        if (om > gm || (om == gm && oi < gi)) { gm = om; gi = oi; }
+      }
+      if (!(gm > NEG_INF)) break;                            // fewer finite candidates than K
+      if (tid == 0) win[r] = gi;
+      n_new = r + 1;
+      if (gi % DEC_NT == tid) {
+        tot[gi] = NEG_INF;
+        best = NEG_INF;
+        bidx = INT32_MAX;
+        for (int idx = tid; idx < ncand; idx += DEC_NT) {
+          const double v = tot[idx];
+          if (v > best) { best = v; bidx = idx; }
+        }
+      }
+    }
+    __syncthreads();
+    // the winners become B_t: scalars, then texts.  A new extension's g_n' is its CTC total, formed again as above
+    // (the key is no longer that total); its state and G come from its parent's rows.
+    const int nxt = cur ^ 1;
+    if (tid < n_new) {
+      const int w = win[tid];
+      if (w < K) {
+        gb[nxt][tid] = sgb[w]; gn[nxt][tid] = sgn[w]; G[nxt][tid] = G[cur][w];
+        hs[nxt][tid] = hs[cur][w]; hp[nxt][tid] = hp[cur][w];
+        tlen[nxt][tid] = tlen[cur][w]; tlast[nxt][tid] = tlast[cur][w];
+        gst[nxt][tid] = gst[cur][w]; slot[nxt][tid] = slot[cur][w];
+      } else {
+        const int u = (w - K) / V, c = (w - K) % V;
+        gb[nxt][tid] = NEG_INF;
+        gn[nxt][tid] = lpd[c] + (tlast[cur][u] == c ? gb[cur][u] : dec_lae(gb[cur][u], gn[cur][u]));
+        G[nxt][tid] = use_g ? G[cur][u] + (double)arow[slot[cur][u]][c] : 0.0;
+        gst[nxt][tid] = use_g ? min(max(nrow[slot[cur][u]][c], 0), s_max) : 0;
+        hs[nxt][tid] = hs[cur][u] * DEC_HASH_MUL + (unsigned long long)(c + 1); hp[nxt][tid] = hs[cur][u];
+        tlen[nxt][tid] = tlen[cur][u] + 1; tlast[nxt][tid] = c;
+      }
+    }
+    if (tid == 0) {                                          // slots: the kept members' stay taken, the rest is free
+      unsigned used = 0;
+      for (int j = 0; j < n_new; ++j)
+        if (win[j] < K) used |= 1u << slot[cur][win[j]];
+      int ne = 0;
+      for (int j = 0; j < n_new; ++j)
+        if (win[j] >= K) {
+          const int s = __ffs((int)~used) - 1;               // K members at most: a bit below K is clear
+          used |= 1u << s;
+          slot[nxt][j] = s;
+          ext[ne++] = j;
+        }
+      n_ext_sh = ne;
+    }
+    for (int j = 0; j < n_new; ++j) {
+      const int w = win[j];
+      const int src = w < K ? w : (w - K) / V;
+      const int l = tlen[cur][src];                          // l <= t < T: the appended character stays in the row
+      for (int i = tid; i < l; i += DEC_NT) tnew[(int64_t)j * T + i] = told[(int64_t)src * T + i];
+      if (w >= K && tid == 0) tnew[(int64_t)j * T + l] = (w - K) % V;
+    }
+    __syncthreads();
+    // the new members' rows: a wave per member; two barriers of the next frame lie before their first reader
+    const int ne = use_g ? n_ext_sh : 0;
+    for (int e = wave; e < ne; e += DEC_WAVES) {
+      const int j = ext[e];
+      const int64_t row = (int64_t)gst[nxt][j] * V;
+      arow[slot[nxt][j]][lane] = lane < V ? g.arc[row + lane] : 0.f;
+      nrow[slot[nxt][j]][lane] = lane < V ? g.next[row + lane] : 0;
+    }
+    cur = nxt;
+    n = n_new;
+  }
+  // the totals, with the end term fin[state]; ranked by counting as rescore_kernel ranks (without a graph the members
+  // are in the order they won, which is this order)
+  if (tid < K) {
+    float key = -INFINITY, total = -INFINITY, ctc = -INFINITY, gr = 0.f;
+    if (tid < n) {
+      const double c = dec_lae(gb[cur][tid], gn[cur][tid]);
+      double l = 0.0, tv = c;
+      if (use_g) {
+        l = G[cur][tid];
+        tv += gw * l;
+      }
+      if (use_len) tv += beta * (double)tlen[cur][tid];
+      if (use_g) {
+        const double e = (double)g.fin[min(max(gst[cur][tid], 0), s_max)];
+        l += e;
+        tv += gw * e;
+      }
+      total = (float)tv; ctc = (float)c; gr = (float)l;
+      key = total != total ? -INFINITY : total;
+    }
+    fkey[tid] = key; ftot[tid] = total; fctc[tid] = ctc; fgr[tid] = gr;
+    fsrc[tid] = -1;
+  }
+  __syncthreads();
+  if (tid < n) {
+    const float key = fkey[tid];
+    int rank = 0;
+    for (int j = 0; j < n; ++j) rank += (fkey[j] > key || (fkey[j] == key && j < tid)) ? 1 : 0;
+    fsrc[rank] = tid;
+  }
+  __syncthreads();
+  const int32_t* tfin = text + (int64_t)cur * K * T;
+  for (int j = 0; j < K; ++j) {
+    const int src = fsrc[j];
+    const int l = src >= 0 ? tlen[cur][src] : 0;
+    int32_t* out = a.chars + ((int64_t)b * K + j) * T;
+    for (int i = tid; i < T; i += DEC_NT) out[i] = i < l ? tfin[(int64_t)src * T + i] : 0;
+  }
+  if (tid < K) {
+    const int src = fsrc[tid];
+    const int64_t o = (int64_t)b * K + tid;
+    a.n_chars[o] = src >= 0 ? tlen[cur][src] : 0;
+    a.scores[o] = src >= 0 ? ftot[src] : -INFINITY;
+    g.ctc_scores[o] = src >= 0 ? fctc[src] : -INFINITY;
+    g.graph_scores[o] = src >= 0 ? fgr[src] : 0.f;
+  }
+  if (tid == 0) a.n_hyps[b] = n;
+}
+
+constexpr int GRAPH_MAX_STATES = 1 << 20;
+
 }  // namespace
 
 extern "C" int64_t ssasr_ctc_decode_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K) {
@@ -735,6 +1011,44 @@ extern "C" int ssasr_ctc_decode(const float* logits, const int32_t* frame_lens, 
   a.chars = chars; a.n_chars = n_chars; a.scores = scores; a.n_hyps = n_hyps;
   void (*fn)(DecodeArgs) = K == 0 ? ctc_best_path_kernel : ctc_prefix_beam_kernel;
   hipLaunchKernelGGL(fn, dim3((unsigned)B), dim3(DEC_NT), 0, (hipStream_t)stream, a);
+  SSASR_LAUNCH_CHECK();
+  return SSASR_OK;
+}
+
+extern "C" int64_t ssasr_ctc_decode_graph_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K) {
+  if (K < 1 || decode_check_shape(B, T, V, K) != SSASR_OK) return 0;
+  return B * 2 * K * T * 4;
+}
+
+extern "C" int ssasr_ctc_decode_graph(const float* logits, const int32_t* frame_lens, int64_t B, int64_t T, int64_t V,
+                                      int64_t K, int blank, void* ws, int64_t ws_bytes, int32_t* chars,
+                                      int32_t* n_chars, float* scores, int32_t* n_hyps, const ssasr_char_graph* graph,
+                                      float graph_weight, float length_bonus, float* ctc_scores, float* graph_scores,
+                                      void* stream) {
+  if (!logits || !frame_lens || !ws || !chars || !n_chars || !scores || !n_hyps || !ctc_scores || !graph_scores)
+    return SSASR_EARG;
+  if (!std::isfinite(graph_weight) || graph_weight < 0.f || !std::isfinite(length_bonus)) return SSASR_EARG;
+  if (K < 1 || decode_check_shape(B, T, V, K) != SSASR_OK || blank < 0 || blank >= V) return SSASR_EARG;
+  if (graph_weight != 0.f && !graph) return SSASR_EARG;
+  if (graph && (!graph->next || !graph->arc || !graph->fin || graph->V != V || graph->S < 1 ||
+                graph->S > GRAPH_MAX_STATES || graph->start < 0 || graph->start >= graph->S))
+    return SSASR_EARG;
+  if ((reinterpret_cast<uintptr_t>(ws) & 7) || ws_bytes < ssasr_ctc_decode_graph_ws_bytes(B, T, V, K)) return SSASR_EARG;
+  GraphArgs g{};
+  DecodeArgs& a = g.d;
+  a.logits = logits; a.frame_lens = frame_lens;
+  a.T = (int)T; a.V = (int)V; a.K = (int)K; a.blank = blank;
+  a.text = reinterpret_cast<int32_t*>(ws);
+  a.chars = chars; a.n_chars = n_chars; a.scores = scores; a.n_hyps = n_hyps;
+  g.graph_weight = graph_weight; g.length_bonus = length_bonus;
+  g.ctc_scores = ctc_scores; g.graph_scores = graph_scores;
+  g.S = 1;
+  if (graph && graph_weight != 0.f) {                        // weight 0: the tables are unread
+    g.next = graph->next; g.arc = graph->arc; g.fin = graph->fin;
+    g.S = graph->S; g.start = graph->start;
+  }
+  hipLaunchKernelGGL(ctc_prefix_beam_graph_kernel, dim3((unsigned)B), dim3(DEC_NT), 0,
+                     (hipStream_t)stream, g);
   SSASR_LAUNCH_CHECK();
   return SSASR_OK;
 }

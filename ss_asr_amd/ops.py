@@ -1142,6 +1142,68 @@ def ctc_head_decode_lm(feat, weight, bias, frame_lens, beam_size, lm, lm_weight=
     return out
 
 
+def ctc_decode_graph(logits, frame_lens, beam_size, graph, graph_weight=0.0, length_bonus=0.0, blank=0):
+    """ssasr_ctc_decode_graph: ctc_decode's prefix beam search with a character graph (char_graph.CharGraph: an n-gram
+    LM, hotwords, their product) in the ranking, in one launch (include/ssasr.h).  logits [B, T, V], frame_lens int32
+    [B] on the device; beam_size 1 .. 32; graph with n_classes == V (None is allowed at graph_weight 0), uploaded to
+    the logits' device on first use and held there; graph_weight finite and >= 0.  -> a dict: chars [B, K, T] int32,
+    n_chars [B, K] int32, scores / ctc_scores / graph_scores [B, K] float32 (the fused total, the CTC part, G + fin),
+    n_hyps [B] int32, best first.  At zero weights the first four are ctc_decode's bits.  No autograd."""
+    from .char_graph import CharGraph
+    lib = _lib.load()
+    blank, graph_weight, length_bonus = int(blank), float(graph_weight), float(length_bonus)
+    if isinstance(beam_size, bool) or not isinstance(beam_size, int) or not 1 <= beam_size <= CTC_DECODE_MAX_BEAM:
+        raise ValueError('ctc_decode_graph: beam_size must be an int in 1..%d (the best path has no graph form), got %r'
+                         % (CTC_DECODE_MAX_BEAM, beam_size))
+    if not (math.isfinite(graph_weight) and graph_weight >= 0.0 and math.isfinite(length_bonus)):
+        raise ValueError('ctc_decode_graph: graph_weight must be finite and >= 0 and length_bonus finite, got %r, %r'
+                         % (graph_weight, length_bonus))
+    if graph is None and graph_weight != 0.0:
+        raise ValueError('ctc_decode_graph: graph_weight %g needs a graph' % graph_weight)
+    if graph is not None and not isinstance(graph, CharGraph):
+        raise TypeError('ctc_decode_graph: graph must be a char_graph.CharGraph, got %s' % type(graph).__name__)
+    if logits.dim() != 3:
+        raise ValueError('ctc_decode_graph: logits must be [B, T, V], got %r' % (tuple(logits.shape),))
+    if frame_lens.dtype != torch.int32 or frame_lens.numel() != logits.shape[0]:
+        raise TypeError('ctc_decode_graph: frame_lens must be int32 [B]')
+    B, T, V = logits.shape
+    if not 0 <= blank < V:
+        raise ValueError('ctc_decode_graph: blank %d is no class of V=%d' % (blank, V))
+    if graph is not None and graph.n_classes != V:
+        raise ValueError('ctc_decode_graph: the graph has %d classes, the logits %d' % (graph.n_classes, V))
+    _need_gpu(logits, frame_lens)
+    logits = _f32c(logits.detach())
+    s, keep = graph.to(logits.device) if graph is not None else (None, None)
+    need = int(lib.ssasr_ctc_decode_graph_ws_bytes(B, T, V, beam_size))
+    if need <= 0:
+        raise ValueError('ctc_decode_graph: shape B=%d T=%d V=%d beam_size=%d has no kernel' % (B, T, V, beam_size))
+    dev = logits.device
+    ws = torch.empty((need + 7) // 8, device=dev, dtype=torch.int64)
+    out = {'chars': torch.empty(B, beam_size, T, device=dev, dtype=torch.int32),
+           'n_chars': torch.empty(B, beam_size, device=dev, dtype=torch.int32),
+           'n_hyps': torch.empty(B, device=dev, dtype=torch.int32)}
+    for name in ('scores', 'ctc_scores', 'graph_scores'):
+        out[name] = torch.empty(B, beam_size, device=dev, dtype=torch.float32)
+    check(lib.ssasr_ctc_decode_graph(_p(logits), _p(frame_lens.contiguous()), B, T, V, beam_size, blank, _p(ws),
+                                     ws.numel() * 8, _p(out['chars']), _p(out['n_chars']), _p(out['scores']),
+                                     _p(out['n_hyps']), C.byref(s) if s is not None else None, graph_weight,
+                                     length_bonus, _p(out['ctc_scores']), _p(out['graph_scores']), _stream()),
+          'ssasr_ctc_decode_graph')
+    return out
+
+
+def ctc_head_decode_graph(feat, weight, bias, frame_lens, beam_size, graph, graph_weight=0.0, length_bonus=0.0, blank=0):
+    """ctc_decode_graph on the head's logits, the product issued as ctc_head_decode issues it.  -> ctc_decode_graph's
+    dict with the logits [B, T, V] they were decoded from under 'logits'.  No autograd."""
+    _need_gpu(feat, weight, bias)
+    feat, w, b = _f32c(feat.detach()), _f32c(weight.detach()), _f32c(bias.detach())
+    B, T, E = feat.shape
+    logits = gemm(feat.view(B * T, E), w, bias=b).view(B, T, w.shape[0])
+    out = ctc_decode_graph(logits, frame_lens, beam_size, graph, graph_weight, length_bonus, blank)
+    out['logits'] = logits
+    return out
+
+
 EDIT_SCORE_MAX_HYP = 8191     # ssasr_edit_score's limits on a row's tokens, counted before dropping
 EDIT_SCORE_MAX_REF = 1023
 

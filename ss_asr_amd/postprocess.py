@@ -445,6 +445,113 @@ def ctc_prefix_beam_lm_reference(lp, K, lm, lm_weight=0.0, length_bonus=0.0, eos
     return [(e[0], e[1]) for e in out], gap
 
 
+def ctc_prefix_beam_graph_reference(lp, K, graph, graph_weight=0.0, length_bonus=0.0, blank=0, dtype=np.float64,
+                                    trace=None, parts=None):
+    """BUILD-DEFINED: CTC prefix beam search with a character graph in the ranking, ssasr_ctc_decode_graph
+    (include/ssasr.h) restated over Python tuples as texts -- what the kernel is defined and tested against.  lp, K,
+    blank, dtype and trace as ctc_prefix_beam_reference takes them (K >= 1); graph: a char_graph.CharGraph (anything
+    with next [S][V], arc [S][V], fin [S] and start; None at graph_weight 0), its float32 tables evaluated in `dtype`.
+      G(w) = sum_i arc[s_{i-1}][c_i] along s_0 = start, s_i = next[s_{i-1}][c_i]; an arc of -inf forbids the extension.
+      Frame t: the candidates and their g_b', g_n' are ctc_prefix_beam_reference's; a candidate's key is
+      logaddexp(g_b', g_n') + graph_weight G(w) + length_bonus len(w), a term whose weight is exactly 0 left out (the
+      weights are taken as float32 values; graph_weight >= 0); a key of -inf is no candidate; the K candidates with the
+      largest keys are the next members.  G(u + (c,)) = G(u) + arc[state(u)][c]: only members are ever extended.
+      After the last frame: total = key + graph_weight fin[state(w)].
+    -> ([(text, total)] best first, gap): gap is the smallest difference that any frame left between the lowest kept
+    and the highest dropped key, or that the final order left between adjacent totals (inf when neither occurred).
+    parts: a list that receives (CTC part, graph part G + fin) per returned entry."""
+    lp = np.asarray(lp, dtype=dtype)
+    K, blank = int(K), int(blank)
+    if lp.ndim != 2:
+        raise ValueError('ctc_prefix_beam_graph_reference: lp must be [T, V], got %r' % (lp.shape,))
+    if K < 1:
+        raise ValueError('ctc_prefix_beam_graph_reference: K must be >= 1, got %d' % K)
+    V = lp.shape[1]
+    f64 = np.dtype(dtype) == np.float64
+    gw, beta = float(np.float32(graph_weight)), float(np.float32(length_bonus))
+    if not (math.isfinite(gw) and math.isfinite(beta)) or gw < 0:
+        raise ValueError('ctc_prefix_beam_graph_reference: graph_weight must be finite and >= 0, length_bonus finite')
+    use_g = gw != 0.0
+    if f64:                                                     # Python floats ARE float64, and ten times faster
+        rows, zero, neg = lp.tolist(), 0.0, -math.inf
+
+        def lae(a, b):
+            if a < b:
+                a, b = b, a
+            return a if b == -math.inf else a + math.log1p(math.exp(b - a))
+    else:
+        rows, zero, neg, lae = [list(row) for row in lp], dtype(0), dtype(-np.inf), np.logaddexp
+        gw, beta = dtype(gw), dtype(beta)
+    walked = {}
+    if use_g:
+        if graph is None:
+            raise ValueError('ctc_prefix_beam_graph_reference: graph_weight %g needs a graph' % gw)
+        nxt = np.asarray(graph.next)
+        arc, fin = np.asarray(graph.arc, dtype=dtype), np.asarray(graph.fin, dtype=dtype)
+        if nxt.ndim != 2 or nxt.shape[1] != V or arc.shape != nxt.shape or fin.shape != nxt.shape[:1]:
+            raise ValueError('ctc_prefix_beam_graph_reference: the graph has tables %r, %r, %r, lp %d classes'
+                             % (nxt.shape, arc.shape, fin.shape, V))
+        nxt = nxt.tolist()
+        arc, fin = (arc.tolist(), fin.tolist()) if f64 else ([list(r) for r in arc], list(fin))
+        walked[()] = (zero, int(graph.start))
+
+    def walk(w):
+        """(G(w), state(w))"""
+        if w not in walked:
+            g, s = walk(w[:-1])
+            walked[w] = (g + arc[s][w[-1]], nxt[s][w[-1]])
+        return walked[w]
+
+    def key_of(w, total):
+        if not total > neg:
+            return neg
+        if use_g:
+            total = total + gw * walk(w)[0]
+        if beta != 0:
+            total = total + beta * len(w)
+        return total
+
+    beam = {(): (zero, neg)}
+    gap = math.inf
+    classes = [c for c in range(V) if c != blank]
+    with np.errstate(all='ignore'):
+        for row in rows:
+            either = {u: lae(g[0], g[1]) for u, g in beam.items()}
+            new, key = {}, {}
+            for w in set(beam) | {u + (c,) for u in beam for c in classes}:
+                g_b = row[blank] + either[w] if w in beam else neg
+                g_n = neg
+                if w:
+                    p, c = w[:-1], w[-1]
+                    stay = beam[w][1] if w in beam else neg
+                    grow = neg
+                    if p in beam:
+                        grow = beam[p][0] if p and p[-1] == c else either[p]
+                    g_n = row[c] + lae(stay, grow)
+                new[w] = (g_b, g_n)
+                key[w] = key_of(w, lae(g_b, g_n))
+            ranked = sorted((w for w in new if key[w] > neg), key=lambda w: (-key[w], w))
+            if len(ranked) > K:
+                gap = min(gap, float(key[ranked[K - 1]] - key[ranked[K]]))
+            beam = {w: new[w] for w in ranked[:K]}
+            if trace is not None:
+                trace.append(frozenset(beam))
+        out = []
+        for w, g in beam.items():
+            ctc = lae(g[0], g[1])
+            total, part = key_of(w, ctc), zero
+            if use_g:
+                part, s = walk(w)
+                part, total = part + fin[s], total + gw * fin[s]
+            out.append((w, float(total), float(ctc), float(part)))
+    out.sort(key=lambda e: (-e[1], e[0]))
+    for a, b in zip(out, out[1:]):
+        gap = min(gap, a[1] - b[1])
+    if parts is not None:
+        parts.extend((e[2], e[3]) for e in out)
+    return [(e[0], e[1]) for e in out], gap
+
+
 class ErrorStats:
     """Corpus-level error rates: sums (S, D, I, N) rows of characters and of words; cer / wer =
     sum(S + D + I) / sum(N), nan when N == 0.  (calc_err below stays the reference's mean of per-utterance ratios.)"""

@@ -679,7 +679,13 @@ class ASRTester(Solver):
     lm_weight and length_bonus (finite numbers, absent: 0; beam_size >= 1) put the tester's language model INSIDE the
     prefix search (ssasr_ctc_decode_lm: a text is ranked by its CTC score + lm_weight log P_lm + length_bonus *
     length); `decode_file` then gains `_clm<lm_weight>` (and `_clb<length_bonus>`) when lm_weight != 0, and with
-    asr.decode_rescore lm_weight (>= 0) is decode_two_pass's first_lm_weight.  It composes with
+    asr.decode_rescore lm_weight (>= 0) is decode_two_pass's first_lm_weight.  The optional keys hotwords (a list of
+    strings) with hotword_bonus (>= 0, absent: 1.0) and ngram_lm (the path of a char_graph.CharGraph.save file) with
+    ngram_weight (>= 0, absent: 0.5) put a character graph INSIDE the prefix search (ssasr_ctc_decode_graph;
+    beam_size >= 1): contextual biasing towards the phrases, a count-based n-gram LM, or with both their product;
+    everything is validated in set_model, length_bonus goes with it, and `decode_file` gains `_hw<n>x<bonus>` /
+    `_ng<weight>` (and `_clb<length_bonus>`) only when a key is present.  Together with asr.decode_rescore or a
+    non-zero lm_weight they are an error (not built).  It composes with
     decode_score, decode_mbr (which then needs THIS beam_size >= 2) and decode_align; together with a positive
     asr.decode_ctc_weight or any of the beam search's terms it is an error.
     asr.decode_rescore: {ctc_weight: 0.3, length_bonus: 0.0} (absent: off; ctc_weight a number in [0, 1], length_bonus
@@ -751,9 +757,9 @@ class ASRTester(Solver):
             return None
         if conf is True:
             conf = {}
-        if not isinstance(conf, dict) or set(conf) - {'beam_size', 'lm_weight', 'length_bonus'}:
-            raise ValueError('asr.decode_ctc_only must be a mapping with the key beam_size (and, optionally, lm_weight '
-                             'and length_bonus), got {!r}'.format(conf))
+        if not isinstance(conf, dict) or set(conf) - ({'beam_size', 'lm_weight', 'length_bonus'} | set(ASRTester.GRAPH_KEYS)):
+            raise ValueError('asr.decode_ctc_only must be a mapping with the key beam_size (and, optionally, lm_weight, '
+                             'length_bonus, hotwords, hotword_bonus, ngram_lm and ngram_weight), got {!r}'.format(conf))
         beam = conf.get('beam_size', 8)
         if isinstance(beam, bool) or not isinstance(beam, int) or not 0 <= beam <= 32:
             raise ValueError('asr.decode_ctc_only.beam_size must be an integer in 0..32, got {!r}'.format(beam))
@@ -780,6 +786,70 @@ class ASRTester(Solver):
             raise ValueError('asr.decode_ctc_only with asr.decode_rescore: the first pass takes lm_weight >= 0 and no '
                              'length_bonus (asr.decode_rescore.length_bonus is the second pass\'s), got {!r}'.format(conf))
         return out
+
+    GRAPH_KEYS = ('hotwords', 'hotword_bonus', 'ngram_lm', 'ngram_weight')
+
+    @staticmethod
+    def ctc_only_graph(asr_config):
+        """The character-graph keys of asr.decode_ctc_only, validated: None when none of them is present, else
+        {'hotwords': [strings] or None, 'hotword_bonus': float, 'ngram_lm': path or None, 'ngram_weight': float}."""
+        import math
+        beam = ASRTester.ctc_only_beam(asr_config)
+        conf = asr_config.get('decode_ctc_only')
+        conf = conf if isinstance(conf, dict) else {}
+        if not set(conf) & set(ASRTester.GRAPH_KEYS):
+            return None
+        words, path = conf.get('hotwords'), conf.get('ngram_lm')
+        if words is None and path is None:
+            raise ValueError('asr.decode_ctc_only: hotword_bonus / ngram_weight need hotwords / ngram_lm, got {!r}'
+                             .format(conf))
+        if words is not None and (not isinstance(words, (list, tuple)) or not words or
+                                  any(not isinstance(w, str) or not w for w in words)):
+            raise ValueError('asr.decode_ctc_only.hotwords must be a non-empty list of non-empty strings, got {!r}'
+                             .format(words))
+        if path is not None and (not isinstance(path, str) or not path):
+            raise ValueError('asr.decode_ctc_only.ngram_lm must be the path of a CharGraph.save file, got {!r}'
+                             .format(path))
+        out = {'hotwords': list(words) if words is not None else None, 'ngram_lm': path}
+        for key, default, need in (('hotword_bonus', 1.0, words), ('ngram_weight', 0.5, path)):
+            v = conf.get(key, default)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+                raise ValueError('asr.decode_ctc_only.{} must be a finite number >= 0, got {!r}'.format(key, v))
+            if key in conf and need is None:
+                raise ValueError('asr.decode_ctc_only.{} needs asr.decode_ctc_only.{}'.format(
+                    key, 'hotwords' if key == 'hotword_bonus' else 'ngram_lm'))
+            out[key] = float(v)
+        if beam == 0:
+            raise ValueError('asr.decode_ctc_only: beam_size 0, the best path, has no graph term; got {!r}'.format(conf))
+        if asr_config.get('decode_rescore') not in (None, False):
+            raise ValueError('asr.decode_ctc_only: hotwords / ngram_lm with asr.decode_rescore is not built '
+                             '(ASR.rescore has no graph term)')
+        if ASRTester.ctc_only_lm(asr_config)['lm_weight'] != 0:
+            raise ValueError('asr.decode_ctc_only: hotwords / ngram_lm together with a CharLM lm_weight in one search is '
+                             'not built; give one of them')
+        return out
+
+    def build_ctc_graph(self, conf):
+        """(CharGraph, graph_weight) of ctc_only_graph's keys: the hotwords' graph at weight 1, the n-gram graph at
+        ngram_weight, or the product of the two, each factor pre-scaled, at weight 1."""
+        from .char_graph import CharGraph
+        V, hot, lm = self.mapper.get_dim(), None, None
+        if conf['hotwords'] is not None:
+            try:
+                phrases = [[self.mapper.char_to_ind(ch) for ch in w] for w in conf['hotwords']]
+            except KeyError as e:
+                raise ValueError('asr.decode_ctc_only.hotwords: {!r} is no character of the model'.format(e.args[0]))
+            hot = CharGraph.hotwords(phrases, conf['hotword_bonus'], V, ops.CTC_BLANK)
+        if conf['ngram_lm'] is not None:
+            if not os.path.isfile(conf['ngram_lm']):
+                raise ValueError('asr.decode_ctc_only.ngram_lm: no file {!r}'.format(conf['ngram_lm']))
+            lm = CharGraph.load(conf['ngram_lm'])
+            if lm.n_classes != V:
+                raise ValueError('asr.decode_ctc_only.ngram_lm: the graph has {} classes, the model {}'
+                                 .format(lm.n_classes, V))
+        if hot is not None and lm is not None:
+            return CharGraph.product(lm.scaled(conf['ngram_weight']), hot), 1.0
+        return (hot, 1.0) if hot is not None else (lm, conf['ngram_weight'])
 
     @staticmethod
     def rescore_args(asr_config):
@@ -825,6 +895,8 @@ class ASRTester(Solver):
         self.decode_ctc_only = self.ctc_only_beam(self.config['asr'])
         self.decode_rescore = self.rescore_args(self.config['asr'])
         self.decode_ctc_lm = self.ctc_only_lm(self.config['asr'])
+        graph_conf = self.ctc_only_graph(self.config['asr'])
+        self.decode_ctc_graph = None if graph_conf is None else self.build_ctc_graph(graph_conf)
         if self.decode_ctc_only is not None:
             if 'ctc_weight' not in self.config['asr']['mdl']:
                 raise ValueError('asr.decode_ctc_only needs a model with a ctc_head: set asr.mdl.ctc_weight '
@@ -863,6 +935,13 @@ class ASRTester(Solver):
             self.decode_file += '_ctconly{:}'.format(self.decode_ctc_only)
             if self.decode_ctc_lm['lm_weight'] != 0:
                 self.decode_file += '_clm{:}'.format(self.decode_ctc_lm['lm_weight'])
+                if self.decode_ctc_lm['length_bonus'] != 0:
+                    self.decode_file += '_clb{:}'.format(self.decode_ctc_lm['length_bonus'])
+            if graph_conf is not None:
+                if graph_conf['hotwords'] is not None:
+                    self.decode_file += '_hw{:}x{:}'.format(len(graph_conf['hotwords']), graph_conf['hotword_bonus'])
+                if graph_conf['ngram_lm'] is not None:
+                    self.decode_file += '_ng{:}'.format(graph_conf['ngram_weight'])
                 if self.decode_ctc_lm['length_bonus'] != 0:
                     self.decode_file += '_clb{:}'.format(self.decode_ctc_lm['length_bonus'])
         if self.decode_rescore is not None:
@@ -910,6 +989,12 @@ class ASRTester(Solver):
                              self.asr_model.decode_two_pass(xs, x_lens, self.lm, self.mapper, lm_weight,
                                                             beam_size=ctc_only, **self.decode_rescore,
                                                             first_lm_weight=self.decode_ctc_lm['lm_weight'])]
+                elif ctc_only is not None and self.decode_ctc_graph is not None:
+                    texts = [hyps[0][0] for hyps in
+                             self.asr_model.decode_ctc(xs, x_lens, self.mapper, beam_size=ctc_only,
+                                                       length_bonus=self.decode_ctc_lm['length_bonus'],
+                                                       graph=self.decode_ctc_graph[0],
+                                                       graph_weight=self.decode_ctc_graph[1])]
                 elif ctc_only is not None:
                     texts = [hyps[0][0] for hyps in
                              self.asr_model.decode_ctc(xs, x_lens, self.mapper, beam_size=ctc_only, rnn_lm=self.lm,

@@ -27,7 +27,8 @@
  * launch-form query -- ssasr_bilstm_forms; beam search --
  * ssasr_beam, ssasr_decode_beam_ws_bytes, ssasr_decode_beam; joint CTC / attention decoding -- ssasr_ctc_prefix,
  * ssasr_decode_beam_ctc_ws_bytes, ssasr_decode_beam_ctc; length bonus, coverage term and end detection in the beam
- * search -- ssasr_beam_terms, ssasr_decode_beam_ex_ws_bytes, ssasr_decode_beam_ex; SpecAugment in batch assembly and label smoothing in the
+ * search -- ssasr_beam_terms, ssasr_decode_beam_ex_ws_bytes, ssasr_decode_beam_ex; a character graph in the beam search --
+ * ssasr_decode_beam_graph_ws_bytes, ssasr_decode_beam_graph; SpecAugment in batch assembly and label smoothing in the
  * masked CE -- ssasr_specaug, ssasr_gather_batch_aug, ssasr_specaug_plan, ssasr_ce_loss_ls_fwd, ssasr_ce_loss_ls_bwd; CTC forced
  * alignment -- ssasr_ctc_align_ws_bytes, ssasr_ctc_align; CTC-only decoding -- ssasr_ctc_decode_ws_bytes, ssasr_ctc_decode; edit-distance scoring -- ssasr_edit_score; MWER training --
  * ssasr_mwer_ws_bytes, ssasr_mwer_loss_fwd, ssasr_mwer_loss_bwd, ssasr_mwer_pack, ssasr_rows_repeat_fwd, ssasr_rows_repeat_bwd; sampled
@@ -1207,6 +1208,50 @@ int64_t ssasr_decode_beam_ex_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E
                                       int64_t V, int64_t Hl, int64_t S, int32_t ctc, int32_t coverage);
 int ssasr_decode_beam_ex(const ssasr_beam* d, const ssasr_ctc_prefix* c /* NULL or weight 0: no CTC */,
                          const ssasr_beam_terms* t, void* stream);
+
+/* ---- a character graph in the attention beam search: n-gram LM and hotword biasing (added under ABI 16) ----------
+ * BUILD-DEFINED.  ssasr_decode_beam_ex's search (c and t both optional) with the ssasr_char_graph of
+ * ssasr_ctc_decode_graph (above: next [S][V], arc [S][V] finite or -inf = FORBIDDEN, fin [S] finite, start) inside the
+ * same one-launch kernel.  Per utterance, on top of that entry's semantics:
+ *   every live hypothesis g carries state(g) (int32) and G(g) (double, the sum of the arcs taken); the empty prefix has
+ *     state = start, G = 0;
+ *   candidate (b, v), v != eos: that entry's candidate score + graph_weight * arc[state_b][v];
+ *   candidate (b, eos): that entry's candidate score + graph_weight * fin[state_b]; the column arc[.][eos] is never read;
+ *   the graph term is ONE float product, added LAST: after the CTC term, the LM term, the parent's score, beta and the
+ *     coverage increment;
+ *   a candidate at -inf (a forbidden arc, or the CTC form's own rule) is never chosen: in every graph form the width is
+ *     min(K - finished, finite candidates).  fin is finite, so a live hypothesis with a finite score keeps a finite
+ *     <EOS> candidate and the loop still ends; a beam may hold fewer than K members;
+ *   a chosen non-eos candidate's new slot takes state = next[state_b][v], clamped to [0, S - 1], and
+ *     G = G_b + arc[state_b][v] (double).  The tables' CONTENTS cannot be checked here: with the clamp (and start checked
+ *     below) a malformed table gives wrong scores and never a read outside the tables;
+ *   the cap is unchanged: a hypothesis still live after max_steps is emitted as it stands, with NO fin term, exactly as
+ *     it carries no <EOS> term.  Consequence: a capped text in the middle of a partial hotword match keeps the advance
+ *     that fin would have retracted;
+ *   ties, the <EOS> rule, end detection (which compares the fused scores), the output order, the unused slots and an
+ *     utterance's independence of N and the padded T are unchanged.
+ * graph_scores [N][K], in output order beside hyp_scores (the fused total): G of a capped hypothesis, G + fin of one
+ * ended by <EOS>, each rounded once from double; unused slots 0.
+ * graph_weight == 0: the term is left out and the tables are unread (graph may be NULL); the call launches exactly the
+ * kernel ssasr_decode_beam_ex would launch (t == NULL: the one ssasr_decode_beam / ssasr_decode_beam_ctc launch), gives
+ * the same bits, and graph_scores is all zeros.
+ * Accepted: what the underlying entry accepts (c NULL or ssasr_decode_beam_ctc's checks; t NULL -- every term off -- or
+ * ssasr_decode_beam_ex's checks); graph_weight finite and >= 0 (a negative weight would turn a forbidden arc into
+ * +inf); graph a HOST pointer to a struct of DEVICE tables, required with its three tables when graph_weight != 0, and
+ * whenever it is passed graph->V == d->V, 1 <= S <= 1,048,576 and 0 <= start < S; graph_scores non-NULL;
+ * ws_bytes >= ssasr_decode_beam_graph_ws_bytes(...), which takes ssasr_decode_beam_ex_ws_bytes' arguments and returns
+ * its figure: the graph state (K states, K doubles, twice, and the finished entries' parts) is in LDS.  Everything else
+ * is an argument error before any HIP call, and the size query returns 0.
+ * One workgroup per utterance, no exchange between workgroups, no spins, no atomics; every loop is bounded by
+ * max_steps, enc_len, K or a dimension.  Table reads per step: one row of arc (4 V bytes) per live hypothesis, then
+ * next / arc of the <= K chosen candidates and fin of the step's finished ones.
+ * Not built: a graph term in ssasr_rescore or ssasr_decode_sample, per-phrase bonuses, word-level n-grams. */
+int64_t ssasr_decode_beam_graph_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
+                                         int64_t V, int64_t Hl, int64_t S, int32_t ctc, int32_t coverage);
+int ssasr_decode_beam_graph(const ssasr_beam* d, const ssasr_ctc_prefix* c /* NULL or weight 0: no CTC */,
+                            const ssasr_beam_terms* t /* NULL: every term off */,
+                            const ssasr_char_graph* graph, float graph_weight,
+                            float* graph_scores, void* stream);
 
 /* ---- sampled decoding (added under ABI 16) ---------------------------------------------------------------------
  * BUILD-DEFINED: the reference draws characters only inside its training loop (scheduled sampling).  The loop of

@@ -135,6 +135,9 @@ SIGNATURES = {
     'ssasr_decode_beam_ctc': (I32, [C.POINTER(Beam), C.POINTER(CtcPrefix), P]),
     'ssasr_decode_beam_ex_ws_bytes': (I64, [I64] * 9 + [I32, I32]),
     'ssasr_decode_beam_ex': (I32, [C.POINTER(Beam), C.POINTER(CtcPrefix), C.POINTER(BeamTerms), P]),
+    'ssasr_decode_beam_graph_ws_bytes': (I64, [I64] * 9 + [I32, I32]),
+    'ssasr_decode_beam_graph': (I32, [C.POINTER(Beam), C.POINTER(CtcPrefix), C.POINTER(BeamTerms), C.POINTER(CharGraph),
+                                      F32, P, P]),
     'ssasr_decode_sample_ws_bytes': (I64, [I64] * 9),
     'ssasr_decode_sample': (I32, [C.POINTER(Beam), C.POINTER(Sample), P]),
     'ssasr_charlm_train_ws_floats': (I64, [I64, I64, I64, I64]),

@@ -288,6 +288,8 @@ class ASR(nn.Module):
         self.last_beam = None
         # n_steps [N] int32 of the last decode_nbest call that had a length bonus, a coverage term or end detection on
         self.last_beam_steps = None
+        # graph_scores [N, K] of the last decode_nbest call if it had a character graph at a weight > 0, else None
+        self.last_beam_graph = None
         # _encode_packed's most recent result: (features [N, T'max, E], int32 [N] frame counts), what align() reuses
         self.last_encoded_packed = None
         # align's device results: (path [N, T'], first [N, Lmax], last [N, Lmax], char_logp [N, Lmax], score [N] double,
@@ -432,19 +434,39 @@ class ASR(nn.Module):
         return dict(length_bonus=length_bonus, coverage_weight=coverage_weight,
                     coverage_threshold=coverage_threshold if coverage_weight != 0.0 else 0.5, end_margin=end_margin)
 
+    def _beam_graph_weight(self, graph, graph_weight):
+        """The beam search's graph keywords, checked as _ctc_graph_weight checks decode_ctc's: the weight as a float,
+        0.0 when no graph term runs (today's path)."""
+        from .char_graph import CharGraph
+        if isinstance(graph_weight, bool) or not isinstance(graph_weight, (int, float)) or \
+                not (math.isfinite(graph_weight) and graph_weight >= 0.0):
+            raise ValueError('graph_weight must be a finite number >= 0, got %r' % (graph_weight,))
+        if graph is not None and not isinstance(graph, CharGraph):
+            raise ValueError('graph must be a char_graph.CharGraph, got %s' % type(graph).__name__)
+        if graph_weight == 0.0:
+            return 0.0
+        if graph is None:
+            raise ValueError('graph_weight %g needs graph' % graph_weight)
+        if graph.n_classes != self.char_trans.weight.shape[0]:
+            raise ValueError('the graph has %d classes, the model %d'
+                             % (graph.n_classes, self.char_trans.weight.shape[0]))
+        return float(graph_weight)
+
     def decode(self, x, x_len, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1, ctc_weight=0.0,
-               length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None):
+               length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None, graph=None,
+               graph_weight=0.0):
         """src/asr.py:112-173: greedy decoding of ONE utterance (x [1, seq, features], x_len from prepare_x)
         until <EOS> or max_decoding_steps (200 in the reference, :128), every step's character scores being
         log_softmax(speller) + lm_weight * log_softmax(rnn_lm).  Returns the decoded string.  rnn_lm None: no LM
         term.  The whole loop is one launch (ssasr_decode_greedy).  beam_size > 1: the best hypothesis of a beam
         search of that width (decode_many).  ctc_weight > 0: joint CTC / attention decoding (decode_nbest).
-        length_bonus, coverage_weight / coverage_threshold, end_margin: the beam search's terms (decode_nbest)."""
+        length_bonus, coverage_weight / coverage_threshold, end_margin: the beam search's terms (decode_nbest).
+        graph / graph_weight: a character graph in the beam search (decode_nbest)."""
         assert len(x.shape) == 3 and x.shape[0] == 1
         return self.decode_many([x], [x_len], rnn_lm, mapper, lm_weight, max_decoding_steps=max_decoding_steps,
                                 beam_size=beam_size, ctc_weight=ctc_weight, length_bonus=length_bonus,
                                 coverage_weight=coverage_weight, coverage_threshold=coverage_threshold,
-                                end_margin=end_margin)[0]
+                                end_margin=end_margin, graph=graph, graph_weight=graph_weight)[0]
 
     def _encode_packed(self, xs, x_lens):
         """Each utterance encoded alone, packed to ([N, T'max, E], int32 [N] frame counts on the device)."""
@@ -617,7 +639,8 @@ class ASR(nn.Module):
         return [m.text for m in self.mbr(mapper, unit=unit, posterior='softmax', scale=scale)]
 
     def decode_many(self, xs, x_lens, rnn_lm, mapper, lm_weight, max_decoding_steps=200, *, beam_size=1,
-                    ctc_weight=0.0, length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None):
+                    ctc_weight=0.0, length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None,
+                    graph=None, graph_weight=0.0):
         """decode() for a list of single utterances in ONE decode launch.  Each utterance is encoded alone
         (blstm_4 recurs over the utterance axis, src/asr.py:237-238, :262: a batched encoder would change every
         transcript); the encoder outputs are packed to [N, T'max, E] and every utterance gets a workgroup of its
@@ -625,12 +648,13 @@ class ASR(nn.Module):
         beam_size > 1 (at most 32): beam search of that width in one launch (ssasr_decode_beam; no length
         normalisation); returns each utterance's best hypothesis and keeps (chars [N, K, steps], n_chars [N, K],
         hyp_scores [N, K], n_hyps [N]) on the device in last_beam; last_decode is left as it was.
-        ctc_weight > 0, or a length bonus, a coverage term or end detection on: as beam_size > 1, for any beam_size
-        in 1..32 (decode_nbest)."""
+        ctc_weight > 0, a length bonus, a coverage term or end detection on, or a graph at a weight > 0: as
+        beam_size > 1, for any beam_size in 1..32 (decode_nbest)."""
         nbest = self.decode_nbest(xs, x_lens, rnn_lm, mapper, lm_weight, beam_size,
                                   max_decoding_steps=max_decoding_steps, ctc_weight=ctc_weight,
                                   length_bonus=length_bonus, coverage_weight=coverage_weight,
-                                  coverage_threshold=coverage_threshold, end_margin=end_margin)
+                                  coverage_threshold=coverage_threshold, end_margin=end_margin, graph=graph,
+                                  graph_weight=graph_weight)
         return [hyps[0][0] for hyps in nbest]
 
     def _decode_args(self, packed, enc_lens, lm, lm_weight, mapper_or_eos, max_steps):
@@ -654,7 +678,8 @@ class ASR(nn.Module):
                  for k in range(n_hyps[i])] for i in range(len(chars))]
 
     def decode_nbest(self, xs, x_lens, rnn_lm, mapper, lm_weight, beam_size, max_decoding_steps=200, *,
-                     ctc_weight=0.0, length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None):
+                     ctc_weight=0.0, length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None,
+                     graph=None, graph_weight=0.0):
         """Beam search over a list of single utterances in ONE launch: per utterance the list of (text, score),
         best first, score = the sum of the chosen characters' log_softmax(speller) + lm_weight *
         log_softmax(rnn_lm) entries (<EOS>'s included when it ended the hypothesis; no length normalisation).
@@ -670,16 +695,30 @@ class ASR(nn.Module):
         the terms of ssasr_decode_beam_ex (include/ssasr.h).  With any of them on, any beam_size in 1..32 runs the
         beam kernel (width 1 is the beam kernel at K = 1), last_beam is set and last_beam_steps keeps n_steps [N],
         the loop iterations each utterance executed.  With all at their defaults every call takes the path above
-        exactly."""
+        exactly.
+        graph / graph_weight: a char_graph.CharGraph (an n-gram LM, hotwords, their product) INSIDE the beam search
+        (ssasr_decode_beam_graph, include/ssasr.h; graph_weight finite and >= 0): a candidate character gains
+        graph_weight * arc[state][character], <EOS> gains graph_weight * fin[state], and a forbidden arc is never
+        taken.  With a graph at a weight > 0 any beam_size in 1..32 runs the beam kernel (width 1 is the beam kernel at
+        K = 1), last_beam and last_beam_steps are set and last_beam_graph keeps graph_scores [N, K], each hypothesis'
+        graph part G (+ fin when <EOS> ended it); every other call sets last_beam_graph to None.  With graph None or
+        graph_weight 0 every call takes the path it takes without the keywords exactly."""
         beam_size = int(beam_size)
         if not 1 <= beam_size <= ops.MAX_BEAM:
             raise ValueError('beam_size must be in 1..%d, got %d' % (ops.MAX_BEAM, beam_size))
         ctc = self._ctc_head(ctc_weight)
         terms = self._beam_terms(length_bonus, coverage_weight, coverage_threshold, end_margin)
+        graph_weight = self._beam_graph_weight(graph, graph_weight)
         with torch.no_grad():
             packed, enc_lens = self._encode_packed(xs, x_lens)
             args = self._decode_args(packed, enc_lens, rnn_lm, lm_weight, mapper, max_decoding_steps)
-            if beam_size == 1 and ctc is None and terms is None:
+            self.last_beam_graph = None
+            if graph_weight != 0.0:
+                out = ops.decode_beam_graph(*args, beam_size, ctc, graph=graph, graph_weight=graph_weight,
+                                            **(terms or {}))
+                self.last_beam, self.last_beam_steps, self.last_beam_graph = out[:4], out[4], out[5]
+                hyps = (self.last_beam[0], self.last_beam[1], self.last_beam[3], self.last_beam[2])
+            elif beam_size == 1 and ctc is None and terms is None:
                 self.last_decode = ops.decode_greedy(*args)
                 chars, n_chars, scores, _ = self.last_decode
                 # the transcript's score: the chosen entries of the executed steps, <EOS>'s too

@@ -635,6 +635,32 @@ __host__ __device__ inline int64_t beam_slice_floats(const BeamWs& m, int K, int
   return (ctc ? ctc_ws_map(m, K, T).total : m.total) + (cover ? cov_ws_floats(m, K) : 0);
 }
 
+// ---- character graph (semantics in include/ssasr.h, ssasr_decode_beam_graph) ---------------------------------------
+// GRAPH true: the same loop with weight * arc[state_b][v] (fin[state_b] on the <EOS> lane) added last to every
+// candidate of parent b, candidates at -inf never chosen.  Per live hypothesis g: state(g) (int32) and G(g) (double) in
+// LDS by step parity, re-parented with the beam like the coverage counts; the finished entries' G + fin beside
+// fin_score.  The only reads of the tables are one row of arc (4 V bytes) per live hypothesis and step in phase 8 and,
+// once the winners are known, next and arc of the <= K picked candidates and fin of the step's finished ones, a lane
+// each.  Every state taken from next is clamped to [0, S - 1] (start is checked by the entry): a malformed table gives
+// wrong scores, never a read outside the tables.  The workspace slice is the form's without a graph.
+struct GraphDev {
+  const int32_t* next;                    // [S][V]
+  const float *arc, *fin;                 // [S][V], [S]
+  int S, start;
+  float weight;                           // > 0 in every GRAPH instantiation
+  float* graph_scores;                    // [N][K], output order
+};
+
+// The graph term of candidate (b, lane) for the wave that owns a hypothesis in `state`: weight * arc[state][lane], or
+// weight * fin[state] on the <EOS> lane, as ONE float product (the caller adds it last).  A lane >= V reads nothing.
+__device__ __forceinline__ float graph_term(const GraphDev& gd, int state, int V, int eos) {
+  const int lane = threadIdx.x & 63;
+  float g = 0.f;
+  if (lane == eos) g = gd.fin[state];
+  else if (lane < V) g = gd.arc[(int64_t)state * V + lane];
+  return __fmul_rn(gd.weight, g);
+}
+
 constexpr int kCtcAhead = 4;              // frames whose loads a lattice loop issues before it needs the first
 
 // log(exp(a) + exp(b))
@@ -725,8 +751,9 @@ __device__ void ctc_extend(const float* lp, const double* pn0, const double* pb0
 // CTC false: ssasr_decode_beam's kernel (cd unread).  CTC true: the same loop with the candidates scored
 // score_b + (1 - lambda) * log_softmax(asr) + lambda * (psi(h) - psi(g)) + lm_weight * log_softmax(lm), candidates
 // at -inf never chosen; only the prologue and phases 8 to 11 differ.  TERMS false: td.n_steps alone is read.
-template <bool CTC, bool TERMS>
-__global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDev cd, TermsDev td) {
+// GRAPH false: gd is unread.
+template <bool CTC, bool TERMS, bool GRAPH = false>
+__global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDev cd, TermsDev td, GraphDev gd) {
   __shared__ float cand[kMaxBeam * 64];            // score_b + row_b[v]; NaN: struck out
   __shared__ float score[2][kMaxBeam];             // live hypotheses' scores, by step parity
   __shared__ float redv[kWaves];
@@ -742,6 +769,9 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
   __shared__ int cov[2][TERMS ? kMaxBeam : 1];     // coverage: the live hypotheses' counts, by step parity
   __shared__ int cov_new[TERMS ? kMaxBeam : 1];    // coverage: cov' of the step's parents
   __shared__ float cov_inc[TERMS ? kMaxBeam : 1];  // coverage: eta * (cov' - cov) of the step's parents
+  __shared__ int gstate[2][GRAPH ? kMaxBeam : 1];  // graph: the live hypotheses' states, by step parity
+  __shared__ double gsum[2][GRAPH ? kMaxBeam : 1]; // graph: the live hypotheses' G, by step parity
+  __shared__ double fin_graph[GRAPH ? kMaxBeam : 1];   // graph: G (+ fin when ended) of the fin_score entries
 
   const InferDev& p = bd.in;
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -804,6 +834,13 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
       if (tid == 0) cov[0][0] = 0;
     }
   }
+  // graph: the empty prefix is in the start state with G = 0
+  if constexpr (GRAPH) {
+    if (tid == 0) {
+      gstate[0][0] = gd.start;
+      gsum[0][0] = 0.0;
+    }
+  }
   phase_sync();
 
   int live = 1, nfin = 0, step = 0;
@@ -854,6 +891,7 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
           if (lane != p.eos) fin += td.beta;
           if (cover) fin += cov_inc[b];
         }
+        if constexpr (GRAPH) fin = __fadd_rn(fin, graph_term(gd, gstate[step & 1][b], V, p.eos));
         cand[b * 64 + lane] = (lane < V && fin == fin) ? fin : -INFINITY;
       }
     } else {
@@ -863,13 +901,14 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
           if (lane != p.eos) fin += td.beta;
           if (cover) fin += cov_inc[b];
         }
+        if constexpr (GRAPH) fin = __fadd_rn(fin, graph_term(gd, gstate[step & 1][b], V, p.eos));
         cand[b * 64 + lane] = (lane < V && fin == fin) ? fin : -INFINITY;      // a NaN is never chosen before a number
       }
     }
     __syncthreads();
     // 9: the W best, in order: W rounds of a block-wide arg-max, ties to the lower flat index
     int width = min(K - nfin, live * V);
-    if constexpr (CTC) {                             // a candidate at -inf is never chosen
+    if constexpr (CTC || GRAPH) {                    // a candidate at -inf is never chosen
       int finite = 0;
       for (int c0 = 0; c0 < live * 64; c0 += kThreads)
         finite += __syncthreads_count(c0 + tid < live * 64 && cand[min(c0 + tid, live * 64 - 1)] > -INFINITY);
@@ -950,6 +989,21 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
     }
     __syncthreads();
     const int nl = counts[0];
+    // graph: a new slot's state and G from next and arc of its picked candidate, the step's finished entries' G + fin;
+    // a lane each, so the up to K look-ups are in flight together (the two ranges lie in different waves)
+    if constexpr (GRAPH) {
+      const int* gs = gstate[step & 1];
+      const double* gG = gsum[step & 1];
+      if (tid < nl) {
+        const int b = par[tid];
+        const int64_t at = (int64_t)gs[b] * V + chr[tid];
+        gstate[(step + 1) & 1][tid] = min(max(gd.next[at], 0), gd.S - 1);
+        gsum[(step + 1) & 1][tid] = gG[b] + (double)gd.arc[at];
+      } else if (tid >= 64 && tid - 64 < counts[1] - nfin) {
+        const int j = nfin + tid - 64, b = fin_par[j];
+        fin_graph[j] = gG[b] + (double)gd.fin[gs[b]];
+      }
+    }
     nfin = counts[1];
     if constexpr (TERMS) {
       if (counts[2]) {                               // the live hypotheses are abandoned prefixes: discarded, not emitted
@@ -1011,6 +1065,7 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
       fin_score[nfin + j] = sc[j];
       fin_len[nfin + j] = step;
       fin_par[nfin + j] = j;
+      if constexpr (GRAPH) fin_graph[nfin + j] = gsum[step & 1][j];      // no fin term, as no <EOS> term
     }
   }
   const int total = nfin + live;                    // <= K: finished + width == K at every step, live <= width
@@ -1018,6 +1073,7 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
   if (tid < K) {
     n_chars[tid] = 0;
     hyp_scores[tid] = 0.f;
+    if constexpr (GRAPH) gd.graph_scores[(int64_t)n * K + tid] = 0.f;
   }
   if (tid == 0) bd.n_hyps[n] = total;
   if (tid == 0 && td.n_steps) td.n_steps[n] = step;  // loop iterations executed
@@ -1028,6 +1084,7 @@ __global__ __launch_bounds__(kThreads) void decode_beam_kernel(BeamDev bd, CtcDe
     int rank = 0;
     for (int j = 0; j < total; ++j) rank += (fin_score[j] > s || (fin_score[j] == s && j < tid)) ? 1 : 0;
     hyp_scores[rank] = s;
+    if constexpr (GRAPH) gd.graph_scores[(int64_t)n * K + rank] = (float)fin_graph[tid];   // rounded once from double
     n_chars[rank] = fin_len[tid];
     int slot = fin_par[tid];
     for (int pos = fin_len[tid] - 1; pos >= 0; --pos) {         // trace the back-pointers
@@ -1631,8 +1688,18 @@ bool beam_dev(const ssasr_beam* dp, Need need, BeamDev& b) {
   return true;
 }
 
-// ssasr_decode_beam (cp == nullptr), ssasr_decode_beam_ctc and ssasr_decode_beam_ex (tp != nullptr)
-int launch_beam(const ssasr_beam* dp, const ssasr_ctc_prefix* cp, const ssasr_beam_terms* tp, void* stream) {
+// ssasr_decode_beam_graph's graph arguments: the weight finite and >= 0, the output there, a graph's shape that of
+// the search (looked at whenever one is passed) and, at a weight != 0, the graph and its tables there
+bool graph_ok(const ssasr_char_graph* gp, float weight, const float* graph_scores, int64_t V) {
+  if (!(std::isfinite(weight) && weight >= 0.f) || !graph_scores) return false;
+  if (gp && (gp->V != V || gp->S < 1 || gp->S > (1 << 20) || gp->start < 0 || gp->start >= gp->S)) return false;
+  return weight == 0.f || (gp && gp->next && gp->arc && gp->fin);
+}
+
+// ssasr_decode_beam (cp == nullptr), ssasr_decode_beam_ctc, ssasr_decode_beam_ex (tp != nullptr) and
+// ssasr_decode_beam_graph (g.weight != 0: its checks are done)
+int launch_beam(const ssasr_beam* dp, const ssasr_ctc_prefix* cp, const ssasr_beam_terms* tp, void* stream,
+                const GraphDev& g = GraphDev{}) {
   TermsDev t{0.f, 0.f, 0.f, -1.f, nullptr};
   if (tp) {
     if (!std::isfinite(tp->length_bonus) || !std::isfinite(tp->coverage_weight) || tp->end_margin != tp->end_margin)
@@ -1659,20 +1726,43 @@ int launch_beam(const ssasr_beam* dp, const ssasr_ctc_prefix* cp, const ssasr_be
     }
   }
   // all terms off: the instantiations ssasr_decode_beam / ssasr_decode_beam_ctc launch
+  // a graph: the TERMS forms alone are instantiated (with every term off they add 0 and stop nothing)
   const dim3 grid((unsigned)d.N), block(kThreads);
-  if (c.w && terms)
-    hipLaunchKernelGGL((decode_beam_kernel<true, true>), grid, block, 0, (hipStream_t)stream, b, c, t);
+  if (g.weight != 0.f && c.w)
+    hipLaunchKernelGGL((decode_beam_kernel<true, true, true>), grid, block, 0, (hipStream_t)stream, b, c, t, g);
+  else if (g.weight != 0.f)
+    hipLaunchKernelGGL((decode_beam_kernel<false, true, true>), grid, block, 0, (hipStream_t)stream, b, c, t, g);
+  else if (c.w && terms)
+    hipLaunchKernelGGL((decode_beam_kernel<true, true>), grid, block, 0, (hipStream_t)stream, b, c, t, g);
   else if (c.w)
-    hipLaunchKernelGGL((decode_beam_kernel<true, false>), grid, block, 0, (hipStream_t)stream, b, c, t);
+    hipLaunchKernelGGL((decode_beam_kernel<true, false>), grid, block, 0, (hipStream_t)stream, b, c, t, g);
   else if (terms)
-    hipLaunchKernelGGL((decode_beam_kernel<false, true>), grid, block, 0, (hipStream_t)stream, b, c, t);
+    hipLaunchKernelGGL((decode_beam_kernel<false, true>), grid, block, 0, (hipStream_t)stream, b, c, t, g);
   else
-    hipLaunchKernelGGL((decode_beam_kernel<false, false>), grid, block, 0, (hipStream_t)stream, b, c, t);
+    hipLaunchKernelGGL((decode_beam_kernel<false, false>), grid, block, 0, (hipStream_t)stream, b, c, t, g);
   SSASR_LAUNCH_CHECK();
   return SSASR_OK;
 }
 
 }  // namespace
+
+extern "C" int64_t ssasr_decode_beam_graph_ws_bytes(int64_t N, int64_t K, int64_t T, int64_t E, int64_t A, int64_t D,
+                                                    int64_t V, int64_t Hl, int64_t S, int32_t ctc, int32_t coverage) {
+  return ssasr_decode_beam_ex_ws_bytes(N, K, T, E, A, D, V, Hl, S, ctc, coverage);   // the graph state is in LDS
+}
+
+extern "C" int ssasr_decode_beam_graph(const ssasr_beam* dp, const ssasr_ctc_prefix* cp, const ssasr_beam_terms* tp,
+                                       const ssasr_char_graph* gp, float graph_weight, float* graph_scores,
+                                       void* stream) {
+  if (!dp || !graph_ok(gp, graph_weight, graph_scores, dp->V)) return SSASR_EARG;
+  if (graph_weight == 0.f) {                        // the tables are unread: ssasr_decode_beam_ex's launch, and G = 0
+    if (const int rc = launch_beam(dp, cp, tp, stream)) return rc;
+    SSASR_HIP(hipMemsetAsync(graph_scores, 0, sizeof(float) * (size_t)(dp->N * dp->K), (hipStream_t)stream));
+    return SSASR_OK;
+  }
+  return launch_beam(dp, cp, tp, stream,
+                     GraphDev{gp->next, gp->arc, gp->fin, gp->S, gp->start, graph_weight, graph_scores});
+}
 
 extern "C" int ssasr_decode_beam(const ssasr_beam* dp, void* stream) {
   return launch_beam(dp, nullptr, nullptr, stream);

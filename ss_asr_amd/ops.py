@@ -1871,6 +1871,41 @@ def decode_beam_ex(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, be
     return outs + (n_steps,)
 
 
+def decode_beam_graph(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ctc=None, *, graph,
+                      graph_weight, length_bonus=0.0, coverage_weight=0.0, coverage_threshold=0.5, end_margin=None,
+                      ws=None, blank=CTC_BLANK):
+    """ssasr_decode_beam_graph: decode_beam_ex's search (ctc and every term optional) with a character graph
+    (char_graph.CharGraph: an n-gram LM, hotwords, their product) in every candidate's score: graph_weight *
+    arc[state][v], graph_weight * fin[state] for <EOS>, a forbidden arc never chosen (include/ssasr.h).  graph with
+    n_classes == V (None is allowed at graph_weight 0), uploaded to feat's device on first use and held there;
+    graph_weight finite and >= 0.  -> decode_beam_ex's five results and graph_scores [N, K] float32, each hypothesis'
+    G (+ fin when <EOS> ended it).  ws: at least ssasr_decode_beam_graph_ws_bytes bytes, or None to allocate one."""
+    from .char_graph import CharGraph
+    graph_weight = float(graph_weight)
+    if not (math.isfinite(graph_weight) and graph_weight >= 0.0):
+        raise ValueError('decode_beam_graph: graph_weight must be finite and >= 0, got %r' % (graph_weight,))
+    if graph is None and graph_weight != 0.0:
+        raise ValueError('decode_beam_graph: graph_weight %g needs a graph' % graph_weight)
+    if graph is not None and not isinstance(graph, CharGraph):
+        raise TypeError('decode_beam_graph: graph must be a char_graph.CharGraph, got %s' % type(graph).__name__)
+    V = params['w_ct'].shape[0]
+    if graph is not None and graph.n_classes != V:
+        raise ValueError('decode_beam_graph: the graph has %d classes, the model %d' % (graph.n_classes, V))
+    d, outs, keep = beam_struct(feat, enc_len, params, psi, lm, lm_weight, eos, max_steps, beam_size, ws,
+                                ctc=ctc is not None, coverage=float(coverage_weight) != 0.0)
+    dev = outs[0].device
+    n_steps = torch.empty(d.N, device=dev, dtype=torch.int32)
+    graph_scores = torch.empty(d.N, d.K, device=dev, dtype=torch.float32)
+    t = _lib.BeamTerms(float(length_bonus), float(coverage_weight), float(coverage_threshold),
+                       -1.0 if end_margin is None else float(end_margin), n_steps.data_ptr())
+    c, c_keep = ctc_prefix_struct(ctc, blank) if ctc is not None else (None, None)
+    g, g_keep = graph.to(dev) if graph is not None else (None, None)
+    check(_lib.load().ssasr_decode_beam_graph(C.byref(d), C.byref(c) if c is not None else None, C.byref(t),
+                                              C.byref(g) if g is not None else None, graph_weight,
+                                              _p(graph_scores), _stream()), 'ssasr_decode_beam_graph')
+    return outs + (n_steps, graph_scores)
+
+
 # ---------------------------------------------------------------------------
 # CharLM training: one chunk forward / backward (csrc/charlm_train.hip)
 # ---------------------------------------------------------------------------

@@ -653,6 +653,13 @@ class ASRTester(Solver):
     asr.decode_end_margin (absent: off) are the beam search's length bonus, coverage term and end detection
     (ssasr_decode_beam_ex, any beam size); `decode_file` gains `_lb<bonus>`, `_cov<weight>`, `_end<margin>` for the
     terms that are on.
+    asr.decode_hotwords (a list of strings) with asr.decode_hotword_bonus (>= 0, absent: 1.0) and asr.decode_ngram_lm
+    (the path of a char_graph.CharGraph.save file) with asr.decode_ngram_weight (>= 0, absent: 0.5) put a character
+    graph INSIDE the attention beam search (ASR.decode_many(graph=..., graph_weight=...), ssasr_decode_beam_graph, any
+    beam size; no ctc_head needed): contextual biasing towards the phrases, a count-based n-gram LM, or with both
+    their product, built and validated in set_model as asr.decode_ctc_only's graph keys are; `decode_file` gains
+    `_hw<n>x<bonus>` / `_ng<weight>` only when a key is present.  Together with asr.decode_ctc_only, which has its own
+    graph keys, they are an error.
     asr.decode_align: true (absent: off; needs 'ctc_weight' in asr.mdl, else set_model raises): after each group is
     decoded its hypotheses are force-aligned to the group's encoder outputs (ASR.align, ssasr_ctc_align); exec()
     still returns the strings, `last_alignments` holds one asr.Alignment per utterance in index order, and
@@ -790,35 +797,55 @@ class ASRTester(Solver):
     GRAPH_KEYS = ('hotwords', 'hotword_bonus', 'ngram_lm', 'ngram_weight')
 
     @staticmethod
-    def ctc_only_graph(asr_config):
-        """The character-graph keys of asr.decode_ctc_only, validated: None when none of them is present, else
-        {'hotwords': [strings] or None, 'hotword_bonus': float, 'ngram_lm': path or None, 'ngram_weight': float}."""
+    def _graph_keys(conf, name):
+        """The four character-graph keys of the mapping conf, validated (name(key): what an error calls the key): None
+        when none of them is present, else {'hotwords': [strings] or None, 'hotword_bonus': float, 'ngram_lm': path or
+        None, 'ngram_weight': float}."""
         import math
-        beam = ASRTester.ctc_only_beam(asr_config)
-        conf = asr_config.get('decode_ctc_only')
-        conf = conf if isinstance(conf, dict) else {}
         if not set(conf) & set(ASRTester.GRAPH_KEYS):
             return None
         words, path = conf.get('hotwords'), conf.get('ngram_lm')
         if words is None and path is None:
-            raise ValueError('asr.decode_ctc_only: hotword_bonus / ngram_weight need hotwords / ngram_lm, got {!r}'
-                             .format(conf))
+            raise ValueError('{} / {} need {} / {}, got {!r}'.format(
+                name('hotword_bonus'), name('ngram_weight'), name('hotwords'), name('ngram_lm'), conf))
         if words is not None and (not isinstance(words, (list, tuple)) or not words or
                                   any(not isinstance(w, str) or not w for w in words)):
-            raise ValueError('asr.decode_ctc_only.hotwords must be a non-empty list of non-empty strings, got {!r}'
-                             .format(words))
+            raise ValueError('{} must be a non-empty list of non-empty strings, got {!r}'.format(name('hotwords'), words))
         if path is not None and (not isinstance(path, str) or not path):
-            raise ValueError('asr.decode_ctc_only.ngram_lm must be the path of a CharGraph.save file, got {!r}'
-                             .format(path))
+            raise ValueError('{} must be the path of a CharGraph.save file, got {!r}'.format(name('ngram_lm'), path))
         out = {'hotwords': list(words) if words is not None else None, 'ngram_lm': path}
         for key, default, need in (('hotword_bonus', 1.0, words), ('ngram_weight', 0.5, path)):
             v = conf.get(key, default)
             if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
-                raise ValueError('asr.decode_ctc_only.{} must be a finite number >= 0, got {!r}'.format(key, v))
+                raise ValueError('{} must be a finite number >= 0, got {!r}'.format(name(key), v))
             if key in conf and need is None:
-                raise ValueError('asr.decode_ctc_only.{} needs asr.decode_ctc_only.{}'.format(
-                    key, 'hotwords' if key == 'hotword_bonus' else 'ngram_lm'))
+                raise ValueError('{} needs {}'.format(name(key), name('hotwords' if key == 'hotword_bonus' else 'ngram_lm')))
             out[key] = float(v)
+        return out
+
+    @staticmethod
+    def beam_graph(asr_config):
+        """The attention search's character-graph keys asr.decode_hotwords, asr.decode_hotword_bonus,
+        asr.decode_ngram_lm and asr.decode_ngram_weight, validated as ctc_only_graph validates its own: None when none
+        of them is present."""
+        conf = {k: asr_config['decode_' + k] for k in ASRTester.GRAPH_KEYS if 'decode_' + k in asr_config}
+        out = ASRTester._graph_keys(conf, 'asr.decode_{}'.format)
+        if out is not None and asr_config.get('decode_ctc_only') not in (None, False):
+            raise ValueError('asr.decode_{} with asr.decode_ctc_only: that mapping has its own graph keys '
+                             '(asr.decode_ctc_only.hotwords, .ngram_lm); the attention beam search does not run'
+                             .format(' / asr.decode_'.join(sorted(conf))))
+        return out
+
+    @staticmethod
+    def ctc_only_graph(asr_config):
+        """The character-graph keys of asr.decode_ctc_only, validated: None when none of them is present, else
+        {'hotwords': [strings] or None, 'hotword_bonus': float, 'ngram_lm': path or None, 'ngram_weight': float}."""
+        beam = ASRTester.ctc_only_beam(asr_config)
+        conf = asr_config.get('decode_ctc_only')
+        conf = conf if isinstance(conf, dict) else {}
+        out = ASRTester._graph_keys(conf, 'asr.decode_ctc_only.{}'.format)
+        if out is None:
+            return None
         if beam == 0:
             raise ValueError('asr.decode_ctc_only: beam_size 0, the best path, has no graph term; got {!r}'.format(conf))
         if asr_config.get('decode_rescore') not in (None, False):
@@ -829,24 +856,24 @@ class ASRTester(Solver):
                              'not built; give one of them')
         return out
 
-    def build_ctc_graph(self, conf):
-        """(CharGraph, graph_weight) of ctc_only_graph's keys: the hotwords' graph at weight 1, the n-gram graph at
-        ngram_weight, or the product of the two, each factor pre-scaled, at weight 1."""
+    def build_ctc_graph(self, conf, name='asr.decode_ctc_only.{}'.format):
+        """(CharGraph, graph_weight) of ctc_only_graph's (or, with its name(key), beam_graph's) keys: the hotwords'
+        graph at weight 1, the n-gram graph at ngram_weight, or the product of the two, each factor pre-scaled, at
+        weight 1."""
         from .char_graph import CharGraph
         V, hot, lm = self.mapper.get_dim(), None, None
         if conf['hotwords'] is not None:
             try:
                 phrases = [[self.mapper.char_to_ind(ch) for ch in w] for w in conf['hotwords']]
             except KeyError as e:
-                raise ValueError('asr.decode_ctc_only.hotwords: {!r} is no character of the model'.format(e.args[0]))
+                raise ValueError('{}: {!r} is no character of the model'.format(name('hotwords'), e.args[0]))
             hot = CharGraph.hotwords(phrases, conf['hotword_bonus'], V, ops.CTC_BLANK)
         if conf['ngram_lm'] is not None:
             if not os.path.isfile(conf['ngram_lm']):
-                raise ValueError('asr.decode_ctc_only.ngram_lm: no file {!r}'.format(conf['ngram_lm']))
+                raise ValueError('{}: no file {!r}'.format(name('ngram_lm'), conf['ngram_lm']))
             lm = CharGraph.load(conf['ngram_lm'])
             if lm.n_classes != V:
-                raise ValueError('asr.decode_ctc_only.ngram_lm: the graph has {} classes, the model {}'
-                                 .format(lm.n_classes, V))
+                raise ValueError('{}: the graph has {} classes, the model {}'.format(name('ngram_lm'), lm.n_classes, V))
         if hot is not None and lm is not None:
             return CharGraph.product(lm.scaled(conf['ngram_weight']), hot), 1.0
         return (hot, 1.0) if hot is not None else (lm, conf['ngram_weight'])
@@ -897,6 +924,9 @@ class ASRTester(Solver):
         self.decode_ctc_lm = self.ctc_only_lm(self.config['asr'])
         graph_conf = self.ctc_only_graph(self.config['asr'])
         self.decode_ctc_graph = None if graph_conf is None else self.build_ctc_graph(graph_conf)
+        beam_graph_conf = self.beam_graph(self.config['asr'])
+        self.decode_beam_graph = None if beam_graph_conf is None else self.build_ctc_graph(
+            beam_graph_conf, 'asr.decode_{}'.format)
         if self.decode_ctc_only is not None:
             if 'ctc_weight' not in self.config['asr']['mdl']:
                 raise ValueError('asr.decode_ctc_only needs a model with a ctc_head: set asr.mdl.ctc_weight '
@@ -946,6 +976,11 @@ class ASRTester(Solver):
                     self.decode_file += '_clb{:}'.format(self.decode_ctc_lm['length_bonus'])
         if self.decode_rescore is not None:
             self.decode_file += '_rescore{:}'.format(self.decode_rescore['ctc_weight'])
+        if beam_graph_conf is not None:
+            if beam_graph_conf['hotwords'] is not None:
+                self.decode_file += '_hw{:}x{:}'.format(len(beam_graph_conf['hotwords']), beam_graph_conf['hotword_bonus'])
+            if beam_graph_conf['ngram_lm'] is not None:
+                self.decode_file += '_ng{:}'.format(beam_graph_conf['ngram_weight'])
         self.decode_term_args, suffix = self.decode_terms(self.config['asr'])
         self.decode_file += suffix
         if self.decode_align:
@@ -965,13 +1000,18 @@ class ASRTester(Solver):
         if isinstance(ctc_weight, bool) or not isinstance(ctc_weight, (int, float)) or not 0 <= ctc_weight <= 1:
             raise ValueError('asr.decode_ctc_weight must be a number in [0, 1], got {!r}'.format(ctc_weight))
         terms = self.decode_term_args
+        if self.decode_beam_graph is not None:       # the attention search's character graph: two more keywords
+            terms = dict(terms, graph=self.decode_beam_graph[0], graph_weight=self.decode_beam_graph[1])
         ctc_only = self.decode_ctc_only
         self.verbose('Start decoding ({}{}{})'.format(
             ('CTC only, ' + ('prefix beam search, beam size {}'.format(ctc_only) if ctc_only else 'best path'))
             if ctc_only is not None else
             'beam search, beam size {}'.format(beam) if beam > 1 else 'greedy, beam size 1',
             ', joint CTC / attention scores, CTC weight {}'.format(ctc_weight) if ctc_weight > 0 else '',
-            ''.join(', {} {}'.format(k.replace('_', ' '), v) for k, v in terms.items())))
+            ''.join(', {} {}'.format(k.replace('_', ' '), v) for k, v in self.decode_term_args.items()) +
+            (', character graph of {} states at weight {}'.format(self.decode_beam_graph[0].n_states,
+                                                                  self.decode_beam_graph[1])
+             if self.decode_beam_graph is not None else '')))
         self.verbose('Number of utts to decode : {}, {} per launch.'.format(len(self.test_set), self.decode_group))
         results, xs, x_lens, ys = [], [], [], []
         if self.decode_align:

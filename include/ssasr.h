@@ -30,7 +30,8 @@
  * search -- ssasr_beam_terms, ssasr_decode_beam_ex_ws_bytes, ssasr_decode_beam_ex; a character graph in the beam search --
  * ssasr_decode_beam_graph_ws_bytes, ssasr_decode_beam_graph; SpecAugment in batch assembly and label smoothing in the
  * masked CE -- ssasr_specaug, ssasr_gather_batch_aug, ssasr_specaug_plan, ssasr_ce_loss_ls_fwd, ssasr_ce_loss_ls_bwd; CTC forced
- * alignment -- ssasr_ctc_align_ws_bytes, ssasr_ctc_align; CTC-only decoding -- ssasr_ctc_decode_ws_bytes, ssasr_ctc_decode; edit-distance scoring -- ssasr_edit_score; MWER training --
+ * alignment -- ssasr_ctc_align_ws_bytes, ssasr_ctc_align; CTC segmentation -- ssasr_ctc_segment_ws_bytes,
+ * ssasr_ctc_segment_form, ssasr_ctc_segment; CTC-only decoding -- ssasr_ctc_decode_ws_bytes, ssasr_ctc_decode; edit-distance scoring -- ssasr_edit_score; MWER training --
  * ssasr_mwer_ws_bytes, ssasr_mwer_loss_fwd, ssasr_mwer_loss_bwd, ssasr_mwer_pack, ssasr_rows_repeat_fwd, ssasr_rows_repeat_bwd; sampled
  * decoding -- ssasr_sample, ssasr_decode_sample_ws_bytes, ssasr_decode_sample, ssasr_mwer_loss_fwd_ex; minimum-Bayes-risk
  * selection -- ssasr_mbr_select.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
@@ -465,6 +466,57 @@ int ssasr_ctc_align(const float* logits, const int32_t* frame_lens, const int32_
                     const int32_t* label_lens, int64_t B, int64_t T, int64_t V, int64_t Lmax, int blank,
                     void* ws, int64_t ws_bytes, int32_t* path, int32_t* first, int32_t* last,
                     float* char_logp, double* score, void* stream);
+
+/* ---- CTC segmentation (added under ABI 16) -----------------------------------------------------------------------
+ * BUILD-DEFINED: the reference has no CTC.  CTC segmentation (Kuerzinger et al. 2020) of a long recording with a
+ * running transcript: where inside the recording the text was spoken, where each of its utterances starts and ends,
+ * and how confident the head is of each.  It is ssasr_ctc_align's lattice with two differences: it runs on
+ * NORMALISED values, and both of its ends are free.
+ * logits [B][T][V], frame_lens, y, y_ld, label_lens, Lmax and blank are what ssasr_ctc_align takes; y holds the WHOLE
+ * text of recording b, its utterances concatenated.  utt_ends int32 [B][utt_ld] holds, for utterance n < n_utts[b],
+ * the exclusive end of its labels in y: strictly increasing, the first >= 1, the last == label_lens[b].
+ *   Lattice, per recording: len = min(frame_lens[b], T), L = label_lens[b], S = 2 L + 1 states, lab_s and the skip
+ *   rule as in ssasr_ctc_align.  It is held in double and runs on lp[t][v] = (double)logit[t][v] - lse_t, lse_t =
+ *   (double)max + (double)logf(sum expf(x - max)) as ssasr_ctc_align forms it -- paths no longer visit the same
+ *   frames, so the normaliser does change which path wins.  For every frame t < len and state s:
+ *     d[t][s] = best(d[t-1][s], d[t-1][s-1], d[t-1][s-2] if the skip is allowed, 0 if s < 2) + lp[t][lab_s]
+ *   with d[-1][.] = -inf.  The 0 is the free start: a path may begin at any frame, in state 0 or 1, and the frames
+ *   before it are not scored.
+ *   Tie rule: the larger value wins; among equal values staying (s) wins, then s - 1, then s - 2, then the start.
+ *   Free end: score = max over t < len and s in {S - 1, S - 2} of d[t][s]; among equal values the earliest frame
+ *   wins, then S - 1 over S - 2.  Frames after the end are not scored.
+ *   Exactness: the lattice's operations are double adds and comparisons in frame order, as in ssasr_ctc_align, but
+ *   lse_t is formed in float, and here it is not common to all paths: a float64 restatement on float64 log-softmax
+ *   values agrees on the path only where its decisions are clear (tests compare the cases whose smallest margin on
+ *   the returned path is >= 1e-3).
+ *   Outputs: path[b][t] = the state of every scored frame, -1 for the frames before the start, after the end and
+ *   from len on; first / last / char_logp [B][Lmax] as in ssasr_ctc_align (frames of the recording); score[b]
+ *   (double) as above; utt_first[b][n] = first of utterance n's first label, utt_last[b][n] = last of its last
+ *   label; utt_conf[b][n] (float) = Kuerzinger's min-mean: q_t = lp[t][lab(path[t])] over the frames utt_first ..
+ *   utt_last, cut into consecutive blocks of `window` frames (the last may be shorter), each block's mean summed in
+ *   double in frame order, the minimum over the blocks.  Slots n >= n_utts[b] get -1, -1 and 0.
+ *   No segmentation (len < 1, L < 1, L > Lmax, n_utts[b] outside 1 .. Nmax, malformed utt_ends, or no finite end,
+ *   i.e. len < L + the number of adjacent equal labels): score = -inf, every index -1, char_logp and utt_conf 0.
+ *   Nothing is left unwritten.
+ * Accepted: 1 <= Lmax, 2 * Lmax + 1 <= 16384, 1 <= T <= 32768, 2 <= V <= 1024, 1 <= B <= 65535, 1 <= Nmax <= Lmax,
+ * window >= 1, 0 <= blank < V, y_ld >= Lmax, utt_ld >= Nmax, every pointer non-NULL, ws 8-byte aligned with ws_bytes
+ * >= ssasr_ctc_segment_ws_bytes(...) (0: no kernel for the shape).  Argument errors return before any HIP call.
+ * utt_ends lives on the device: the kernel checks it per recording and writes the no-segmentation outputs.
+ * One launch, one workgroup per recording; a thread owns P consecutive states in registers.
+ * ssasr_ctc_segment_form returns the launch form that serves (T, Lmax) -- 0 .. 6: 256 / 512 / 1024 threads x 1 state
+ * up to 2 Lmax + 1 = 256 / 512 / 1024, 256 / 512 / 1024 threads x 8 states up to 2048 / 4096 / 8192, 1024 threads x 16
+ * states up to 16384 -- and its threads and states per thread through the two pointers (either may be NULL); -1 when
+ * no form does.  Every form gives the same bits.  The workspace holds the normalisers and the path's q_t [B][T]
+ * (double each), the back-pointers (two bits per state and frame, 16 bytes per 64 states: 4 KB per frame and 128 MB
+ * per recording at the limits), and in its last 4 x B 64-bit words each recording's wall_clock64 at the start, before
+ * and after the traceback and at the end (tools/segment_time.py); four zeros for a recording without a segmentation. */
+int64_t ssasr_ctc_segment_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t Lmax, int64_t Nmax);
+int ssasr_ctc_segment_form(int64_t T, int64_t Lmax, int* threads, int* states_per_thread);
+int ssasr_ctc_segment(const float* logits, const int32_t* frame_lens, const int32_t* y, int64_t y_ld,
+                      const int32_t* label_lens, const int32_t* utt_ends, int64_t utt_ld, const int32_t* n_utts,
+                      int64_t B, int64_t T, int64_t V, int64_t Lmax, int64_t Nmax, int64_t window, int blank,
+                      void* ws, int64_t ws_bytes, int32_t* path, int32_t* first, int32_t* last, float* char_logp,
+                      double* score, int32_t* utt_first, int32_t* utt_last, float* utt_conf, void* stream);
 
 /* ---- CTC-only decoding (added under ABI 16) ----------------------------------------------------------------------
  * BUILD-DEFINED: the reference has no CTC.  A transcript from the head's posteriors alone, with no Speller step: the

@@ -152,6 +152,10 @@ SIGNATURES = {
     'ssasr_ctc_loss_bwd': (I32, [P, P, P, I64, P, I64, I64, I64, I64, I32, P, P, P, P, P]),
     'ssasr_ctc_align_ws_bytes': (I64, [I64, I64, I64, I64]),
     'ssasr_ctc_align': (I32, [P, P, P, I64, P, I64, I64, I64, I64, I32, P, I64, P, P, P, P, P, P]),
+    'ssasr_ctc_segment_ws_bytes': (I64, [I64, I64, I64, I64, I64]),
+    'ssasr_ctc_segment_form': (I32, [I64, I64, P, P]),
+    'ssasr_ctc_segment': (I32, [P, P, P, I64, P, P, I64, P, I64, I64, I64, I64, I64, I64, I32, P, I64, P, P, P, P, P, P,
+                                P, P, P]),
     'ssasr_ctc_decode_ws_bytes': (I64, [I64, I64, I64, I64]),
     'ssasr_ctc_decode': (I32, [P, P, I64, I64, I64, I64, I32, P, I64, P, P, P, P, P]),
     'ssasr_ctc_decode_lm_ws_bytes': (I64, [I64, I64, I64, I64, I64]),

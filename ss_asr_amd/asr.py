@@ -38,6 +38,14 @@ ENCODER_STRIDE = 8      # input frames per encoder frame: three pBLSTM layers, e
 # frame_shift), or None when no alignment fits.
 Alignment = collections.namedtuple('Alignment', ('score', 'chars'))
 
+# ASR.segment's result for one recording (BUILD-DEFINED).  score: log-probability of the best CTC path of the whole
+# text inside the recording (float, -inf when nothing fits); span: (start, end exclusive) of the text in input frames
+# (seconds with frame_shift); utterances: [Segment(text, start, end, confidence)], confidence the min-mean of the path's
+# log-probabilities over blocks of `window` encoder frames; chars as in Alignment.  span, utterances and chars are None
+# when nothing fits.
+Segmentation = collections.namedtuple('Segmentation', ('score', 'span', 'utterances', 'chars'))
+Segment = collections.namedtuple('Segment', ('text', 'start', 'end', 'confidence'))
+
 # ASR.score's result for one utterance (BUILD-DEFINED).  chars, words: (S, D, I, N) of the best hypothesis against
 # the reference, N the reference's count; oracle: (k, chars, words) of the n-best entry with the fewest word errors
 # (ties: fewest character errors, then lowest k), the best entry itself for a greedy decode.
@@ -295,6 +303,7 @@ class ASR(nn.Module):
         # align's device results: (path [N, T'], first [N, Lmax], last [N, Lmax], char_logp [N, Lmax], score [N] double,
         # logits [N, T', V])
         self.last_align = None
+        self.last_segment = None
         # what the most recent decode_many / decode_nbest call left to score(): (chars [N, K, steps] int32,
         # n_chars [N, K] int32, n_hyps [N] int32), views of last_decode (K = 1) or last_beam
         self.last_hyps = None
@@ -533,6 +542,95 @@ class ASR(nn.Module):
             n = int(x_lens[i][0])
             out.append(Alignment(score[i], [(c,) + input_span(first[i][j], last[i][j], n, frame_shift) + (char_logp[i][j],)
                                             for j, c in enumerate(text)]))
+        return out
+
+    def segment(self, xs, x_lens, texts, mapper, *, window=30, frame_shift=None, encoded=None):
+        """BUILD-DEFINED: CTC segmentation of recording i (xs, x_lens as align takes them) with the running transcript
+        texts[i], the LIST of its utterance strings, on a model with a ctc_head: where inside the recording the text
+        was spoken and where each utterance starts and ends (ssasr_ctc_segment, include/ssasr.h: align's lattice on
+        normalised values, with a free start and a free end, so audio before, after and beyond the text is left
+        out).  `<` and `>` are stripped as in align; an unknown character or an empty utterance is a ValueError.  Each
+        recording is encoded alone and whole (_encode_packed; at most ops.CTC_SEGMENT_MAX_FRAMES encoder frames and
+        ops.CTC_SEGMENT_MAX_LABELS characters per recording -- encoding in chunks is not done here), then ONE launch
+        serves the group.  encoded: as in align.  window: the confidence's block length in encoder frames.
+        Returns one Segmentation(score, span, utterances, chars) per recording, spans in INPUT frames through
+        input_span (seconds when frame_shift is given); utterances is None and score -inf when nothing fits.
+        last_segment keeps (path, first, last, char_logp, score, utt_first, utt_last, utt_conf, logits) on the device,
+        in encoder frames."""
+        head = getattr(self, 'ctc_head', None)
+        if head is None:
+            raise ValueError(self._NO_CTC_HEAD % type(self).__name__)
+        if not len(xs) == len(x_lens) == len(texts):
+            raise ValueError('segment: %d recordings, %d lengths, %d texts' % (len(xs), len(x_lens), len(texts)))
+        if not len(texts):
+            raise ValueError('segment: no recording')
+        if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+            raise ValueError('segment: window must be an integer >= 1, got %r' % (window,))
+        clean, labels, ends = [], [], []
+        for utts in texts:
+            if isinstance(utts, str) or not len(utts):
+                raise ValueError('segment: a recording\'s text is the non-empty list of its utterances, got %r' % (utts,))
+            utts = [u.replace(SOS_TKN, '').replace(EOS_TKN, '') for u in utts]
+            row, row_ends = [], []
+            for u in utts:
+                if not u:
+                    raise ValueError('segment: an utterance is empty')
+                try:
+                    row.extend(int(mapper.char_to_ind(c)) for c in u)
+                except (KeyError, ValueError):
+                    raise ValueError('segment: %r has a character the mapper does not know' % (u,)) from None
+                row_ends.append(len(row))
+            if len(row) > ops.CTC_SEGMENT_MAX_LABELS:
+                raise ValueError('segment: a text of %d characters; the kernel takes at most %d'
+                                 % (len(row), ops.CTC_SEGMENT_MAX_LABELS))
+            clean.append(utts)
+            labels.append(row)
+            ends.append(row_ends)
+        lmax, nmax = max(len(row) for row in labels), max(len(row) for row in ends)
+        with torch.no_grad():
+            if encoded is None:
+                for x_len in x_lens:
+                    if -(-int(x_len[0]) // ENCODER_STRIDE) > ops.CTC_SEGMENT_MAX_FRAMES:
+                        raise ValueError('segment: a recording of %d input frames; the kernel takes at most %d encoder '
+                                         'frames (%d input frames)' % (int(x_len[0]), ops.CTC_SEGMENT_MAX_FRAMES,
+                                                                       ops.CTC_SEGMENT_MAX_FRAMES * ENCODER_STRIDE))
+                try:
+                    encoded = self._encode_packed(xs, x_lens)
+                except ValueError as err:                      # what ops raise for a shape that has no kernel
+                    raise ValueError('segment: encoding failed for recordings of up to %d input frames (the '
+                                     'segmentation kernel takes %d; a recording is encoded whole, not in chunks): %s'
+                                     % (max(int(l[0]) for l in x_lens), ops.CTC_SEGMENT_MAX_FRAMES * ENCODER_STRIDE,
+                                        err)) from err
+            packed, enc_lens = encoded
+            if packed.shape[0] != len(texts):
+                raise ValueError('segment: the encoded group holds %d recordings, not %d' % (packed.shape[0], len(texts)))
+            y = torch.zeros(len(labels), lmax, dtype=torch.int32)
+            ue = torch.zeros(len(labels), nmax, dtype=torch.int32)
+            for i, (row, row_ends) in enumerate(zip(labels, ends)):
+                y[i, :len(row)] = torch.tensor(row, dtype=torch.int32)
+                ue[i, :len(row_ends)] = torch.tensor(row_ends, dtype=torch.int32)
+            dev = packed.device
+            self.last_segment = ops.ctc_head_segment(packed, head.weight, head.bias, enc_lens, y.to(dev),
+                                                     _dev_i32([len(row) for row in labels], dev), ue.to(dev),
+                                                     _dev_i32([len(row) for row in ends], dev), lmax, nmax, window,
+                                                     ops.CTC_BLANK)
+        path, first, last, char_logp, score, utt_first, utt_last, utt_conf, _ = self.last_segment
+        path, first, last, char_logp, score, utt_first, utt_last, utt_conf = [
+            t.cpu().tolist() for t in (path, first, last, char_logp, score, utt_first, utt_last, utt_conf)]
+        out = []
+        for i, utts in enumerate(clean):
+            if score[i] == -math.inf:
+                out.append(Segmentation(score[i], None, None, None))
+                continue
+            n = int(x_lens[i][0])
+            frames = [t for t, s in enumerate(path[i]) if s >= 0]
+            text = ''.join(utts)
+            out.append(Segmentation(
+                score[i], input_span(frames[0], frames[-1], n, frame_shift),
+                [Segment(u, *(input_span(utt_first[i][k], utt_last[i][k], n, frame_shift) + (utt_conf[i][k],)))
+                 for k, u in enumerate(utts)],
+                [(c,) + input_span(first[i][j], last[i][j], n, frame_shift) + (char_logp[i][j],)
+                 for j, c in enumerate(text)]))
         return out
 
     def score(self, refs, mapper):

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libssasr_hip.so')
 SOURCES = ['gemm.hip', 'rnn.hip', 'decoder.hip', 'loss_opt.hip', 'ctc.hip', 'frontend.hip', 'seed.hip', 'sae.hip', 'infer.hip', 'charlm_train.hip',
-           'options.hip', 'score.hip', 'mwer.hip', 'mbr.hip', 'rescore.hip']
+           'options.hip', 'score.hip', 'mwer.hip', 'mbr.hip', 'rescore.hip', 'segment.hip']
 HEADERS = ['common.h', 'rnn_kernels.h', 'attn_kernels.h', 'decoder_persistent.h', 'decoder_long.h',
            'decoder_bwd_persistent.h', 'edit_dp.h', 'seq_logp.h',
            os.path.join('..', '..', 'include', 'ssasr.h')]

@@ -1033,6 +1033,68 @@ def ctc_head_align(feat, weight, bias, frame_lens, y32, label_lens, lmax, blank=
     return ctc_align(logits, frame_lens, y32, label_lens, lmax, blank) + (logits,)
 
 
+CTC_SEGMENT_MAX_LABELS = 8191   # ssasr_ctc_segment's limits (include/ssasr.h): 2 * Lmax + 1 <= 16384
+CTC_SEGMENT_MAX_FRAMES = 32768
+
+
+def ctc_segment_form(T, lmax):
+    """ssasr_ctc_segment_form: (form, threads, states per thread) of the launch that serves T frames and lmax labels;
+    None when no form does."""
+    threads, per_thread = C.c_int(0), C.c_int(0)
+    form = int(_lib.load().ssasr_ctc_segment_form(int(T), int(lmax), C.byref(threads), C.byref(per_thread)))
+    return None if form < 0 else (form, threads.value, per_thread.value)
+
+
+def ctc_segment(logits, frame_lens, y32, label_lens, utt_ends, n_utts, lmax, nmax, window, blank=0):
+    """ssasr_ctc_segment: CTC segmentation of each row's WHOLE text (its utterances concatenated in y32) inside its
+    frames, on the raw logits [B, T, V]: ctc_align's lattice on normalised values with a free start and a free end
+    (include/ssasr.h).  utt_ends int32 [B, >= nmax]: the exclusive end of each utterance's labels; n_utts int32 [B].
+    -> (path [B, T] int32, -1 outside the span; first, last [B, lmax] int32; char_logp [B, lmax] float32; score [B]
+    float64, -inf: nothing fits; utt_first, utt_last [B, nmax] int32; utt_conf [B, nmax] float32: the min-mean of the
+    path's log-probabilities over blocks of `window` frames) on the device.  No autograd."""
+    lib = _lib.load()
+    lmax, nmax, window, blank = int(lmax), int(nmax), int(window), int(blank)
+    _need_gpu(logits, frame_lens, y32, label_lens, utt_ends, n_utts)
+    logits = _f32c(logits.detach())
+    B, T, V = logits.shape
+    for name, t in (('labels', y32), ('utt_ends', utt_ends)):
+        if t.dtype != torch.int32 or t.dim() != 2 or t.stride(-1) != 1:
+            raise TypeError('ctc_segment: %s must be an int32 matrix with unit column stride' % name)
+    if lmax > y32.shape[1] or nmax > utt_ends.shape[1]:
+        raise ValueError('ctc_segment: Lmax / Nmax exceed the label / utterance matrix')
+    if window < 1:
+        raise ValueError('ctc_segment: window must be >= 1, got %d' % window)
+    need = int(lib.ssasr_ctc_segment_ws_bytes(B, T, V, lmax, nmax))
+    if need <= 0:
+        raise ValueError('ctc_segment: shape B=%d T=%d V=%d Lmax=%d Nmax=%d has no kernel (at most %d frames and %d '
+                         'labels)' % (B, T, V, lmax, nmax, CTC_SEGMENT_MAX_FRAMES, CTC_SEGMENT_MAX_LABELS))
+    dev = logits.device
+    ws = torch.empty(need // 8, device=dev, dtype=torch.float64)
+    path = torch.empty(B, T, device=dev, dtype=torch.int32)
+    first = torch.empty(B, lmax, device=dev, dtype=torch.int32)
+    last = torch.empty(B, lmax, device=dev, dtype=torch.int32)
+    char_logp = torch.empty(B, lmax, device=dev, dtype=torch.float32)
+    score = torch.empty(B, device=dev, dtype=torch.float64)
+    utt_first = torch.empty(B, nmax, device=dev, dtype=torch.int32)
+    utt_last = torch.empty(B, nmax, device=dev, dtype=torch.int32)
+    utt_conf = torch.empty(B, nmax, device=dev, dtype=torch.float32)
+    check(lib.ssasr_ctc_segment(_p(logits), _p(frame_lens), _p(y32), y32.stride(0), _p(label_lens), _p(utt_ends),
+                                utt_ends.stride(0), _p(n_utts), B, T, V, lmax, nmax, window, blank, _p(ws), need,
+                                _p(path), _p(first), _p(last), _p(char_logp), _p(score), _p(utt_first), _p(utt_last),
+                                _p(utt_conf), _stream()), 'ssasr_ctc_segment')
+    return path, first, last, char_logp, score, utt_first, utt_last, utt_conf
+
+
+def ctc_head_segment(feat, weight, bias, frame_lens, y32, label_lens, utt_ends, n_utts, lmax, nmax, window, blank=0):
+    """ctc_segment on the head's logits, the product issued exactly as the training node issues it (_CTCHead.forward).
+    -> ctc_segment's eight tensors and the logits [B, T, V] they were computed on.  No autograd."""
+    _need_gpu(feat, weight, bias)
+    feat, w, b = _f32c(feat.detach()), _f32c(weight.detach()), _f32c(bias.detach())
+    B, T, E = feat.shape
+    logits = gemm(feat.view(B * T, E), w, bias=b).view(B, T, w.shape[0])
+    return ctc_segment(logits, frame_lens, y32, label_lens, utt_ends, n_utts, lmax, nmax, window, blank) + (logits,)
+
+
 CTC_DECODE_MAX_BEAM = 32       # ssasr_ctc_decode's limits (include/ssasr.h)
 CTC_DECODE_MAX_FRAMES = 4096
 

@@ -552,6 +552,122 @@ def ctc_prefix_beam_graph_reference(lp, K, graph, graph_weight=0.0, length_bonus
     return [(e[0], e[1]) for e in out], gap
 
 
+def _segment_frame(dp, lp_t, lab, pen, neg, zero):
+    """One frame of ctc_segment_reference's lattice.  dp [S + 2]: the values of the frame before behind two -inf
+    pads; pen [S]: 0 where the skip is allowed, -inf elsewhere.  -> (the new padded values, the back-pointer codes
+    0 stay / 1 s - 1 / 2 s - 2 / 3 start)."""
+    d, one, two = dp[2:], dp[1:-1], dp[:-2] + pen
+    m1 = one > d                                                # stay wins a tie, then s - 1, then s - 2, then the start
+    best = np.where(m1, one, d)
+    m2 = two > best
+    best = np.where(m2, two, best)
+    code = m1.astype(np.int8)
+    code[m2] = 2
+    for s in range(min(d.shape[0], 2)):
+        if zero > best[s]:
+            best[s], code[s] = zero, 3
+    out = np.empty_like(dp)
+    out[:2] = neg
+    np.add(best, lp_t[lab], out=out[2:])
+    return out, code
+
+
+def _segment_margin(dp, s, pen, neg, zero):
+    """The margin of state s's decision on the padded values dp of the frame before: the winner minus the best
+    loser."""
+    cand = sorted(float(c) for c in (dp[s + 2], dp[s + 1], dp[s] + pen[s], zero if s < 2 else neg))
+    return math.inf if cand[-2] == -math.inf else cand[-1] - cand[-2]
+
+
+def ctc_segment_reference(lp, y, utt_ends, window, blank=0, dtype=np.float64):
+    """BUILD-DEFINED: CTC segmentation, ssasr_ctc_segment (include/ssasr.h) restated in numpy -- what the kernel is
+    defined and tested against.  lp [T, V]: one recording's NORMALISED log-probabilities, already cut to its frames;
+    y: the whole text's labels; utt_ends: each utterance's exclusive end in y; every sum runs in `dtype` (float64;
+    float32 measures the arithmetic's noise).  The same operations in the same order as the header states them,
+    vectorised over the states of a frame:
+      d[t][s] = best(d[t-1][s], d[t-1][s-1], d[t-1][s-2] if the skip is allowed, 0 if s < 2) + lp[t][lab_s]
+    the larger value wins, among equals stay, then s - 1, then s - 2, then the start; the end is the largest d[t][s]
+    over every frame and s in {S - 1, S - 2}, among equals the earliest frame, then S - 1.
+    -> None when nothing can be segmented (no frame, no label, malformed utt_ends, no finite end), else a namespace of
+    score, path [T] (-1 outside the span), first / last / char_logp [L], utt_first / utt_last / utt_conf [N] and gap:
+    the smallest difference between the winner and the best loser over the decisions ON the returned path (each
+    frame's choice among stay / s - 1 / s - 2 / start) and the end choice -- below it a rounding can change the path.
+    The lattice is run twice, the second time to read the margins along the path, so that no [T, S] table of values
+    is kept."""
+    import types
+    lp = np.asarray(lp).astype(dtype)
+    if lp.ndim != 2:
+        raise ValueError('ctc_segment_reference: lp must be [T, V], got %r' % (lp.shape,))
+    window, blank = int(window), int(blank)
+    if window < 1:
+        raise ValueError('ctc_segment_reference: window must be >= 1, got %d' % window)
+    y, ends = [int(c) for c in y], [int(e) for e in utt_ends]
+    T, L = lp.shape[0], len(y)
+    if T < 1 or L < 1 or not ends or ends[-1] != L or any(b <= a for a, b in zip([0] + ends, ends)):
+        return None
+    neg, zero = dtype(-np.inf), dtype(0)
+    S = 2 * L + 1
+    lab = np.full(S, blank, dtype=np.int64)
+    lab[1::2] = y
+    skip = np.zeros(S, dtype=bool)
+    skip[3::2] = lab[3::2] != lab[1:-2:2]
+    pen = np.where(skip, zero, neg).astype(dtype)
+    back = np.zeros((T, S), dtype=np.int8)
+    dp = np.full(S + 2, neg, dtype=dtype)
+    ends_seen = []                                              # (value, frame, state) of every end candidate
+    best_end = None
+    for t in range(T):
+        dp, back[t] = _segment_frame(dp, lp[t], lab, pen, neg, zero)
+        for s in (S - 1, S - 2):
+            v = dp[s + 2]
+            ends_seen.append(v)
+            if v > neg and (best_end is None or v > best_end[0]):         # strict: the earliest frame, then S - 1
+                best_end = (v, t, s)
+    if best_end is None:
+        return None
+    score, t_end, s = best_end
+    top = np.sort(np.asarray(ends_seen, dtype=dtype))
+    gap = float(top[-1] - top[-2]) if top[-2] > neg else math.inf
+    path = np.full(T, -1, dtype=np.int64)
+    t = t_end
+    while True:
+        path[t] = s
+        code = int(back[t, s])
+        if code == 3:
+            break
+        s -= code
+        t -= 1
+    t_start = t
+    del back
+    dp = np.full(S + 2, neg, dtype=dtype)
+    for t in range(t_end + 1):                                  # again, for the margins along the path
+        if t >= t_start:
+            gap = min(gap, _segment_margin(dp, int(path[t]), pen, neg, zero))
+        dp, _ = _segment_frame(dp, lp[t], lab, pen, neg, zero)
+    q = np.zeros(T, dtype=dtype)
+    span = np.arange(t_start, t_end + 1)
+    q[span] = lp[span, lab[path[span]]]
+
+    def total(lo, hi):                                          # q[lo .. hi] summed in frame order
+        return np.cumsum(q[lo:hi + 1], dtype=dtype)[-1]
+    first, last = np.zeros(L, dtype=np.int64), np.zeros(L, dtype=np.int64)
+    logp = np.zeros(L, dtype=dtype)
+    for j in range(L):
+        frames = np.nonzero(path == 2 * j + 1)[0]
+        first[j], last[j] = frames[0], frames[-1]
+        logp[j] = total(first[j], last[j])
+    N = len(ends)
+    utt_first = np.array([first[a] for a in [0] + ends[:-1]], dtype=np.int64)
+    utt_last = np.array([last[e - 1] for e in ends], dtype=np.int64)
+    conf = np.zeros(N, dtype=dtype)
+    for n in range(N):
+        means = [total(lo, min(lo + window - 1, utt_last[n])) / dtype(min(lo + window - 1, utt_last[n]) - lo + 1)
+                 for lo in range(utt_first[n], utt_last[n] + 1, window)]
+        conf[n] = min(means)
+    return types.SimpleNamespace(score=float(score), path=path, first=first, last=last, char_logp=logp,
+                                 utt_first=utt_first, utt_last=utt_last, utt_conf=conf, gap=gap, span=(t_start, t_end))
+
+
 class ErrorStats:
     """Corpus-level error rates: sums (S, D, I, N) rows of characters and of words; cer / wer =
     sum(S + D + I) / sum(N), nan when N == 0.  (calc_err below stays the reference's mean of per-utterance ratios.)"""

@@ -31,7 +31,7 @@
  * ssasr_decode_beam_graph_ws_bytes, ssasr_decode_beam_graph; SpecAugment in batch assembly and label smoothing in the
  * masked CE -- ssasr_specaug, ssasr_gather_batch_aug, ssasr_specaug_plan, ssasr_ce_loss_ls_fwd, ssasr_ce_loss_ls_bwd; CTC forced
  * alignment -- ssasr_ctc_align_ws_bytes, ssasr_ctc_align; CTC segmentation -- ssasr_ctc_segment_ws_bytes,
- * ssasr_ctc_segment_form, ssasr_ctc_segment; CTC-only decoding -- ssasr_ctc_decode_ws_bytes, ssasr_ctc_decode; edit-distance scoring -- ssasr_edit_score; MWER training --
+ * ssasr_ctc_segment_form, ssasr_ctc_segment, ssasr_ctc_segment_skip_ws_bytes, ssasr_ctc_segment_skip; CTC-only decoding -- ssasr_ctc_decode_ws_bytes, ssasr_ctc_decode; edit-distance scoring -- ssasr_edit_score; MWER training --
  * ssasr_mwer_ws_bytes, ssasr_mwer_loss_fwd, ssasr_mwer_loss_bwd, ssasr_mwer_pack, ssasr_rows_repeat_fwd, ssasr_rows_repeat_bwd; sampled
  * decoding -- ssasr_sample, ssasr_decode_sample_ws_bytes, ssasr_decode_sample, ssasr_mwer_loss_fwd_ex; minimum-Bayes-risk
  * selection -- ssasr_mbr_select.  16: CharLM training -- ssasr_charlm_train_ws_floats, ssasr_charlm_train_fwd, ssasr_charlm_train_bwd
@@ -517,6 +517,45 @@ int ssasr_ctc_segment(const float* logits, const int32_t* frame_lens, const int3
                       int64_t B, int64_t T, int64_t V, int64_t Lmax, int64_t Nmax, int64_t window, int blank,
                       void* ws, int64_t ws_bytes, int32_t* path, int32_t* first, int32_t* last, float* char_logp,
                       double* score, int32_t* utt_first, int32_t* utt_last, float* utt_conf, void* stream);
+
+/* ---- CTC segmentation with utterance skips and a filler (added under ABI 16) --------------------------------------
+ * BUILD-DEFINED.  ssasr_ctc_segment for transcripts that are not verbatim: an utterance that was never spoken can be
+ * passed over, and speech that nobody wrote down can be absorbed between two utterances.  Everything is
+ * ssasr_ctc_segment's -- arguments, lattice, tie rule, free start (states 0 and 1), free end (S - 1 and S - 2),
+ * outputs -- except what follows.  NOTE: skip_penalty and fill_penalty are the only HOST pointers among this entry's
+ * device pointers.  They point to one double each in host memory, read before
+ * the call returns (this ABI passes no double by value); each value is finite and <= 0, or -inf, which turns that
+ * mechanism off; with both -inf every output that ssasr_ctc_segment writes is bit-equal to its.
+ *   Junctions.  Recording b has N = n_utts[b] utterances; utterance n owns the labels [utt_ends[n-1], utt_ends[n])
+ *   with utt_ends[-1] = 0.  The junction J_n is the blank state 2 * utt_ends[n-1]: J_0 = 0, J_N = S - 1, the others
+ *   are the blanks between two utterances.
+ *   Filler.  f_t = (double)(m + logf(sum_{v != blank} expf(x_v - m))) - lse_t, m the largest logit that is not the
+ *   blank's and lse_t ssasr_ctc_segment's: the log-probability that frame t is some speech.  At a junction state,
+ *   and only there, the frame's emission is max(lp[t][blank], f_t + fill_penalty); the blank wins a tie.
+ *   Skip.  For n = 0 .. N - 1, J_{n+1} has one more predecessor: d[t-1][J_n] + skip_penalty -- the path passes over
+ *   utterance n without visiting any of its labels.  The skip consumes the frame it lands on, scored with the
+ *   junction's emission: m skipped utterances cost m frames and m penalties, there is no chain within a frame.  A
+ *   blank state has no s - 2; the skip takes that place in the tie rule: stay, s - 1, skip, start.  The free ends
+ *   stay where they are, so leading and trailing unspoken utterances are skipped through the chain and pay for it.
+ *   An utterance is aligned whole or skipped whole.
+ *   Outputs.  A skipped utterance has utt_first = utt_last = -1 and utt_conf = 0, its characters first = last = -1
+ *   and char_logp = 0.  utt_skipped int32 [B][Nmax]: 1 skipped, 0 aligned, -1 for slots >= n_utts[b] and for a
+ *   recording without a segmentation.  is_fill int32 [B][T]: 1 on a scored frame whose state is a junction and where
+ *   the filler's value won (strictly), 0 on every other scored frame, -1 outside the span.  q_t of a junction frame
+ *   is the junction's emission; no such frame lies inside an utterance's span.  No segmentation is: no finite end
+ *   (with skips a recording may be shorter than its text), or ssasr_ctc_segment's other reasons.  Nothing is left
+ *   unwritten.
+ * Accepted: what ssasr_ctc_segment accepts, with Nmax <= 1024 (the junctions' values live in LDS: 2 x (Nmax + 3) doubles, J_0 .. J_Nmax and two spare slots),
+ * both penalties <= 0 or -inf (a positive value, +inf or a NaN is an argument error), skip_penalty, fill_penalty,
+ * utt_skipped and is_fill non-NULL, ws_bytes >= ssasr_ctc_segment_skip_ws_bytes(...): ssasr_ctc_segment's workspace and one more double per
+ * frame, f_t, behind q_t.  Argument errors return before any HIP call.  The launch forms are ssasr_ctc_segment_form's. */
+int64_t ssasr_ctc_segment_skip_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t Lmax, int64_t Nmax);
+int ssasr_ctc_segment_skip(const float* logits, const int32_t* frame_lens, const int32_t* y, int64_t y_ld,
+                           const int32_t* label_lens, const int32_t* utt_ends, int64_t utt_ld, const int32_t* n_utts,
+                           int64_t B, int64_t T, int64_t V, int64_t Lmax, int64_t Nmax, int64_t window, int blank,
+                           const double* skip_penalty, const double* fill_penalty, void* ws, int64_t ws_bytes, int32_t* path,
+                           int32_t* first, int32_t* last, float* char_logp, double* score, int32_t* utt_first,
+                           int32_t* utt_last, float* utt_conf, int32_t* utt_skipped, int32_t* is_fill, void* stream);
 
 /* ---- CTC-only decoding (added under ABI 16) ----------------------------------------------------------------------
  * BUILD-DEFINED: the reference has no CTC.  A transcript from the head's posteriors alone, with no Speller step: the

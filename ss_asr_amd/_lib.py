@@ -156,6 +156,9 @@ SIGNATURES = {
     'ssasr_ctc_segment_form': (I32, [I64, I64, P, P]),
     'ssasr_ctc_segment': (I32, [P, P, P, I64, P, P, I64, P, I64, I64, I64, I64, I64, I64, I32, P, I64, P, P, P, P, P, P,
                                 P, P, P]),
+    'ssasr_ctc_segment_skip_ws_bytes': (I64, [I64, I64, I64, I64, I64]),
+    'ssasr_ctc_segment_skip': (I32, [P, P, P, I64, P, P, I64, P, I64, I64, I64, I64, I64, I64, I32, P, P, P, I64, P, P,
+                                     P, P, P, P, P, P, P, P, P]),
     'ssasr_ctc_decode_ws_bytes': (I64, [I64, I64, I64, I64]),
     'ssasr_ctc_decode': (I32, [P, P, I64, I64, I64, I64, I32, P, I64, P, P, P, P, P]),
     'ssasr_ctc_decode_lm_ws_bytes': (I64, [I64, I64, I64, I64, I64]),

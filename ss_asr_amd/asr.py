@@ -42,9 +42,11 @@ Alignment = collections.namedtuple('Alignment', ('score', 'chars'))
 # text inside the recording (float, -inf when nothing fits); span: (start, end exclusive) of the text in input frames
 # (seconds with frame_shift); utterances: [Segment(text, start, end, confidence)], confidence the min-mean of the path's
 # log-probabilities over blocks of `window` encoder frames; chars as in Alignment.  span, utterances and chars are None
-# when nothing fits.
-Segmentation = collections.namedtuple('Segmentation', ('score', 'span', 'utterances', 'chars'))
-Segment = collections.namedtuple('Segment', ('text', 'start', 'end', 'confidence'))
+# when nothing fits.  With ASR.segment's skip_penalty / fill_penalty: an utterance that was passed over has skipped True,
+# start = end = None and confidence 0.0 (its characters (char, None, None, 0.0)); fillers: [(start, end exclusive)] of the
+# runs of frames taken as unwritten speech at an utterance boundary, in the spans' unit (None without the penalties).
+Segmentation = collections.namedtuple('Segmentation', ('score', 'span', 'utterances', 'chars', 'fillers'), defaults=(None,))
+Segment = collections.namedtuple('Segment', ('text', 'start', 'end', 'confidence', 'skipped'), defaults=(False,))
 
 # ASR.score's result for one utterance (BUILD-DEFINED).  chars, words: (S, D, I, N) of the best hypothesis against
 # the reference, N the reference's count; oracle: (k, chars, words) of the n-best entry with the fewest word errors
@@ -544,7 +546,8 @@ class ASR(nn.Module):
                                             for j, c in enumerate(text)]))
         return out
 
-    def segment(self, xs, x_lens, texts, mapper, *, window=30, frame_shift=None, encoded=None):
+    def segment(self, xs, x_lens, texts, mapper, *, window=30, frame_shift=None, encoded=None, skip_penalty=None,
+                fill_penalty=None):
         """BUILD-DEFINED: CTC segmentation of recording i (xs, x_lens as align takes them) with the running transcript
         texts[i], the LIST of its utterance strings, on a model with a ctc_head: where inside the recording the text
         was spoken and where each utterance starts and ends (ssasr_ctc_segment, include/ssasr.h: align's lattice on
@@ -556,7 +559,12 @@ class ASR(nn.Module):
         Returns one Segmentation(score, span, utterances, chars) per recording, spans in INPUT frames through
         input_span (seconds when frame_shift is given); utterances is None and score -inf when nothing fits.
         last_segment keeps (path, first, last, char_logp, score, utt_first, utt_last, utt_conf, logits) on the device,
-        in encoder frames."""
+        in encoder frames.
+        skip_penalty / fill_penalty (None: off; else a finite number <= 0), for transcripts that are not verbatim
+        (ssasr_ctc_segment_skip): an utterance that was never spoken may be passed over at skip_penalty -- it comes
+        back with skipped True and no span -- and frames of speech that nobody wrote down may be taken at an utterance
+        boundary at fill_penalty each -- they come back as Segmentation.fillers.  last_segment then holds utt_skipped
+        and is_fill before the logits.  With both None nothing changes."""
         head = getattr(self, 'ctc_head', None)
         if head is None:
             raise ValueError(self._NO_CTC_HEAD % type(self).__name__)
@@ -566,6 +574,9 @@ class ASR(nn.Module):
             raise ValueError('segment: no recording')
         if isinstance(window, bool) or not isinstance(window, int) or window < 1:
             raise ValueError('segment: window must be an integer >= 1, got %r' % (window,))
+        ops._segment_penalty('skip_penalty', skip_penalty)       # a ValueError for anything but None or a finite number <= 0
+        ops._segment_penalty('fill_penalty', fill_penalty)
+        with_skip = skip_penalty is not None or fill_penalty is not None
         clean, labels, ends = [], [], []
         for utts in texts:
             if isinstance(utts, str) or not len(utts):
@@ -587,6 +598,9 @@ class ASR(nn.Module):
             labels.append(row)
             ends.append(row_ends)
         lmax, nmax = max(len(row) for row in labels), max(len(row) for row in ends)
+        if with_skip and nmax > ops.CTC_SEGMENT_SKIP_MAX_UTTS:
+            raise ValueError('segment: a text of %d utterances; with skip_penalty / fill_penalty the kernel takes at most '
+                             '%d' % (nmax, ops.CTC_SEGMENT_SKIP_MAX_UTTS))
         with torch.no_grad():
             if encoded is None:
                 for x_len in x_lens:
@@ -613,10 +627,11 @@ class ASR(nn.Module):
             self.last_segment = ops.ctc_head_segment(packed, head.weight, head.bias, enc_lens, y.to(dev),
                                                      _dev_i32([len(row) for row in labels], dev), ue.to(dev),
                                                      _dev_i32([len(row) for row in ends], dev), lmax, nmax, window,
-                                                     ops.CTC_BLANK)
-        path, first, last, char_logp, score, utt_first, utt_last, utt_conf, _ = self.last_segment
+                                                     ops.CTC_BLANK, skip_penalty=skip_penalty,
+                                                     fill_penalty=fill_penalty)
         path, first, last, char_logp, score, utt_first, utt_last, utt_conf = [
-            t.cpu().tolist() for t in (path, first, last, char_logp, score, utt_first, utt_last, utt_conf)]
+            t.cpu().tolist() for t in self.last_segment[:8]]
+        utt_skipped, is_fill = [t.cpu().tolist() for t in self.last_segment[8:10]] if with_skip else (None, None)
         out = []
         for i, utts in enumerate(clean):
             if score[i] == -math.inf:
@@ -625,12 +640,28 @@ class ASR(nn.Module):
             n = int(x_lens[i][0])
             frames = [t for t, s in enumerate(path[i]) if s >= 0]
             text = ''.join(utts)
+            if not with_skip:
+                out.append(Segmentation(
+                    score[i], input_span(frames[0], frames[-1], n, frame_shift),
+                    [Segment(u, *(input_span(utt_first[i][k], utt_last[i][k], n, frame_shift) + (utt_conf[i][k],)))
+                     for k, u in enumerate(utts)],
+                    [(c,) + input_span(first[i][j], last[i][j], n, frame_shift) + (char_logp[i][j],)
+                     for j, c in enumerate(text)]))
+                continue
+            span_of = lambda lo, hi: (None, None) if lo < 0 else input_span(lo, hi, n, frame_shift)
+            runs = []                                           # maximal runs of filler frames, (first, last)
+            for t in frames:
+                if is_fill[i][t] == 1:
+                    if runs and runs[-1][1] == t - 1:
+                        runs[-1][1] = t
+                    else:
+                        runs.append([t, t])
             out.append(Segmentation(
                 score[i], input_span(frames[0], frames[-1], n, frame_shift),
-                [Segment(u, *(input_span(utt_first[i][k], utt_last[i][k], n, frame_shift) + (utt_conf[i][k],)))
+                [Segment(u, *(span_of(utt_first[i][k], utt_last[i][k]) + (utt_conf[i][k], bool(utt_skipped[i][k]))))
                  for k, u in enumerate(utts)],
-                [(c,) + input_span(first[i][j], last[i][j], n, frame_shift) + (char_logp[i][j],)
-                 for j, c in enumerate(text)]))
+                [(c,) + span_of(first[i][j], last[i][j]) + (char_logp[i][j],) for j, c in enumerate(text)],
+                [input_span(lo, hi, n, frame_shift) for lo, hi in runs]))
         return out
 
     def score(self, refs, mapper):

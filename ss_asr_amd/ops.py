@@ -1045,15 +1045,35 @@ def ctc_segment_form(T, lmax):
     return None if form < 0 else (form, threads.value, per_thread.value)
 
 
-def ctc_segment(logits, frame_lens, y32, label_lens, utt_ends, n_utts, lmax, nmax, window, blank=0):
+CTC_SEGMENT_SKIP_MAX_UTTS = 1024   # ssasr_ctc_segment_skip's: the junctions' values live in LDS
+
+
+def _segment_penalty(name, value):
+    """None (off) -> -inf; else a finite number <= 0."""
+    if value is None:
+        return -math.inf
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or value > 0:
+        raise ValueError('ctc_segment: %s must be None or a finite number <= 0, got %r' % (name, value))
+    return float(value)
+
+
+def ctc_segment(logits, frame_lens, y32, label_lens, utt_ends, n_utts, lmax, nmax, window, blank=0, *,
+                skip_penalty=None, fill_penalty=None):
     """ssasr_ctc_segment: CTC segmentation of each row's WHOLE text (its utterances concatenated in y32) inside its
     frames, on the raw logits [B, T, V]: ctc_align's lattice on normalised values with a free start and a free end
     (include/ssasr.h).  utt_ends int32 [B, >= nmax]: the exclusive end of each utterance's labels; n_utts int32 [B].
     -> (path [B, T] int32, -1 outside the span; first, last [B, lmax] int32; char_logp [B, lmax] float32; score [B]
     float64, -inf: nothing fits; utt_first, utt_last [B, nmax] int32; utt_conf [B, nmax] float32: the min-mean of the
-    path's log-probabilities over blocks of `window` frames) on the device.  No autograd."""
+    path's log-probabilities over blocks of `window` frames) on the device.  No autograd.
+    skip_penalty / fill_penalty (None: off; else finite and <= 0): with either given, ssasr_ctc_segment_skip runs
+    instead -- an utterance may be passed over at skip_penalty, and a frame at an utterance boundary may be taken as
+    unwritten speech at fill_penalty (include/ssasr.h) -- and two more tensors follow the eight: utt_skipped [B, nmax]
+    int32 (1 skipped, 0 aligned, -1 no such utterance) and is_fill [B, T] int32 (1 a filler frame, 0 another scored
+    frame, -1 outside the span).  With both None the call and its result are what they were."""
     lib = _lib.load()
     lmax, nmax, window, blank = int(lmax), int(nmax), int(window), int(blank)
+    skip_pen, fill_pen = _segment_penalty('skip_penalty', skip_penalty), _segment_penalty('fill_penalty', fill_penalty)
+    with_skip = skip_penalty is not None or fill_penalty is not None
     _need_gpu(logits, frame_lens, y32, label_lens, utt_ends, n_utts)
     logits = _f32c(logits.detach())
     B, T, V = logits.shape
@@ -1064,7 +1084,10 @@ def ctc_segment(logits, frame_lens, y32, label_lens, utt_ends, n_utts, lmax, nma
         raise ValueError('ctc_segment: Lmax / Nmax exceed the label / utterance matrix')
     if window < 1:
         raise ValueError('ctc_segment: window must be >= 1, got %d' % window)
-    need = int(lib.ssasr_ctc_segment_ws_bytes(B, T, V, lmax, nmax))
+    if with_skip and nmax > CTC_SEGMENT_SKIP_MAX_UTTS:
+        raise ValueError('ctc_segment: %d utterances; with skip_penalty / fill_penalty at most %d'
+                         % (nmax, CTC_SEGMENT_SKIP_MAX_UTTS))
+    need = int((lib.ssasr_ctc_segment_skip_ws_bytes if with_skip else lib.ssasr_ctc_segment_ws_bytes)(B, T, V, lmax, nmax))
     if need <= 0:
         raise ValueError('ctc_segment: shape B=%d T=%d V=%d Lmax=%d Nmax=%d has no kernel (at most %d frames and %d '
                          'labels)' % (B, T, V, lmax, nmax, CTC_SEGMENT_MAX_FRAMES, CTC_SEGMENT_MAX_LABELS))
@@ -1078,6 +1101,16 @@ def ctc_segment(logits, frame_lens, y32, label_lens, utt_ends, n_utts, lmax, nma
     utt_first = torch.empty(B, nmax, device=dev, dtype=torch.int32)
     utt_last = torch.empty(B, nmax, device=dev, dtype=torch.int32)
     utt_conf = torch.empty(B, nmax, device=dev, dtype=torch.float32)
+    if with_skip:
+        utt_skipped = torch.empty(B, nmax, device=dev, dtype=torch.int32)
+        is_fill = torch.empty(B, T, device=dev, dtype=torch.int32)
+        pens = (C.c_double * 2)(skip_pen, fill_pen)            # host memory, read before the call returns
+        check(lib.ssasr_ctc_segment_skip(
+            _p(logits), _p(frame_lens), _p(y32), y32.stride(0), _p(label_lens), _p(utt_ends), utt_ends.stride(0),
+            _p(n_utts), B, T, V, lmax, nmax, window, blank, C.addressof(pens), C.addressof(pens) + 8, _p(ws), need,
+            _p(path), _p(first), _p(last), _p(char_logp), _p(score), _p(utt_first), _p(utt_last), _p(utt_conf),
+            _p(utt_skipped), _p(is_fill), _stream()), 'ssasr_ctc_segment_skip')
+        return path, first, last, char_logp, score, utt_first, utt_last, utt_conf, utt_skipped, is_fill
     check(lib.ssasr_ctc_segment(_p(logits), _p(frame_lens), _p(y32), y32.stride(0), _p(label_lens), _p(utt_ends),
                                 utt_ends.stride(0), _p(n_utts), B, T, V, lmax, nmax, window, blank, _p(ws), need,
                                 _p(path), _p(first), _p(last), _p(char_logp), _p(score), _p(utt_first), _p(utt_last),
@@ -1085,14 +1118,17 @@ def ctc_segment(logits, frame_lens, y32, label_lens, utt_ends, n_utts, lmax, nma
     return path, first, last, char_logp, score, utt_first, utt_last, utt_conf
 
 
-def ctc_head_segment(feat, weight, bias, frame_lens, y32, label_lens, utt_ends, n_utts, lmax, nmax, window, blank=0):
+def ctc_head_segment(feat, weight, bias, frame_lens, y32, label_lens, utt_ends, n_utts, lmax, nmax, window, blank=0, *,
+                     skip_penalty=None, fill_penalty=None):
     """ctc_segment on the head's logits, the product issued exactly as the training node issues it (_CTCHead.forward).
-    -> ctc_segment's eight tensors and the logits [B, T, V] they were computed on.  No autograd."""
+    -> ctc_segment's eight (with a penalty: ten) tensors and the logits [B, T, V] they were computed on.  No
+    autograd."""
     _need_gpu(feat, weight, bias)
     feat, w, b = _f32c(feat.detach()), _f32c(weight.detach()), _f32c(bias.detach())
     B, T, E = feat.shape
     logits = gemm(feat.view(B * T, E), w, bias=b).view(B, T, w.shape[0])
-    return ctc_segment(logits, frame_lens, y32, label_lens, utt_ends, n_utts, lmax, nmax, window, blank) + (logits,)
+    return ctc_segment(logits, frame_lens, y32, label_lens, utt_ends, n_utts, lmax, nmax, window, blank,
+                       skip_penalty=skip_penalty, fill_penalty=fill_penalty) + (logits,)
 
 
 CTC_DECODE_MAX_BEAM = 32       # ssasr_ctc_decode's limits (include/ssasr.h)

@@ -668,6 +668,150 @@ def ctc_segment_reference(lp, y, utt_ends, window, blank=0, dtype=np.float64):
                                  utt_first=utt_first, utt_last=utt_last, utt_conf=conf, gap=gap, span=(t_start, t_end))
 
 
+def _segment_skip_frame(dp, lp_t, lab, pen, junc, skip_pen, fill_pen, blank, others, neg, zero):
+    """One frame of ctc_segment_skip_reference's lattice: _segment_frame with the junctions' emission and skip.
+    junc: the junction states J_0 .. J_N; others: the classes that are not the blank.
+    -> (the new padded values, the codes, whether the filler won this frame's junction emission, its margin, the
+    states' emissions)."""
+    dtype = dp.dtype.type
+    d, one, two = dp[2:], dp[1:-1], dp[:-2] + pen
+    two[junc[1:]] = dp[junc[:-1] + 2] + skip_pen                # a blank has no s - 2: the skip takes its place
+    m1 = one > d                                                # stay, then s - 1, then s - 2 / the skip, then the start
+    best = np.where(m1, one, d)
+    m2 = two > best
+    best = np.where(m2, two, best)
+    code = m1.astype(np.int8)
+    code[m2] = 2
+    for s in range(min(d.shape[0], 2)):
+        if zero > best[s]:
+            best[s], code[s] = zero, 3
+    x = lp_t[others]
+    m = x.max()
+    fv = dtype(m + np.log(np.exp(x - m).sum(dtype=dtype))) + fill_pen
+    lpb = lp_t[blank]
+    fill = bool(fv > lpb)                                       # the blank wins a tie
+    emit = lp_t[lab]
+    emit[junc] = fv if fill else lpb
+    out = np.empty_like(dp)
+    out[:2] = neg
+    np.add(best, emit, out=out[2:])
+    return out, code, fill, (math.inf if fv == neg else abs(float(fv) - float(lpb))), emit
+
+
+def ctc_segment_skip_reference(lp, y, utt_ends, window, skip_penalty=-math.inf, fill_penalty=-math.inf, blank=0,
+                               dtype=np.float64):
+    """BUILD-DEFINED: CTC segmentation with utterance skips and a filler, ssasr_ctc_segment_skip (include/ssasr.h)
+    restated in numpy -- what the kernel is defined and tested against.  Arguments as ctc_segment_reference takes
+    them; skip_penalty, fill_penalty: finite and <= 0, or -inf (that mechanism off; with both off every output is
+    ctc_segment_reference's).  The junction J_n is the blank state 2 * utt_ends[n - 1] (J_0 = 0, J_N = S - 1).
+      f_t = log sum_{v != blank} exp(lp[t][v]); a junction state's emission is max(lp[t][blank], f_t + fill_penalty),
+      the blank winning a tie; J_{n+1} has one more predecessor, d[t-1][J_n] + skip_penalty, which takes the place of
+      s - 2 in the tie rule (stay, s - 1, skip, start).
+    -> None when nothing can be segmented, else ctc_segment_reference's namespace with utt_skipped [N] (1 / 0) and
+    is_fill [T] (1 on a junction frame of the path where the filler won, 0 on the other scored frames, -1 outside
+    the span); a skipped utterance has utt_first = utt_last = -1, utt_conf = 0, its characters first = last = -1 and
+    char_logp = 0.  gap also covers the filler-versus-blank choice on every junction frame of the path."""
+    import types
+    lp = np.asarray(lp).astype(dtype)
+    if lp.ndim != 2:
+        raise ValueError('ctc_segment_skip_reference: lp must be [T, V], got %r' % (lp.shape,))
+    window, blank = int(window), int(blank)
+    if window < 1:
+        raise ValueError('ctc_segment_skip_reference: window must be >= 1, got %d' % window)
+    for name, p in (('skip_penalty', skip_penalty), ('fill_penalty', fill_penalty)):
+        if not p <= 0:                                          # a NaN too
+            raise ValueError('ctc_segment_skip_reference: %s must be <= 0 or -inf, got %r' % (name, p))
+    y, ends = [int(c) for c in y], [int(e) for e in utt_ends]
+    T, L = lp.shape[0], len(y)
+    if T < 1 or L < 1 or not ends or ends[-1] != L or any(b <= a for a, b in zip([0] + ends, ends)):
+        return None
+    neg, zero = dtype(-np.inf), dtype(0)
+    skip_pen, fill_pen = dtype(skip_penalty), dtype(fill_penalty)
+    S, N = 2 * L + 1, len(ends)
+    lab = np.full(S, blank, dtype=np.int64)
+    lab[1::2] = y
+    skip = np.zeros(S, dtype=bool)
+    skip[3::2] = lab[3::2] != lab[1:-2:2]
+    pen = np.where(skip, zero, neg).astype(dtype)
+    junc = np.array([0] + [2 * e for e in ends], dtype=np.int64)
+    is_junc = np.zeros(S, dtype=bool)
+    is_junc[junc] = True
+    others = np.array([v for v in range(lp.shape[1]) if v != blank], dtype=np.int64)
+    frame = lambda dp, t: _segment_skip_frame(dp, lp[t], lab, pen, junc, skip_pen, fill_pen, blank, others, neg, zero)
+    back = np.zeros((T, S), dtype=np.int8)
+    dp = np.full(S + 2, neg, dtype=dtype)
+    ends_seen = []
+    best_end = None
+    with np.errstate(invalid='ignore'):
+        for t in range(T):
+            dp, back[t] = frame(dp, t)[:2]
+            for s in (S - 1, S - 2):
+                v = dp[s + 2]
+                ends_seen.append(v)
+                if v > neg and (best_end is None or v > best_end[0]):
+                    best_end = (v, t, s)
+        if best_end is None:
+            return None
+        score, t_end, s = best_end
+        top = np.sort(np.asarray(ends_seen, dtype=dtype))
+        gap = float(top[-1] - top[-2]) if top[-2] > neg else math.inf
+        path = np.full(T, -1, dtype=np.int64)
+        t = t_end
+        while True:
+            path[t] = s
+            code = int(back[t, s])
+            if code == 3:
+                break
+            if code == 2 and is_junc[s]:
+                s = int(junc[int(np.searchsorted(junc, s)) - 1])
+            else:
+                s -= code
+            t -= 1
+        t_start = t
+        del back
+        q = np.zeros(T, dtype=dtype)
+        is_fill = np.full(T, -1, dtype=np.int64)
+        dp = np.full(S + 2, neg, dtype=dtype)
+        for t in range(t_end + 1):                              # again, for the margins along the path
+            s = int(path[t])
+            if t >= t_start:
+                cand = [dp[s + 2], dp[s + 1], dp[s] + pen[s], zero if s < 2 else neg]
+                if is_junc[s] and s:
+                    cand[2] = dp[junc[int(np.searchsorted(junc, s)) - 1] + 2] + skip_pen
+                cand = sorted(float(c) for c in cand)
+                gap = min(gap, math.inf if cand[-2] == -math.inf else cand[-1] - cand[-2])
+            dp, _, fill, margin, emit = frame(dp, t)
+            if t >= t_start:
+                is_fill[t] = int(fill and is_junc[s])
+                if is_junc[s]:
+                    gap = min(gap, margin)
+                q[t] = emit[s]
+
+    def total(lo, hi):
+        return np.cumsum(q[lo:hi + 1], dtype=dtype)[-1]
+    first, last = np.full(L, -1, dtype=np.int64), np.full(L, -1, dtype=np.int64)
+    logp = np.zeros(L, dtype=dtype)
+    for j in range(L):
+        frames = np.nonzero(path == 2 * j + 1)[0]
+        if len(frames):
+            first[j], last[j] = frames[0], frames[-1]
+            logp[j] = total(first[j], last[j])
+    utt_first = np.array([first[a] for a in [0] + ends[:-1]], dtype=np.int64)
+    utt_last = np.array([last[e - 1] for e in ends], dtype=np.int64)
+    utt_skipped = (utt_first < 0).astype(np.int64)
+    conf = np.zeros(N, dtype=dtype)
+    for n in range(N):
+        if utt_skipped[n]:
+            utt_last[n] = -1
+            continue
+        means = [total(lo, min(lo + window - 1, utt_last[n])) / dtype(min(lo + window - 1, utt_last[n]) - lo + 1)
+                 for lo in range(utt_first[n], utt_last[n] + 1, window)]
+        conf[n] = min(means)
+    return types.SimpleNamespace(score=float(score), path=path, first=first, last=last, char_logp=logp,
+                                 utt_first=utt_first, utt_last=utt_last, utt_conf=conf, gap=gap, span=(t_start, t_end),
+                                 utt_skipped=utt_skipped, is_fill=is_fill)
+
+
 class ErrorStats:
     """Corpus-level error rates: sums (S, D, I, N) rows of characters and of words; cer / wer =
     sum(S + D + I) / sum(N), nan when N == 0.  (calc_err below stays the reference's mean of per-utterance ratios.)"""

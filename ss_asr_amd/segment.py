@@ -14,6 +14,16 @@ from .preprocess import EOS_TKN, SOS_TKN, zero_pad
 Written = collections.namedtuple('Written', ('segment', 'row'))
 
 
+class WrittenSegments(tuple):
+    """write_segments' result: the pair (kept, dropped), which unpacks and compares as that tuple, and `skipped`: how
+    many of the dropped utterances the segmentation had passed over as never spoken."""
+
+    def __new__(cls, kept, dropped, skipped=0):
+        self = super().__new__(cls, (kept, dropped))
+        self.skipped = skipped
+        return self
+
+
 def write_segments(segmentation, fbank, out_dir, index_path, *, min_confidence, name, pad_to=None):
     """Cuts fbank [frames, features], the recording that `segmentation` (one ASR.segment result, spans in INPUT
     frames, i.e. made without frame_shift) belongs to, at every utterance whose confidence is >= min_confidence:
@@ -23,13 +33,19 @@ def write_segments(segmentation, fbank, out_dir, index_path, *, min_confidence, 
     as preprocess.sort_index writes (tab separated, minimal quoting, '\\n' line ends): normalized_text = '<' + text +
     '>', s_len = its length (normalize_string's count: the text's characters + 2), unpadded_num_frames = end - start,
     text_fname 'na', wav_fname = <name>_<k>.wav.  A recording that could not be segmented (utterances None) keeps
-    nothing.  -> (kept, dropped): lists of Written(segment, row), row None for the dropped ones."""
+    nothing.  An utterance that ASR.segment passed over (skipped True: it was never spoken) is never written and has
+    no span to check; it is counted among the dropped ones, and the result's `skipped` is their number.
+    -> (kept, dropped): lists of Written(segment, row), row None for the dropped ones; the pair is a WrittenSegments,
+    a tuple that also carries `skipped`."""
     fbank = np.asarray(fbank)
     if fbank.ndim != 2:
         raise ValueError('write_segments: fbank must be [frames, features], got %r' % (fbank.shape,))
     utterances = segmentation.utterances or []
     kept, dropped = [], []
     for k, seg in enumerate(utterances):
+        if getattr(seg, 'skipped', False):
+            dropped.append((k, seg))
+            continue
         if isinstance(seg.start, float) or isinstance(seg.end, float):
             raise ValueError('write_segments: spans must be in input frames (ASR.segment without frame_shift)')
         if not 0 <= seg.start < seg.end <= fbank.shape[0]:
@@ -52,4 +68,5 @@ def write_segments(segmentation, fbank, out_dir, index_path, *, min_confidence, 
         w = csv.writer(f, delimiter='\t', quoting=csv.QUOTE_MINIMAL, lineterminator='\n')
         for r in rows:
             w.writerow([r[c] for c in COLUMNS])
-    return ([Written(seg, r) for (_, seg), r in zip(kept, rows)], [Written(seg, None) for _, seg in dropped])
+    return WrittenSegments([Written(seg, r) for (_, seg), r in zip(kept, rows)], [Written(seg, None) for _, seg in dropped],
+                           sum(1 for _, seg in dropped if getattr(seg, 'skipped', False)))

@@ -14,7 +14,7 @@ LIB = os.path.join(HERE, 'libssasr_hip.so')
 SOURCES = ['gemm.hip', 'rnn.hip', 'decoder.hip', 'loss_opt.hip', 'ctc.hip', 'frontend.hip', 'seed.hip', 'sae.hip', 'infer.hip', 'charlm_train.hip',
            'options.hip', 'score.hip', 'mwer.hip', 'mbr.hip', 'rescore.hip', 'segment.hip']
 HEADERS = ['common.h', 'rnn_kernels.h', 'attn_kernels.h', 'decoder_persistent.h', 'decoder_long.h',
-           'decoder_bwd_persistent.h', 'edit_dp.h', 'seq_logp.h',
+           'decoder_bwd_persistent.h', 'edit_dp.h', 'seq_logp.h', 'ctc_prefix.h',
            os.path.join('..', '..', 'include', 'ssasr.h')]
 FLAGS = ['-O3', '--offload-arch=gfx950', '-fPIC', '-std=c++17', '-Wno-pass-failed']
 

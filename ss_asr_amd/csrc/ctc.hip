@@ -17,6 +17,7 @@
 // running maximum (magnitude <= log 3 on the way out), which is where a float is exact enough.
 #include "../../include/ssasr.h"
 #include "common.h"
+#include "ctc_prefix.h"
 
 #include <cmath>
 
@@ -461,37 +462,14 @@ int align_check_shape(int64_t B, int64_t T, int64_t V, int64_t Lmax) {
 
 // ---- CTC-only decoding: best path and prefix beam search (include/ssasr.h) -----------------------------------------
 // BUILD-DEFINED like the rest of this file.  One workgroup of 256 threads per utterance, a serial loop over its
-// frames.  The prefix search keeps, per beam member, g_b / g_n in double, the text's length, last character and a
-// rolling hash of the text and of its parent in LDS, and the texts themselves in the workspace, one block per beam
-// (B_{t-1} is read, B_t written).  A frame is: the row's log-softmax (wave 0, the next row's logits loaded one frame
-// ahead); each member's parent looked up among the members (length and hash as a filter, then the characters,
-// one wave per member); the K + K V candidate totals into LDS, an extension that is itself a member being no
-// candidate; K rounds of a block-wide argmax; the winners' scalars and texts written to the other beam.
+// frames.  The prefix search's frame body, its limits and its argument block live in ctc_prefix.h, shared with the
+// graph kernel below and with infer.hip's CharLM kernel; this file holds the best path and the two kernels' set-up.
 constexpr int DEC_NT = 256;
 constexpr int DEC_WAVES = DEC_NT / 64;
-constexpr int DEC_MAX_K = 32;
-constexpr int DEC_MAX_V = 64;
 constexpr int DEC_MAX_V_BEST = 1024;
-constexpr int DEC_MAX_T = 4096;
-constexpr unsigned long long DEC_HASH_MUL = 0x9E3779B97F4A7C15ull;
 
-struct DecodeArgs {
-  const float* logits;       // [B][T][V]
-  const int32_t* frame_lens; // [B]
-  int T, V, K, blank;
-  int32_t* text;             // K >= 1: [B][2][K][T] the two beams' texts; K = 0: [B][T] the frames' labels
-  int32_t* chars;            // [B][max(K,1)][T]
-  int32_t* n_chars;          // [B][max(K,1)]
-  float* scores;             // [B][max(K,1)]
-  int32_t* n_hyps;           // [B]
-};
-
-// log(exp(a) + exp(b)): double operands, exp and log in float on the difference from the larger one
-__device__ __forceinline__ double dec_lae(double a, double b) {
-  const double m = fmax(a, b), n = fmin(a, b);
-  if (n == NEG_INF) return m;
-  return m + (double)logf(1.f + expf((float)(n - m)));
-}
+// K = 0 (the best path): text is [B][T] the frames' labels, the outputs hold one hypothesis a row
+using DecodeArgs = ctc_prefix::Args;
 
 __global__ __launch_bounds__(DEC_NT) void ctc_best_path_kernel(DecodeArgs a) {
   __shared__ double red[DEC_WAVES];
@@ -550,184 +528,30 @@ __global__ __launch_bounds__(DEC_NT) void ctc_best_path_kernel(DecodeArgs a) {
   }
 }
 
+// the prefix search with no term beside the CTC total: ctc_prefix.h's body as it is
 __global__ __launch_bounds__(DEC_NT) void ctc_prefix_beam_kernel(DecodeArgs a) {
-  __shared__ double gb[2][DEC_MAX_K], gn[2][DEC_MAX_K];      // the two beams' members
-  __shared__ unsigned long long hs[2][DEC_MAX_K], hp[2][DEC_MAX_K];   // hash of the text, of the text's parent
-  __shared__ int tlen[2][DEC_MAX_K], tlast[2][DEC_MAX_K];    // length, last character (-1: the empty text)
-  __shared__ int par[DEC_MAX_K];                             // the member that is this member's parent, -1: none
-  __shared__ signed char child[DEC_MAX_K * DEC_MAX_V];       // [u][c]: the member that is u.c, -1: none
-  __shared__ double lpd[DEC_MAX_V];                          // the frame's log-softmax
-  __shared__ double sgb[DEC_MAX_K], sgn[DEC_MAX_K];          // g_b', g_n' of the kept texts
-  __shared__ double tot[DEC_MAX_K + DEC_MAX_K * DEC_MAX_V];  // the candidates' totals: [K] kept, then [K][V] extensions
-  __shared__ double wv[2][DEC_WAVES], winv[DEC_MAX_K];
-  __shared__ int wi[2][DEC_WAVES], win[DEC_MAX_K];
-  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int len = max(min(a.frame_lens[b], a.T), 0), V = a.V, K = a.K, T = a.T, blank = a.blank;
-  const float* logits = a.logits + (int64_t)b * T * V;
-  int32_t* text = a.text + (int64_t)b * 2 * K * T;
-  const int ncand = K + K * V;
-  int n = 1, cur = 0;
-  if (tid == 0) {
-    gb[0][0] = 0.0; gn[0][0] = NEG_INF;
-    hs[0][0] = 0; hp[0][0] = 0;
-    tlen[0][0] = 0; tlast[0][0] = -1;
-  }
-  float x_next = (wave == 0 && lane < V && len > 0) ? logits[lane] : -INFINITY;
-  __syncthreads();
-  for (int t = 0; t < len; ++t) {
-    const int32_t* told = text + (int64_t)cur * K * T;
-    int32_t* tnew = text + (int64_t)(cur ^ 1) * K * T;
-    for (int i = tid; i < K * V; i += DEC_NT) child[i] = -1;
-    if (wave == 0) {                                         // the row's log-softmax (ctc_table's normaliser)
-      const float x = x_next;
-      if (t + 1 < len && lane < V) x_next = logits[(int64_t)(t + 1) * V + lane];
-      const float m = wave_max(x);
-      const float s = wave_sum(lane < V ? expf(x - m) : 0.f);
-      const double lse = (double)m + (double)logf(s);
-      if (lane < V) lpd[lane] = (double)x - lse;
-    }
-    __syncthreads();
-    // each member's parent among the members: a lane per possible parent filters, the wave compares the characters
-    for (int w = wave; w < n; w += DEC_WAVES) {
-      const int lw = tlen[cur][w];
-      int found = -1;
-      if (lw >= 1) {
-        unsigned long long mask = __ballot(lane < n && tlen[cur][lane < n ? lane : 0] == lw - 1 &&
-                                           hs[cur][lane < n ? lane : 0] == hp[cur][w]);
-        while (mask != 0 && found < 0) {                     // at most n turns
-          const int u = __ffsll((long long)mask) - 1;
-          mask &= mask - 1;
-          int differ = 0;
-          for (int i = lane; i < lw - 1; i += 64) differ |= told[(int64_t)w * T + i] != told[(int64_t)u * T + i];
-          if (!__any(differ)) found = u;
-        }
-        if (lane == 0 && found >= 0) child[found * V + tlast[cur][w]] = (signed char)w;
-      }
-      if (lane == 0) par[w] = found;
-    }
-    __syncthreads();
-    // the candidates' totals; each thread remembers the best of its own
-    const double lpb = lpd[blank];
-    double best = NEG_INF;
-    int bidx = INT32_MAX;
-    for (int idx = tid; idx < ncand; idx += DEC_NT) {
-      double v = NEG_INF;
-      if (idx < K) {
-        const int w = idx;
-        if (w < n) {
-          const double nb = lpb + dec_lae(gb[cur][w], gn[cur][w]);
-          double nn = NEG_INF;
-          const int c = tlast[cur][w];
-          if (c >= 0) {
-            const int p = par[w];
-            double via = NEG_INF;
-            if (p >= 0) via = tlast[cur][p] == c ? gb[cur][p] : dec_lae(gb[cur][p], gn[cur][p]);
-            nn = lpd[c] + dec_lae(gn[cur][w], via);
-          }
-          sgb[w] = nb;
-          sgn[w] = nn;
-          v = dec_lae(nb, nn);
-        }
-      } else {
-        const int u = (idx - K) / V, c = (idx - K) % V;
-        if (u < n && c != blank && child[u * V + c] < 0)
-          v = lpd[c] + (tlast[cur][u] == c ? gb[cur][u] : dec_lae(gb[cur][u], gn[cur][u]));
-      }
-      tot[idx] = v;
-      if (v > best) { best = v; bidx = idx; }
-    }
-    // B_t: K rounds of a block-wide argmax (the lowest index among equals), the winner leaving the pool
-    int n_new = 0;
-    for (int r = 0; r < K; ++r) {
-      double m = best;
-      int mi = bidx;
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) {
-        const double om = __shfl_xor(m, off);
-        const int oi = __shfl_xor(mi, off);
-        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-      }
-      if (lane == 0) { wv[r & 1][wave] = m; wi[r & 1][wave] = mi; }
-      __syncthreads();
-      double gm = wv[r & 1][0];
-      int gi = wi[r & 1][0];
-#pragma unroll
-      for (int w = 1; w < DEC_WAVES; ++w) {
-        const double om = wv[r & 1][w];
-        const int oi = wi[r & 1][w];
-        if (om > gm || (om == gm && oi < gi)) { gm = om; gi = oi; }
-      }
-      if (!(gm > NEG_INF)) break;                            // fewer finite candidates than K
-      if (tid == 0) { win[r] = gi; winv[r] = gm; }
-      n_new = r + 1;
-      if (gi % DEC_NT == tid) {
-        tot[gi] = NEG_INF;
-        best = NEG_INF;
-        bidx = INT32_MAX;
-        for (int idx = tid; idx < ncand; idx += DEC_NT) {
-          const double v = tot[idx];
-          if (v > best) { best = v; bidx = idx; }
-        }
-      }
-    }
-    __syncthreads();
-    // the winners become B_t: scalars, then texts
-    const int nxt = cur ^ 1;
-    if (tid < n_new) {
-      const int gi = win[tid];
-      if (gi < K) {
-        gb[nxt][tid] = sgb[gi]; gn[nxt][tid] = sgn[gi];
-        hs[nxt][tid] = hs[cur][gi]; hp[nxt][tid] = hp[cur][gi];
-        tlen[nxt][tid] = tlen[cur][gi]; tlast[nxt][tid] = tlast[cur][gi];
-      } else {
-        const int u = (gi - K) / V, c = (gi - K) % V;
-        gb[nxt][tid] = NEG_INF; gn[nxt][tid] = winv[tid];
-        hs[nxt][tid] = hs[cur][u] * DEC_HASH_MUL + (unsigned long long)(c + 1); hp[nxt][tid] = hs[cur][u];
-        tlen[nxt][tid] = tlen[cur][u] + 1; tlast[nxt][tid] = c;
-      }
-    }
-    for (int j = 0; j < n_new; ++j) {
-      const int gi = win[j];
-      const int src = gi < K ? gi : (gi - K) / V;
-      const int l = tlen[cur][src];                          // l <= t < T: the appended character stays in the row
-      for (int i = tid; i < l; i += DEC_NT) tnew[(int64_t)j * T + i] = told[(int64_t)src * T + i];
-      if (gi >= K && tid == 0) tnew[(int64_t)j * T + l] = (gi - K) % V;
-    }
-    __syncthreads();
-    cur = nxt;
-    n = n_new;
-  }
-  // the members are in the order they won: best first
-  const int32_t* tfin = text + (int64_t)cur * K * T;
-  for (int j = 0; j < K; ++j) {
-    const int l = j < n ? tlen[cur][j] : 0;
-    int32_t* out = a.chars + ((int64_t)b * K + j) * T;
-    for (int i = tid; i < T; i += DEC_NT) out[i] = i < l ? tfin[(int64_t)j * T + i] : 0;
-  }
-  if (tid < K) {
-    a.n_chars[(int64_t)b * K + tid] = tid < n ? tlen[cur][tid] : 0;
-    a.scores[(int64_t)b * K + tid] = tid < n ? (float)dec_lae(gb[cur][tid], gn[cur][tid]) : -INFINITY;
-  }
-  if (tid == 0) a.n_hyps[b] = n;
+  __shared__ ctc_prefix::State<DEC_NT, ctc_prefix::NoTerm> s;
+  ctc_prefix::NoTerm term;
+  ctc_prefix::search(a, term, s);
 }
 
+// K = 0: the best path's limits; K >= 1: the prefix search's
 int decode_check_shape(int64_t B, int64_t T, int64_t V, int64_t K) {
-  if (B < 1 || B > 65535 || T < 1 || T > DEC_MAX_T || V < 2 || K < 0 || K > DEC_MAX_K) return SSASR_EARG;
-  if (V > (K == 0 ? DEC_MAX_V_BEST : DEC_MAX_V)) return SSASR_EARG;
+  if (K != 0) return ctc_prefix::shape_ok(B, T, V, K) ? SSASR_OK : SSASR_EARG;
+  if (B < 1 || B > ctc_prefix::kMaxB || T < 1 || T > ctc_prefix::kMaxT || V < 2 || V > DEC_MAX_V_BEST) return SSASR_EARG;
   return SSASR_OK;
 }
 
 
 // ---- the prefix beam search with a character graph in the ranking (include/ssasr.h, ssasr_ctc_decode_graph) --------
-// ctc_prefix_beam_kernel restated, as infer.hip restates it for the CharLM: the same frame body, and beside g_b / g_n
-// every member carries the graph's state after its text (int32) and G, the sum of the arcs taken (double).  The rows
-// next[state][.] and arc[state][.] of a member sit in LDS, [slot][64], from the frame after the member entered a beam
-// until it leaves: a kept member keeps its slot, so the candidate loop and the winners' update read LDS alone.  The
-// only global reads of the tables are the rows of a frame's new members: issued once the winners are known, a wave per
-// member, and stored to LDS as they arrive; the next frame's two barriers lie before their first reader.  (Holding
-// them in registers over the frame boundary and storing after the next frame's parent look-up measured no faster:
-// DESIGN.md 4.22.)  Every state read from the table is clamped to [0, S - 1]: a malformed table gives wrong scores, no
-// stray read.
+// ctc_prefix.h's frame body with GraphTerm: beside g_b / g_n every member carries the graph's state after its text
+// (int32) and, in the body's acc, G, the sum of the arcs taken (double).  The rows next[state][.] and arc[state][.] of
+// a member sit in LDS, [slot][64], from the frame after the member entered a beam until it leaves: a kept member keeps
+// its slot, so the candidate loop and the winners' update read LDS alone.  The only global reads of the tables are the
+// rows of a frame's new members: issued in after_commit, once the winners are known, a wave per member, and stored to
+// LDS as they arrive; the next frame's two barriers lie before their first reader.  (Holding them in registers over
+// the frame boundary and storing after the next frame's parent look-up measured no faster: DESIGN.md 4.22.)  Every
+// state read from the table is clamped to [0, S - 1]: a malformed table gives wrong scores, no stray read.
 
 struct GraphArgs {
   DecodeArgs d;
@@ -739,254 +563,53 @@ struct GraphArgs {
   float *ctc_scores, *graph_scores;   // [B][K]
 };
 
+struct GraphTerm : ctc_prefix::Scored {
+  struct Mem : ctc_prefix::ScoredMem {
+    int gst[2][ctc_prefix::kMaxK];                           // the graph's state after the text
+    float arow[ctc_prefix::kMaxK][64];                       // [slot]: arc[state][.]
+    int nrow[ctc_prefix::kMaxK][64];                         // [slot]: next[state][.]
+  };
+  const GraphArgs& g;
+  int s_max;
+
+  __device__ explicit GraphTerm(const GraphArgs& ga)
+      : Scored{ga.graph_weight != 0.f, ga.length_bonus != 0.f, (double)ga.graph_weight, (double)ga.length_bonus,
+               ga.ctc_scores, ga.graph_scores},
+        g(ga), s_max(ga.S - 1) {}
+
+  __device__ void load_rows(Mem& m, int slot, int state, int V) const {   // one wave
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)state * V;
+    m.arow[slot][lane] = lane < V ? g.arc[row + lane] : 0.f;
+    m.nrow[slot][lane] = lane < V ? g.next[row + lane] : 0;
+  }
+  __device__ void init(Mem& m, int V) const {                // the empty text's rows: the start state's
+    if (threadIdx.x == 0) m.gst[0][0] = on ? g.start : 0;
+    if (on && threadIdx.x < 64) load_rows(m, 0, g.start, V);
+  }
+  __device__ double step(const Mem& m, int cur, int u, int c) const { return (double)m.arow[m.slot[cur][u]][c]; }
+  __device__ void keep(Mem& m, int cur, int nxt, int j, int w) const { m.gst[nxt][j] = m.gst[cur][w]; }
+  __device__ void inherit(Mem& m, int cur, int nxt, int j, int u, int c) const {
+    m.gst[nxt][j] = on ? min(max(m.nrow[m.slot[cur][u]][c], 0), s_max) : 0;
+  }
+  // the new members' rows: a wave per member; two barriers of the next frame lie before their first reader
+  template <class S>
+  __device__ void after_commit(S& s, int, int nxt, int, int V) const {
+    Mem& m = s.tm;
+    const int ne = on ? m.n_ext : 0;
+    for (int e = threadIdx.x >> 6; e < ne; e += DEC_WAVES) {
+      const int j = m.ext[e];
+      load_rows(m, m.slot[nxt][j], m.gst[nxt][j], V);
+    }
+  }
+  __device__ bool has_end() const { return true; }
+  __device__ double end(const Mem& m, int cur, int j) const { return (double)g.fin[min(max(m.gst[cur][j], 0), s_max)]; }
+};
+
 __global__ __launch_bounds__(DEC_NT) void ctc_prefix_beam_graph_kernel(GraphArgs g) {
-  __shared__ double gb[2][DEC_MAX_K], gn[2][DEC_MAX_K];      // the two beams' members
-  __shared__ double G[2][DEC_MAX_K];                         // the graph's score of the member's text
-  __shared__ unsigned long long hs[2][DEC_MAX_K], hp[2][DEC_MAX_K];   // hash of the text, of the text's parent
-  __shared__ int tlen[2][DEC_MAX_K], tlast[2][DEC_MAX_K];    // length, last character (-1: the empty text)
-  __shared__ int gst[2][DEC_MAX_K], slot[2][DEC_MAX_K];      // the graph's state after the text; the member's row slot
-  __shared__ int par[DEC_MAX_K];                             // the member that is this member's parent, -1: none
-  __shared__ signed char child[DEC_MAX_K * DEC_MAX_V];       // [u][c]: the member that is u.c, -1: none
-  __shared__ double lpd[DEC_MAX_V];                          // the frame's log-softmax
-  __shared__ double sgb[DEC_MAX_K], sgn[DEC_MAX_K];          // g_b', g_n' of the kept texts
-  __shared__ double tot[DEC_MAX_K + DEC_MAX_K * DEC_MAX_V];  // the candidates' keys: [K] kept, then [K][V] extensions
-  __shared__ double wv[2][DEC_WAVES];
-  __shared__ int wi[2][DEC_WAVES], win[DEC_MAX_K];
-  __shared__ float arow[DEC_MAX_K][64];                      // [slot]: arc[state][.]
-  __shared__ int nrow[DEC_MAX_K][64];                        // [slot]: next[state][.]
-  __shared__ int ext[DEC_MAX_K];                             // the frame's winners that are new extensions
-  __shared__ int n_ext_sh;
-  __shared__ float fkey[DEC_MAX_K], ftot[DEC_MAX_K], fctc[DEC_MAX_K], fgr[DEC_MAX_K];
-  __shared__ int fsrc[DEC_MAX_K];
-  const DecodeArgs& a = g.d;
-  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int len = max(min(a.frame_lens[b], a.T), 0), V = a.V, K = a.K, T = a.T, blank = a.blank;
-  const bool use_g = g.graph_weight != 0.f, use_len = g.length_bonus != 0.f;
-  const double gw = (double)g.graph_weight, beta = (double)g.length_bonus;
-  const int s_max = g.S - 1;
-  const float* logits = a.logits + (int64_t)b * T * V;
-  int32_t* text = a.text + (int64_t)b * 2 * K * T;
-  const int ncand = K + K * V;
-  int n = 1, cur = 0;
-  if (tid == 0) {
-    gb[0][0] = 0.0; gn[0][0] = NEG_INF; G[0][0] = 0.0;
-    hs[0][0] = 0; hp[0][0] = 0;
-    tlen[0][0] = 0; tlast[0][0] = -1;
-    gst[0][0] = use_g ? g.start : 0; slot[0][0] = 0;
-  }
-  if (use_g && wave == 0) {                                  // the empty text's rows: the start state's
-    const int64_t row = (int64_t)g.start * V;
-    arow[0][lane] = lane < V ? g.arc[row + lane] : 0.f;
-    nrow[0][lane] = lane < V ? g.next[row + lane] : 0;
-  }
-  float x_next = (wave == 0 && lane < V && len > 0) ? logits[lane] : -INFINITY;
-  __syncthreads();
-  for (int t = 0; t < len; ++t) {
-    const int32_t* told = text + (int64_t)cur * K * T;
-    int32_t* tnew = text + (int64_t)(cur ^ 1) * K * T;
-    for (int i = tid; i < K * V; i += DEC_NT) child[i] = -1;
-    if (wave == 0) {                                         // the row's log-softmax (ctc_table's normaliser)
-      const float x = x_next;
-      if (t + 1 < len && lane < V) x_next = logits[(int64_t)(t + 1) * V + lane];
-      const float m = wave_max(x);
-      const float s = wave_sum(lane < V ? expf(x - m) : 0.f);
-      const double lse = (double)m + (double)logf(s);
-      if (lane < V) lpd[lane] = (double)x - lse;
-    }
-    __syncthreads();
-    // each member's parent among the members: a lane per possible parent filters, the wave compares the characters
-    for (int w = wave; w < n; w += DEC_WAVES) {
-      const int lw = tlen[cur][w];
-      int found = -1;
-      if (lw >= 1) {
-        unsigned long long mask = __ballot(lane < n && tlen[cur][lane < n ? lane : 0] == lw - 1 &&
-                                           hs[cur][lane < n ? lane : 0] == hp[cur][w]);
-        while (mask != 0 && found < 0) {                     // at most n turns
-          const int u = __ffsll((long long)mask) - 1;
-          mask &= mask - 1;
-          int differ = 0;
-          for (int i = lane; i < lw - 1; i += 64) differ |= told[(int64_t)w * T + i] != told[(int64_t)u * T + i];
-          if (!__any(differ)) found = u;
-        }
-        if (lane == 0 && found >= 0) child[found * V + tlast[cur][w]] = (signed char)w;
-      }
-      if (lane == 0) par[w] = found;
-    }
-    __syncthreads();
-    // the candidates' keys: the CTC total, + graph_weight G(w) + length_bonus |w|; each thread remembers its best
-    const double lpb = lpd[blank];
-    double best = NEG_INF;
-    int bidx = INT32_MAX;
-    for (int idx = tid; idx < ncand; idx += DEC_NT) {
-      double v = NEG_INF;
-      if (idx < K) {
-        const int w = idx;
-        if (w < n) {
-          const double nb = lpb + dec_lae(gb[cur][w], gn[cur][w]);
-          double nn = NEG_INF;
-          const int c = tlast[cur][w];
-          if (c >= 0) {
-            const int p = par[w];
-            double via = NEG_INF;
-            if (p >= 0) via = tlast[cur][p] == c ? gb[cur][p] : dec_lae(gb[cur][p], gn[cur][p]);
-            nn = lpd[c] + dec_lae(gn[cur][w], via);
-          }
-          sgb[w] = nb;
-          sgn[w] = nn;
-          v = dec_lae(nb, nn);
-          if (v > NEG_INF) {
-            if (use_g) v += gw * G[cur][w];
-            if (use_len) v += beta * (double)tlen[cur][w];
-          }
-        }
-      } else {
-        const int u = (idx - K) / V, c = (idx - K) % V;
-        if (u < n && c != blank && child[u * V + c] < 0) {
-          v = lpd[c] + (tlast[cur][u] == c ? gb[cur][u] : dec_lae(gb[cur][u], gn[cur][u]));
-          if (v > NEG_INF) {                                 // a forbidden arc (-inf) leaves no candidate
-            if (use_g) v += gw * (G[cur][u] + (double)arow[slot[cur][u]][c]);
-            if (use_len) v += beta * (double)(tlen[cur][u] + 1);
-          }
-        }
-      }
-      tot[idx] = v;
-      if (v > best) { best = v; bidx = idx; }
-    }
-    // B_t: K rounds of a block-wide argmax (the lowest index among equals), the winner leaving the pool
-    int n_new = 0;
-    for (int r = 0; r < K; ++r) {
-      double m = best;
-      int mi = bidx;
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) {
-        const double om = __shfl_xor(m, off);
-        const int oi = __shfl_xor(mi, off);
-        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-      }
-      if (lane == 0) { wv[r & 1][wave] = m; wi[r & 1][wave] = mi; }
-      __syncthreads();
-      double gm = wv[r & 1][0];
-      int gi = wi[r & 1][0];
-#pragma unroll
-      for (int w = 1; w < DEC_WAVES; ++w) {
-        const double om = wv[r & 1][w];
-        const int oi = wi[r & 1][w];
-        if (om > gm || (om == gm && oi < gi)) { gm = om; gi = oi; }
-      }
-      if (!(gm > NEG_INF)) break;                            // fewer finite candidates than K
-      if (tid == 0) win[r] = gi;
-      n_new = r + 1;
-      if (gi % DEC_NT == tid) {
-        tot[gi] = NEG_INF;
-        best = NEG_INF;
-        bidx = INT32_MAX;
-        for (int idx = tid; idx < ncand; idx += DEC_NT) {
-          const double v = tot[idx];
-          if (v > best) { best = v; bidx = idx; }
-        }
-      }
-    }
-    __syncthreads();
-    // the winners become B_t: scalars, then texts.  A new extension's g_n' is its CTC total, formed again as above
-    // (the key is no longer that total); its state and G come from its parent's rows.
-    const int nxt = cur ^ 1;
-    if (tid < n_new) {
-      const int w = win[tid];
-      if (w < K) {
-        gb[nxt][tid] = sgb[w]; gn[nxt][tid] = sgn[w]; G[nxt][tid] = G[cur][w];
-        hs[nxt][tid] = hs[cur][w]; hp[nxt][tid] = hp[cur][w];
-        tlen[nxt][tid] = tlen[cur][w]; tlast[nxt][tid] = tlast[cur][w];
-        gst[nxt][tid] = gst[cur][w]; slot[nxt][tid] = slot[cur][w];
-      } else {
-        const int u = (w - K) / V, c = (w - K) % V;
-        gb[nxt][tid] = NEG_INF;
-        gn[nxt][tid] = lpd[c] + (tlast[cur][u] == c ? gb[cur][u] : dec_lae(gb[cur][u], gn[cur][u]));
-        G[nxt][tid] = use_g ? G[cur][u] + (double)arow[slot[cur][u]][c] : 0.0;
-        gst[nxt][tid] = use_g ? min(max(nrow[slot[cur][u]][c], 0), s_max) : 0;
-        hs[nxt][tid] = hs[cur][u] * DEC_HASH_MUL + (unsigned long long)(c + 1); hp[nxt][tid] = hs[cur][u];
-        tlen[nxt][tid] = tlen[cur][u] + 1; tlast[nxt][tid] = c;
-      }
-    }
-    if (tid == 0) {                                          // slots: the kept members' stay taken, the rest is free
-      unsigned used = 0;
-      for (int j = 0; j < n_new; ++j)
-        if (win[j] < K) used |= 1u << slot[cur][win[j]];
-      int ne = 0;
-      for (int j = 0; j < n_new; ++j)
-        if (win[j] >= K) {
-          const int s = __ffs((int)~used) - 1;               // K members at most: a bit below K is clear
-          used |= 1u << s;
-          slot[nxt][j] = s;
-          ext[ne++] = j;
-        }
-      n_ext_sh = ne;
-    }
-    for (int j = 0; j < n_new; ++j) {
-      const int w = win[j];
-      const int src = w < K ? w : (w - K) / V;
-      const int l = tlen[cur][src];                          // l <= t < T: the appended character stays in the row
-      for (int i = tid; i < l; i += DEC_NT) tnew[(int64_t)j * T + i] = told[(int64_t)src * T + i];
-      if (w >= K && tid == 0) tnew[(int64_t)j * T + l] = (w - K) % V;
-    }
-    __syncthreads();
-    // the new members' rows: a wave per member; two barriers of the next frame lie before their first reader
-    const int ne = use_g ? n_ext_sh : 0;
-    for (int e = wave; e < ne; e += DEC_WAVES) {
-      const int j = ext[e];
-      const int64_t row = (int64_t)gst[nxt][j] * V;
-      arow[slot[nxt][j]][lane] = lane < V ? g.arc[row + lane] : 0.f;
-      nrow[slot[nxt][j]][lane] = lane < V ? g.next[row + lane] : 0;
-    }
-    cur = nxt;
-    n = n_new;
-  }
-  // the totals, with the end term fin[state]; ranked by counting as rescore_kernel ranks (without a graph the members
-  // are in the order they won, which is this order)
-  if (tid < K) {
-    float key = -INFINITY, total = -INFINITY, ctc = -INFINITY, gr = 0.f;
-    if (tid < n) {
-      const double c = dec_lae(gb[cur][tid], gn[cur][tid]);
-      double l = 0.0, tv = c;
-      if (use_g) {
-        l = G[cur][tid];
-        tv += gw * l;
-      }
-      if (use_len) tv += beta * (double)tlen[cur][tid];
-      if (use_g) {
-        const double e = (double)g.fin[min(max(gst[cur][tid], 0), s_max)];
-        l += e;
-        tv += gw * e;
-      }
-      total = (float)tv; ctc = (float)c; gr = (float)l;
-      key = total != total ? -INFINITY : total;
-    }
-    fkey[tid] = key; ftot[tid] = total; fctc[tid] = ctc; fgr[tid] = gr;
-    fsrc[tid] = -1;
-  }
-  __syncthreads();
-  if (tid < n) {
-    const float key = fkey[tid];
-    int rank = 0;
-    for (int j = 0; j < n; ++j) rank += (fkey[j] > key || (fkey[j] == key && j < tid)) ? 1 : 0;
-    fsrc[rank] = tid;
-  }
-  __syncthreads();
-  const int32_t* tfin = text + (int64_t)cur * K * T;
-  for (int j = 0; j < K; ++j) {
-    const int src = fsrc[j];
-    const int l = src >= 0 ? tlen[cur][src] : 0;
-    int32_t* out = a.chars + ((int64_t)b * K + j) * T;
-    for (int i = tid; i < T; i += DEC_NT) out[i] = i < l ? tfin[(int64_t)src * T + i] : 0;
-  }
-  if (tid < K) {
-    const int src = fsrc[tid];
-    const int64_t o = (int64_t)b * K + tid;
-    a.n_chars[o] = src >= 0 ? tlen[cur][src] : 0;
-    a.scores[o] = src >= 0 ? ftot[src] : -INFINITY;
-    g.ctc_scores[o] = src >= 0 ? fctc[src] : -INFINITY;
-    g.graph_scores[o] = src >= 0 ? fgr[src] : 0.f;
-  }
-  if (tid == 0) a.n_hyps[b] = n;
+  __shared__ ctc_prefix::State<DEC_NT, GraphTerm> s;
+  GraphTerm term(g);
+  ctc_prefix::search(g.d, term, s);
 }
 
 constexpr int GRAPH_MAX_STATES = 1 << 20;
@@ -1004,11 +627,7 @@ extern "C" int ssasr_ctc_decode(const float* logits, const int32_t* frame_lens, 
   if (!logits || !frame_lens || !ws || !chars || !n_chars || !scores || !n_hyps) return SSASR_EARG;
   if (decode_check_shape(B, T, V, K) != SSASR_OK || blank < 0 || blank >= V) return SSASR_EARG;
   if ((reinterpret_cast<uintptr_t>(ws) & 7) || ws_bytes < ssasr_ctc_decode_ws_bytes(B, T, V, K)) return SSASR_EARG;
-  DecodeArgs a{};
-  a.logits = logits; a.frame_lens = frame_lens;
-  a.T = (int)T; a.V = (int)V; a.K = (int)K; a.blank = blank;
-  a.text = reinterpret_cast<int32_t*>(ws);
-  a.chars = chars; a.n_chars = n_chars; a.scores = scores; a.n_hyps = n_hyps;
+  const DecodeArgs a = ctc_prefix::make_args(logits, frame_lens, T, V, K, blank, ws, chars, n_chars, scores, n_hyps);
   void (*fn)(DecodeArgs) = K == 0 ? ctc_best_path_kernel : ctc_prefix_beam_kernel;
   hipLaunchKernelGGL(fn, dim3((unsigned)B), dim3(DEC_NT), 0, (hipStream_t)stream, a);
   SSASR_LAUNCH_CHECK();
@@ -1016,7 +635,7 @@ extern "C" int ssasr_ctc_decode(const float* logits, const int32_t* frame_lens, 
 }
 
 extern "C" int64_t ssasr_ctc_decode_graph_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K) {
-  if (K < 1 || decode_check_shape(B, T, V, K) != SSASR_OK) return 0;
+  if (!ctc_prefix::shape_ok(B, T, V, K)) return 0;
   return B * 2 * K * T * 4;
 }
 
@@ -1028,18 +647,14 @@ extern "C" int ssasr_ctc_decode_graph(const float* logits, const int32_t* frame_
   if (!logits || !frame_lens || !ws || !chars || !n_chars || !scores || !n_hyps || !ctc_scores || !graph_scores)
     return SSASR_EARG;
   if (!std::isfinite(graph_weight) || graph_weight < 0.f || !std::isfinite(length_bonus)) return SSASR_EARG;
-  if (K < 1 || decode_check_shape(B, T, V, K) != SSASR_OK || blank < 0 || blank >= V) return SSASR_EARG;
+  if (!ctc_prefix::shape_ok(B, T, V, K) || blank < 0 || blank >= V) return SSASR_EARG;
   if (graph_weight != 0.f && !graph) return SSASR_EARG;
   if (graph && (!graph->next || !graph->arc || !graph->fin || graph->V != V || graph->S < 1 ||
                 graph->S > GRAPH_MAX_STATES || graph->start < 0 || graph->start >= graph->S))
     return SSASR_EARG;
   if ((reinterpret_cast<uintptr_t>(ws) & 7) || ws_bytes < ssasr_ctc_decode_graph_ws_bytes(B, T, V, K)) return SSASR_EARG;
   GraphArgs g{};
-  DecodeArgs& a = g.d;
-  a.logits = logits; a.frame_lens = frame_lens;
-  a.T = (int)T; a.V = (int)V; a.K = (int)K; a.blank = blank;
-  a.text = reinterpret_cast<int32_t*>(ws);
-  a.chars = chars; a.n_chars = n_chars; a.scores = scores; a.n_hyps = n_hyps;
+  g.d = ctc_prefix::make_args(logits, frame_lens, T, V, K, blank, ws, chars, n_chars, scores, n_hyps);
   g.graph_weight = graph_weight; g.length_bonus = length_bonus;
   g.ctc_scores = ctc_scores; g.graph_scores = graph_scores;
   g.S = 1;

@@ -25,6 +25,7 @@
 #include <cmath>
 #include "../../include/ssasr.h"
 #include "common.h"
+#include "ctc_prefix.h"
 
 namespace {
 
@@ -1240,19 +1241,14 @@ __global__ __launch_bounds__(kThreads) void charlm_step_kernel(LmStepDev p) {
 }
 
 // ---- CTC prefix beam search with the CharLM inside the search (include/ssasr.h, "CTC decoding with an LM") ----------
-// BUILD-DEFINED.  ctc.hip's ctc_prefix_beam_kernel with one more term in a candidate's key: the frame body below is
-// that kernel's, at this file's kThreads, because the LM step is this file's helpers (matmat / gru_update / score_row).
-// g_b / g_n stay pure CTC masses; a member also carries L (double, the LM's log-probability of its text) and a SLOT:
-// lmrow[slot] in LDS is the LM's log-softmax row after the text, st[slot] in the workspace its two GRU rows.  A kept
-// member keeps its slot; a new extension takes a slot no kept member holds.  A frame's new members step together:
-// their parents' states are gathered into `stage` (all of them, before any slot is overwritten), stepped kHyps at a
-// time with the gate rows in the workspace, and scattered to their slots.  With lm.H == 0 (lm_weight == 0) no step
-// runs and no slot is read.
-constexpr int kCtcLmMaxK = 32;
-constexpr int kCtcLmMaxV = 64;
-constexpr int kCtcLmMaxT = 4096;
-constexpr unsigned long long kCtcLmHashMul = 0x9E3779B97F4A7C15ull;
-constexpr double kNegInf = -INFINITY;
+// BUILD-DEFINED.  ctc_prefix.h's frame body (the one ctc.hip's ctc_prefix_beam_kernel runs) with CtcLmTerm, at this
+// file's kThreads: the term is here because the LM step is this file's helpers (matmat / gru_update / score_row).
+// g_b / g_n stay pure CTC masses; a member also carries, in the body's acc, L (double, the LM's log-probability of its
+// text) and a SLOT: lmrow[slot] in LDS is the LM's log-softmax row after the text, st[slot] in the workspace its two
+// GRU rows.  A kept member keeps its slot; a new extension takes a slot no kept member holds.  A frame's new members
+// step together in after_commit: their parents' states are gathered into `stage` (all of them, before any slot is
+// overwritten), stepped kHyps at a time with the gate rows in the workspace, and scattered to their slots.  With
+// lm.H == 0 (lm_weight == 0) no step runs and no slot is read.
 
 // one utterance's float blocks of the workspace (floats; every block starts on 16 bytes)
 struct CtcLmWs {
@@ -1273,26 +1269,14 @@ __host__ __device__ inline CtcLmWs ctc_lm_ws_map(int K, int H) {
 }
 
 struct CtcLmDev {
-  const float* logits;       // [B][T][V]
-  const int32_t* frame_lens; // [B]
-  int T, V, K, blank, eos;
+  ctc_prefix::Args d;
+  int eos;
   float lm_weight, length_bonus;
   LmDev lm;                  // H == 0: no LM term
   float* fws;                // [B][ctc_lm_ws_map(K, H).total]
-  int32_t* text;             // [B][2][K][T] the two beams' texts
   int32_t* lm_frames;        // [B] frames that ran an LM step (tools/ctc_lm_time.py)
-  int32_t* chars;            // [B][K][T]
-  int32_t* n_chars;          // [B][K]
-  float *scores, *ctc_scores, *lm_scores;   // [B][K]
-  int32_t* n_hyps;           // [B]
+  float *ctc_scores, *lm_scores;   // [B][K]
 };
-
-// ctc.hip's dec_lae: log(exp(a) + exp(b)), double operands, exp and log in float on the difference from the larger
-__device__ __forceinline__ double ctc_lm_lae(double a, double b) {
-  const double m = fmax(a, b), n = fmin(a, b);
-  if (n == kNegInf) return m;
-  return m + (double)logf(1.f + expf((float)(n - m)));
-}
 
 // One CharLM step (speller_step's LM phases) for n <= kHyps hypotheses: st holds their (h1 | h2) rows 2 H apart and
 // is updated in place, lmx the embeddings of the characters fed; leaves the output rows in lmlg, 64 apart.
@@ -1314,277 +1298,77 @@ __device__ void ctc_lm_step(const LmDev& lm, int V, float* st, const float* lmx,
   phase_sync();
 }
 
-__global__ __launch_bounds__(kThreads) void ctc_prefix_beam_lm_kernel(CtcLmDev a) {
-  __shared__ double gb[2][kCtcLmMaxK], gn[2][kCtcLmMaxK];    // the two beams' members
-  __shared__ double Lm[2][kCtcLmMaxK];                       // the LM's log-probability of the member's text
-  __shared__ unsigned long long hs[2][kCtcLmMaxK], hp[2][kCtcLmMaxK];   // hash of the text, of the text's parent
-  __shared__ int tlen[2][kCtcLmMaxK], tlast[2][kCtcLmMaxK];  // length, last character (-1: the empty text)
-  __shared__ int slot[2][kCtcLmMaxK];                        // the member's row of lmrow and of st
-  __shared__ int par[kCtcLmMaxK];                            // the member that is this member's parent, -1: none
-  __shared__ signed char child[kCtcLmMaxK * kCtcLmMaxV];     // [u][c]: the member that is u.c, -1: none
-  __shared__ double lpd[kCtcLmMaxV];                         // the frame's log-softmax
-  __shared__ double sgb[kCtcLmMaxK], sgn[kCtcLmMaxK];        // g_b', g_n' of the kept texts
-  __shared__ double tot[kCtcLmMaxK + kCtcLmMaxK * kCtcLmMaxV];   // the candidates' keys: [K] kept, then [K][V]
-  __shared__ double wv[2][kWaves];
-  __shared__ int wi[2][kWaves], win[kCtcLmMaxK];
-  __shared__ float lmrow[kCtcLmMaxK][64];                    // [slot]: the LM's log-softmax row after the text
-  __shared__ int ext[kCtcLmMaxK];                            // the frame's winners that are new extensions
-  __shared__ int n_ext_sh;
-  __shared__ float fkey[kCtcLmMaxK], ftot[kCtcLmMaxK], fctc[kCtcLmMaxK], flm[kCtcLmMaxK];
-  __shared__ int fsrc[kCtcLmMaxK];
-  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int len = max(min(a.frame_lens[b], a.T), 0), V = a.V, K = a.K, T = a.T, blank = a.blank;
-  const int H = a.lm.H, Sz = 2 * H;
-  const bool use_lm = H > 0, use_len = a.length_bonus != 0.f;
-  const double alpha = (double)a.lm_weight, beta = (double)a.length_bonus;
-  const float* logits = a.logits + (int64_t)b * T * V;
-  int32_t* text = a.text + (int64_t)b * 2 * K * T;
-  const CtcLmWs m = ctc_lm_ws_map(K, H);
-  float* ws = a.fws + (int64_t)b * m.total;
-  float *st = ws + m.st, *stage = ws + m.stage, *lmx = ws + m.lmx, *gi = ws + m.gi, *gh = ws + m.gh,
-        *lmlg = ws + m.lmlg;
-  const int ncand = K + K * V;
-  int n = 1, cur = 0, lm_frames = 0;
-  if (tid == 0) {
-    gb[0][0] = 0.0; gn[0][0] = kNegInf; Lm[0][0] = 0.0;
-    hs[0][0] = 0; hp[0][0] = 0;
-    tlen[0][0] = 0; tlast[0][0] = -1; slot[0][0] = 0;
+struct CtcLmTerm : ctc_prefix::Scored {
+  struct Mem : ctc_prefix::ScoredMem {
+    float lmrow[ctc_prefix::kMaxK][64];                      // [slot]: the LM's log-softmax row after the text
+  };
+  const CtcLmDev& a;
+  float *st, *stage, *lmx, *gi, *gh, *lmlg;                  // the utterance's blocks of the workspace
+  int lm_frames = 0;
+
+  __device__ explicit CtcLmTerm(const CtcLmDev& dev)
+      : Scored{dev.lm.H > 0, dev.length_bonus != 0.f, (double)dev.lm_weight, (double)dev.length_bonus, dev.ctc_scores,
+               dev.lm_scores},
+        a(dev) {
+    const CtcLmWs m = ctc_lm_ws_map(dev.d.K, dev.lm.H);
+    float* ws = dev.fws + (int64_t)blockIdx.x * m.total;
+    st = ws + m.st; stage = ws + m.stage; lmx = ws + m.lmx; gi = ws + m.gi; gh = ws + m.gh; lmlg = ws + m.lmlg;
   }
-  float x_next = (wave == 0 && lane < V && len > 0) ? logits[lane] : -INFINITY;
-  if (use_lm) {                                              // the empty text's row: <SOS> = 0 from zero states
+
+  __device__ void init(Mem& m, int V) const {                // the empty text's row: <SOS> = 0 from zero states
+    if (!on) return;
+    const int tid = threadIdx.x, H = a.lm.H, Sz = 2 * H;
     for (int i = tid; i < Sz; i += kThreads) stage[i] = 0.f;
     for (int i = tid; i < H; i += kThreads) lmx[i] = a.lm.emb[i];
     phase_sync();
     ctc_lm_step(a.lm, V, stage, lmx, gi, gh, lmlg, 1);
-    if (wave == 0) {
+    if (tid < 64) {
       const float r = score_row(lmlg, nullptr, V, 0.f);
-      lmrow[0][lane] = lane < V ? r : 0.f;
+      m.lmrow[0][tid] = tid < V ? r : 0.f;
     }
     for (int i = tid; i < Sz; i += kThreads) st[i] = stage[i];
+    __threadfence_block();                                   // with the body's barrier: a phase_sync()
   }
-  phase_sync();
-  for (int t = 0; t < len; ++t) {
-    const int32_t* told = text + (int64_t)cur * K * T;
-    int32_t* tnew = text + (int64_t)(cur ^ 1) * K * T;
-    for (int i = tid; i < K * V; i += kThreads) child[i] = -1;
-    if (wave == 0) {                                         // the row's log-softmax (ctc_table's normaliser)
-      const float x = x_next;
-      if (t + 1 < len && lane < V) x_next = logits[(int64_t)(t + 1) * V + lane];
-      const float mx = wave_max(x);
-      const float s = wave_sum(lane < V ? expf(x - mx) : 0.f);
-      const double lse = (double)mx + (double)logf(s);
-      if (lane < V) lpd[lane] = (double)x - lse;
+  __device__ double step(const Mem& m, int cur, int u, int c) const { return (double)m.lmrow[m.slot[cur][u]][c]; }
+  __device__ void keep(Mem&, int, int, int, int) const {}
+  __device__ void inherit(Mem&, int, int, int, int, int) const {}
+  // the new members' LM step
+  template <class S>
+  __device__ void after_commit(S& s, int cur, int nxt, int K, int V) {
+    Mem& m = s.tm;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, H = a.lm.H, Sz = 2 * H;
+    const int ne = on ? m.n_ext : 0;
+    if (ne == 0) return;
+    ++lm_frames;
+    for (int i = tid; i < ne * Sz; i += kThreads) {          // every parent's state, before any slot is written
+      const int e = i / Sz, u = (s.win[m.ext[e]] - K) / V;
+      stage[i] = st[(int64_t)m.slot[cur][u] * Sz + i % Sz];
     }
-    __syncthreads();
-    // each member's parent among the members: a lane per possible parent filters, the wave compares the characters
-    for (int w = wave; w < n; w += kWaves) {
-      const int lw = tlen[cur][w];
-      int found = -1;
-      if (lw >= 1) {
-        unsigned long long mask = __ballot(lane < n && tlen[cur][lane < n ? lane : 0] == lw - 1 &&
-                                           hs[cur][lane < n ? lane : 0] == hp[cur][w]);
-        while (mask != 0 && found < 0) {                     // at most n turns
-          const int u = __ffsll((long long)mask) - 1;
-          mask &= mask - 1;
-          int differ = 0;
-          for (int i = lane; i < lw - 1; i += 64) differ |= told[(int64_t)w * T + i] != told[(int64_t)u * T + i];
-          if (!__any(differ)) found = u;
-        }
-        if (lane == 0 && found >= 0) child[found * V + tlast[cur][w]] = (signed char)w;
+    for (int e0 = 0; e0 < ne; e0 += kHyps) {
+      const int nb = min(kHyps, ne - e0);
+      for (int i = tid; i < nb * H; i += kThreads) {
+        const int c = (s.win[m.ext[e0 + i / H]] - K) % V;
+        lmx[i] = a.lm.emb[(int64_t)c * H + i % H];
       }
-      if (lane == 0) par[w] = found;
-    }
-    __syncthreads();
-    // the candidates' keys: the CTC total, + lm_weight L(w) + length_bonus |w|; each thread remembers its best
-    const double lpb = lpd[blank];
-    double best = kNegInf;
-    int bidx = INT32_MAX;
-    for (int idx = tid; idx < ncand; idx += kThreads) {
-      double v = kNegInf;
-      if (idx < K) {
-        const int w = idx;
-        if (w < n) {
-          const double nb = lpb + ctc_lm_lae(gb[cur][w], gn[cur][w]);
-          double nn = kNegInf;
-          const int c = tlast[cur][w];
-          if (c >= 0) {
-            const int p = par[w];
-            double via = kNegInf;
-            if (p >= 0) via = tlast[cur][p] == c ? gb[cur][p] : ctc_lm_lae(gb[cur][p], gn[cur][p]);
-            nn = lpd[c] + ctc_lm_lae(gn[cur][w], via);
-          }
-          sgb[w] = nb;
-          sgn[w] = nn;
-          v = ctc_lm_lae(nb, nn);
-          if (v > kNegInf) {
-            if (use_lm) v += alpha * Lm[cur][w];
-            if (use_len) v += beta * (double)tlen[cur][w];
-          }
-        }
-      } else {
-        const int u = (idx - K) / V, c = (idx - K) % V;
-        if (u < n && c != blank && child[u * V + c] < 0) {
-          v = lpd[c] + (tlast[cur][u] == c ? gb[cur][u] : ctc_lm_lae(gb[cur][u], gn[cur][u]));
-          if (v > kNegInf) {
-            if (use_lm) v += alpha * (Lm[cur][u] + (double)lmrow[slot[cur][u]][c]);
-            if (use_len) v += beta * (double)(tlen[cur][u] + 1);
-          }
-        }
-      }
-      tot[idx] = v;
-      if (v > best) { best = v; bidx = idx; }
-    }
-    // B_t: K rounds of a block-wide argmax (the lowest index among equals), the winner leaving the pool
-    int n_new = 0;
-    for (int r = 0; r < K; ++r) {
-      double mv = best;
-      int mi = bidx;
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) {
-        const double om = __shfl_xor(mv, off);
-        const int oi = __shfl_xor(mi, off);
-        if (om > mv || (om == mv && oi < mi)) { mv = om; mi = oi; }
-      }
-      if (lane == 0) { wv[r & 1][wave] = mv; wi[r & 1][wave] = mi; }
-      __syncthreads();
-      double gm = wv[r & 1][0];
-      int gidx = wi[r & 1][0];
-#pragma unroll
-      for (int w = 1; w < kWaves; ++w) {
-        const double om = wv[r & 1][w];
-        const int oi = wi[r & 1][w];
-        if (om > gm || (om == gm && oi < gidx)) { gm = om; gidx = oi; }
-      }
-      if (!(gm > kNegInf)) break;                            // fewer finite candidates than K
-      if (tid == 0) win[r] = gidx;
-      n_new = r + 1;
-      if (gidx % kThreads == tid) {
-        tot[gidx] = kNegInf;
-        best = kNegInf;
-        bidx = INT32_MAX;
-        for (int idx = tid; idx < ncand; idx += kThreads) {
-          const double v = tot[idx];
-          if (v > best) { best = v; bidx = idx; }
-        }
-      }
-    }
-    __syncthreads();
-    // the winners become B_t: scalars, then texts.  A new extension's g_n' is its CTC total, formed again as above.
-    const int nxt = cur ^ 1;
-    if (tid < n_new) {
-      const int w = win[tid];
-      if (w < K) {
-        gb[nxt][tid] = sgb[w]; gn[nxt][tid] = sgn[w]; Lm[nxt][tid] = Lm[cur][w];
-        hs[nxt][tid] = hs[cur][w]; hp[nxt][tid] = hp[cur][w];
-        tlen[nxt][tid] = tlen[cur][w]; tlast[nxt][tid] = tlast[cur][w];
-        slot[nxt][tid] = slot[cur][w];
-      } else {
-        const int u = (w - K) / V, c = (w - K) % V;
-        gb[nxt][tid] = kNegInf;
-        gn[nxt][tid] = lpd[c] + (tlast[cur][u] == c ? gb[cur][u] : ctc_lm_lae(gb[cur][u], gn[cur][u]));
-        Lm[nxt][tid] = use_lm ? Lm[cur][u] + (double)lmrow[slot[cur][u]][c] : 0.0;
-        hs[nxt][tid] = hs[cur][u] * kCtcLmHashMul + (unsigned long long)(c + 1); hp[nxt][tid] = hs[cur][u];
-        tlen[nxt][tid] = tlen[cur][u] + 1; tlast[nxt][tid] = c;
-      }
-    }
-    if (tid == 0) {                                          // slots: the kept members' stay taken, the rest is free
-      unsigned used = 0;
-      for (int j = 0; j < n_new; ++j)
-        if (win[j] < K) used |= 1u << slot[cur][win[j]];
-      int ne = 0;
-      for (int j = 0; j < n_new; ++j)
-        if (win[j] >= K) {
-          const int s = __ffs((int)~used) - 1;               // K members at most: a bit below K is clear
-          used |= 1u << s;
-          slot[nxt][j] = s;
-          ext[ne++] = j;
-        }
-      n_ext_sh = ne;
-    }
-    for (int j = 0; j < n_new; ++j) {
-      const int w = win[j];
-      const int src = w < K ? w : (w - K) / V;
-      const int l = tlen[cur][src];                          // l <= t < T: the appended character stays in the row
-      for (int i = tid; i < l; i += kThreads) tnew[(int64_t)j * T + i] = told[(int64_t)src * T + i];
-      if (w >= K && tid == 0) tnew[(int64_t)j * T + l] = (w - K) % V;
-    }
-    __syncthreads();
-    const int ne = use_lm ? n_ext_sh : 0;
-    if (ne > 0) {                                            // the new members' LM step
-      ++lm_frames;
-      for (int i = tid; i < ne * Sz; i += kThreads) {        // every parent's state, before any slot is written
-        const int e = i / Sz, u = (win[ext[e]] - K) / V;
-        stage[i] = st[(int64_t)slot[cur][u] * Sz + i % Sz];
-      }
-      for (int e0 = 0; e0 < ne; e0 += kHyps) {
-        const int nb = min(kHyps, ne - e0);
-        for (int i = tid; i < nb * H; i += kThreads) {
-          const int c = (win[ext[e0 + i / H]] - K) % V;
-          lmx[i] = a.lm.emb[(int64_t)c * H + i % H];
-        }
-        phase_sync();
-        ctc_lm_step(a.lm, V, stage + (int64_t)e0 * Sz, lmx, gi, gh, lmlg, nb);
-        for (int e = wave; e < nb; e += kWaves) {
-          const float r = score_row(lmlg + e * 64, nullptr, V, 0.f);
-          lmrow[slot[nxt][ext[e0 + e]]][lane] = lane < V ? r : 0.f;
-        }
-      }
-      for (int i = tid; i < ne * Sz; i += kThreads) st[(int64_t)slot[nxt][ext[i / Sz]] * Sz + i % Sz] = stage[i];
       phase_sync();
-    }
-    cur = nxt;
-    n = n_new;
-  }
-  // the totals, with the end term; ranked by counting as rescore_kernel ranks (without an end term the members are
-  // in the order they won, which is this order)
-  if (tid < K) {
-    float key = -INFINITY, total = -INFINITY, ctc = -INFINITY, lmv = 0.f;
-    if (tid < n) {
-      const double c = ctc_lm_lae(gb[cur][tid], gn[cur][tid]);
-      double l = 0.0, tv = c;
-      if (use_lm) {
-        l = Lm[cur][tid];
-        tv += alpha * l;
+      ctc_lm_step(a.lm, V, stage + (int64_t)e0 * Sz, lmx, gi, gh, lmlg, nb);
+      for (int e = wave; e < nb; e += kWaves) {
+        const float r = score_row(lmlg + e * 64, nullptr, V, 0.f);
+        m.lmrow[m.slot[nxt][m.ext[e0 + e]]][lane] = lane < V ? r : 0.f;
       }
-      if (use_len) tv += beta * (double)tlen[cur][tid];
-      if (use_lm && a.eos >= 0) {
-        const double e = (double)lmrow[slot[cur][tid]][a.eos];
-        l += e;
-        tv += alpha * e;
-      }
-      total = (float)tv; ctc = (float)c; lmv = (float)l;
-      key = total != total ? -INFINITY : total;
     }
-    fkey[tid] = key; ftot[tid] = total; fctc[tid] = ctc; flm[tid] = lmv;
-    fsrc[tid] = -1;
+    for (int i = tid; i < ne * Sz; i += kThreads) st[(int64_t)m.slot[nxt][m.ext[i / Sz]] * Sz + i % Sz] = stage[i];
+    phase_sync();
   }
-  __syncthreads();
-  if (tid < n) {
-    const float key = fkey[tid];
-    int rank = 0;
-    for (int j = 0; j < n; ++j) rank += (fkey[j] > key || (fkey[j] == key && j < tid)) ? 1 : 0;
-    fsrc[rank] = tid;
-  }
-  __syncthreads();
-  const int32_t* tfin = text + (int64_t)cur * K * T;
-  for (int j = 0; j < K; ++j) {
-    const int src = fsrc[j];
-    const int l = src >= 0 ? tlen[cur][src] : 0;
-    int32_t* out = a.chars + ((int64_t)b * K + j) * T;
-    for (int i = tid; i < T; i += kThreads) out[i] = i < l ? tfin[(int64_t)src * T + i] : 0;
-  }
-  if (tid < K) {
-    const int src = fsrc[tid];
-    const int64_t o = (int64_t)b * K + tid;
-    a.n_chars[o] = src >= 0 ? tlen[cur][src] : 0;
-    a.scores[o] = src >= 0 ? ftot[src] : -INFINITY;
-    a.ctc_scores[o] = src >= 0 ? fctc[src] : -INFINITY;
-    a.lm_scores[o] = src >= 0 ? flm[src] : 0.f;
-  }
-  if (tid == 0) {
-    a.n_hyps[b] = n;
-    a.lm_frames[b] = lm_frames;
-  }
+  __device__ bool has_end() const { return a.eos >= 0; }
+  __device__ double end(const Mem& m, int cur, int j) const { return (double)m.lmrow[m.slot[cur][j]][a.eos]; }
+};
+
+__global__ __launch_bounds__(kThreads) void ctc_prefix_beam_lm_kernel(CtcLmDev a) {
+  __shared__ ctc_prefix::State<kThreads, CtcLmTerm> s;
+  CtcLmTerm term(a);
+  ctc_prefix::search(a.d, term, s);
+  if (threadIdx.x == 0) a.lm_frames[blockIdx.x] = term.lm_frames;
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -1810,8 +1594,7 @@ extern "C" int ssasr_charlm_step(const ssasr_charlm* lm, const int32_t* x, const
 namespace {
 
 bool ctc_lm_shape_ok(int64_t B, int64_t T, int64_t V, int64_t K, int64_t H) {
-  return B >= 1 && B <= 65535 && T >= 1 && T <= kCtcLmMaxT && V >= 2 && V <= kCtcLmMaxV && K >= 1 && K <= kCtcLmMaxK &&
-         H >= 0 && H <= 4096 && H % 4 == 0;
+  return ctc_prefix::shape_ok(B, T, V, K) && H >= 0 && H <= 4096 && H % 4 == 0;
 }
 
 // bytes of the float blocks, then of the texts; the lm_frames words follow
@@ -1839,15 +1622,14 @@ extern "C" int ssasr_ctc_decode_lm(const float* logits, const int32_t* frame_len
   const int64_t H = a.lm.H;
   if (!ctc_lm_shape_ok(B, T, V, K, H) || blank < 0 || blank >= V) return SSASR_EARG;
   if (!aligned16(ws) || ws_bytes < ssasr_ctc_decode_lm_ws_bytes(B, T, V, K, H)) return SSASR_EARG;
-  a.logits = logits; a.frame_lens = frame_lens;
-  a.T = (int)T; a.V = (int)V; a.K = (int)K; a.blank = blank; a.eos = eos < 0 ? -1 : eos;
-  a.lm_weight = lm_weight; a.length_bonus = length_bonus;
   char* base = reinterpret_cast<char*>(ws);
+  a.d = ctc_prefix::make_args(logits, frame_lens, T, V, K, blank, base + ctc_lm_float_bytes(B, K, H), chars, n_chars,
+                              scores, n_hyps);
+  a.eos = eos < 0 ? -1 : eos;
+  a.lm_weight = lm_weight; a.length_bonus = length_bonus;
   a.fws = reinterpret_cast<float*>(base);
-  a.text = reinterpret_cast<int32_t*>(base + ctc_lm_float_bytes(B, K, H));
   a.lm_frames = reinterpret_cast<int32_t*>(base + ctc_lm_float_bytes(B, K, H) + ctc_lm_text_bytes(B, T, K));
-  a.chars = chars; a.n_chars = n_chars; a.scores = scores; a.ctc_scores = ctc_scores; a.lm_scores = lm_scores;
-  a.n_hyps = n_hyps;
+  a.ctc_scores = ctc_scores; a.lm_scores = lm_scores;
   hipLaunchKernelGGL(ctc_prefix_beam_lm_kernel, dim3((unsigned)B), dim3(kThreads), 0, (hipStream_t)stream, a);
   SSASR_LAUNCH_CHECK();
   return SSASR_OK;

@@ -904,12 +904,26 @@ def masked_ce_loss(logits, y, ans_len, label_smoothing=0.0):
 # ---------------------------------------------------------------------------
 # CTC branch (build-defined: the reference has no CTC; checker = torch's ctc_loss)
 # ---------------------------------------------------------------------------
+def _ctc_label_matrix(name, y32, lmax):
+    """The label matrix every CTC kernel reads: int32 with unit column stride, at least lmax columns."""
+    if y32.dtype != torch.int32 or y32.stride(-1) != 1:
+        raise TypeError('%s: labels must be int32 with unit column stride' % name)
+    if lmax > y32.shape[1]:
+        raise ValueError('%s: Lmax exceeds the label matrix' % name)
+
+
+def _ctc_head_logits(feat, weight, bias):
+    """The CTC head's product feat @ weight.T + bias, issued one way by the training node and by every decoder,
+    aligner and segmenter.  -> (logits [B, T, V], and the contiguous float32 feat and weight the product read)."""
+    _need_gpu(feat, weight, bias)
+    feat, w, b = _f32c(feat), _f32c(weight), _f32c(bias)
+    B, T, E = feat.shape
+    return gemm(feat.view(B * T, E), w, bias=b).view(B, T, w.shape[0]), feat, w
+
+
 def _ctc_geometry(logits, y32, lmax):
     B, T, V = logits.shape
-    if y32.dtype != torch.int32 or y32.stride(-1) != 1:
-        raise TypeError('ctc: labels must be int32 with unit column stride')
-    if lmax > y32.shape[1]:
-        raise ValueError('ctc: Lmax exceeds the label matrix')
+    _ctc_label_matrix('ctc', y32, lmax)
     n = _lib.load().ssasr_ctc_ws_floats(B, T, V, lmax)
     if n <= 0:
         raise ValueError('ctc: shape B=%d T=%d V=%d Lmax=%d has no kernel' % (B, T, V, lmax))
@@ -959,10 +973,8 @@ class _CTCHead(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat, w, b, frame_lens, y32, label_lens, lmax, blank):
-        _need_gpu(feat, w, b, frame_lens, y32, label_lens)
-        feat, w, b = _f32c(feat), _f32c(w), _f32c(b)
-        B, T, E = feat.shape
-        logits = gemm(feat.view(B * T, E), w, bias=b).view(B, T, w.shape[0])
+        _need_gpu(frame_lens, y32, label_lens)
+        logits, feat, w = _ctc_head_logits(feat, w, b)
         loss, ws = _ctc_fwd(logits, frame_lens, y32, label_lens, lmax, blank)
         ctx.save_for_backward(feat, w, logits, frame_lens, y32, label_lens, ws)
         ctx.geom = (lmax, blank)
@@ -1003,10 +1015,7 @@ def ctc_align(logits, frame_lens, y32, label_lens, lmax, blank=0):
     _need_gpu(logits, frame_lens, y32, label_lens)
     logits = _f32c(logits.detach())
     B, T, V = logits.shape
-    if y32.dtype != torch.int32 or y32.stride(-1) != 1:
-        raise TypeError('ctc_align: labels must be int32 with unit column stride')
-    if lmax > y32.shape[1]:
-        raise ValueError('ctc_align: Lmax exceeds the label matrix')
+    _ctc_label_matrix('ctc_align', y32, lmax)
     need = int(lib.ssasr_ctc_align_ws_bytes(B, T, V, lmax))
     if need <= 0:
         raise ValueError('ctc_align: shape B=%d T=%d V=%d Lmax=%d has no kernel' % (B, T, V, lmax))
@@ -1026,10 +1035,7 @@ def ctc_align(logits, frame_lens, y32, label_lens, lmax, blank=0):
 def ctc_head_align(feat, weight, bias, frame_lens, y32, label_lens, lmax, blank=0):
     """ctc_align on the head's logits, the product issued exactly as the training node issues it (_CTCHead.forward).
     -> ctc_align's five tensors and the logits [B, T, V] they were aligned on.  No autograd."""
-    _need_gpu(feat, weight, bias)
-    feat, w, b = _f32c(feat.detach()), _f32c(weight.detach()), _f32c(bias.detach())
-    B, T, E = feat.shape
-    logits = gemm(feat.view(B * T, E), w, bias=b).view(B, T, w.shape[0])
+    logits = _ctc_head_logits(feat.detach(), weight.detach(), bias.detach())[0]
     return ctc_align(logits, frame_lens, y32, label_lens, lmax, blank) + (logits,)
 
 
@@ -1123,16 +1129,45 @@ def ctc_head_segment(feat, weight, bias, frame_lens, y32, label_lens, utt_ends, 
     """ctc_segment on the head's logits, the product issued exactly as the training node issues it (_CTCHead.forward).
     -> ctc_segment's eight (with a penalty: ten) tensors and the logits [B, T, V] they were computed on.  No
     autograd."""
-    _need_gpu(feat, weight, bias)
-    feat, w, b = _f32c(feat.detach()), _f32c(weight.detach()), _f32c(bias.detach())
-    B, T, E = feat.shape
-    logits = gemm(feat.view(B * T, E), w, bias=b).view(B, T, w.shape[0])
+    logits = _ctc_head_logits(feat.detach(), weight.detach(), bias.detach())[0]
     return ctc_segment(logits, frame_lens, y32, label_lens, utt_ends, n_utts, lmax, nmax, window, blank,
                        skip_penalty=skip_penalty, fill_penalty=fill_penalty) + (logits,)
 
 
 CTC_DECODE_MAX_BEAM = 32       # ssasr_ctc_decode's limits (include/ssasr.h)
 CTC_DECODE_MAX_FRAMES = 4096
+
+
+def _prefix_search_entry(name, logits, frame_lens, beam_size, blank, score_names, term=None, classes=None):
+    """What ctc_decode, ctc_decode_lm and ctc_decode_graph (`name`) do before their launch: the checks of beam_size
+    (from 0 without a `term`, from 1 and an int with one: 'LM' or 'graph', the word the message uses), of logits,
+    frame_lens and blank, then classes(V) (the caller's own checks against the number of classes), then the tensors'
+    device.  -> (logits float32 contiguous, (B, T, V), the outputs: chars [B, Kr, T], n_chars [B, Kr], n_hyps [B]
+    int32 and a float32 [B, Kr] per name in score_names, Kr = max(beam_size, 1))."""
+    if isinstance(beam_size, bool) or not isinstance(beam_size, int) or \
+            not (0 if term is None else 1) <= beam_size <= CTC_DECODE_MAX_BEAM:
+        if term is None:
+            raise ValueError('%s: beam_size must be in 0..%d, got %d' % (name, CTC_DECODE_MAX_BEAM, beam_size))
+        raise ValueError('%s: beam_size must be an int in 1..%d (the best path has no %s form), got %r'
+                         % (name, CTC_DECODE_MAX_BEAM, term, beam_size))
+    if logits.dim() != 3:
+        raise ValueError('%s: logits must be [B, T, V], got %r' % (name, tuple(logits.shape)))
+    if frame_lens.dtype != torch.int32 or frame_lens.numel() != logits.shape[0]:
+        raise TypeError('%s: frame_lens must be int32 [B]' % name)
+    B, T, V = logits.shape
+    if not 0 <= blank < V:
+        raise ValueError('%s: blank %d is no class of V=%d' % (name, blank, V))
+    if classes is not None:
+        classes(V)
+    _need_gpu(logits, frame_lens)
+    logits = _f32c(logits.detach())
+    dev, kr = logits.device, max(beam_size, 1)
+    out = {'chars': torch.empty(B, kr, T, device=dev, dtype=torch.int32),
+           'n_chars': torch.empty(B, kr, device=dev, dtype=torch.int32),
+           'n_hyps': torch.empty(B, device=dev, dtype=torch.int32)}
+    for score in score_names:
+        out[score] = torch.empty(B, kr, device=dev, dtype=torch.float32)
+    return logits, (B, T, V), out
 
 
 def ctc_decode(logits, frame_lens, beam_size, blank=0):
@@ -1143,38 +1178,21 @@ def ctc_decode(logits, frame_lens, beam_size, blank=0):
     and score -inf.  No autograd."""
     lib = _lib.load()
     beam_size, blank = int(beam_size), int(blank)
-    _need_gpu(logits, frame_lens)
-    logits = _f32c(logits.detach())
-    if logits.dim() != 3:
-        raise ValueError('ctc_decode: logits must be [B, T, V], got %r' % (tuple(logits.shape),))
-    if frame_lens.dtype != torch.int32 or frame_lens.numel() != logits.shape[0]:
-        raise TypeError('ctc_decode: frame_lens must be int32 [B]')
-    B, T, V = logits.shape
-    if not 0 <= beam_size <= CTC_DECODE_MAX_BEAM:
-        raise ValueError('ctc_decode: beam_size must be in 0..%d, got %d' % (CTC_DECODE_MAX_BEAM, beam_size))
-    if not 0 <= blank < V:
-        raise ValueError('ctc_decode: blank %d is no class of V=%d' % (blank, V))
+    logits, (B, T, V), out = _prefix_search_entry('ctc_decode', logits, frame_lens, beam_size, blank, ('scores',))
     need = int(lib.ssasr_ctc_decode_ws_bytes(B, T, V, beam_size))
     if need <= 0:
         raise ValueError('ctc_decode: shape B=%d T=%d V=%d beam_size=%d has no kernel' % (B, T, V, beam_size))
-    dev, kr = logits.device, max(beam_size, 1)
-    ws = torch.empty((need + 7) // 8, device=dev, dtype=torch.int64)
-    chars = torch.empty(B, kr, T, device=dev, dtype=torch.int32)
-    n_chars = torch.empty(B, kr, device=dev, dtype=torch.int32)
-    scores = torch.empty(B, kr, device=dev, dtype=torch.float32)
-    n_hyps = torch.empty(B, device=dev, dtype=torch.int32)
+    ws = torch.empty((need + 7) // 8, device=logits.device, dtype=torch.int64)
     check(lib.ssasr_ctc_decode(_p(logits), _p(frame_lens.contiguous()), B, T, V, beam_size, blank, _p(ws), ws.numel() * 8,
-                               _p(chars), _p(n_chars), _p(scores), _p(n_hyps), _stream()), 'ssasr_ctc_decode')
-    return chars, n_chars, scores, n_hyps
+                               _p(out['chars']), _p(out['n_chars']), _p(out['scores']), _p(out['n_hyps']), _stream()),
+          'ssasr_ctc_decode')
+    return out['chars'], out['n_chars'], out['scores'], out['n_hyps']
 
 
 def ctc_head_decode(feat, weight, bias, frame_lens, beam_size, blank=0):
     """ctc_decode on the head's logits, the product issued exactly as the training node issues it (_CTCHead.forward).
     -> ctc_decode's four tensors and the logits [B, T, V] they were decoded from.  No autograd."""
-    _need_gpu(feat, weight, bias)
-    feat, w, b = _f32c(feat.detach()), _f32c(weight.detach()), _f32c(bias.detach())
-    B, T, E = feat.shape
-    logits = gemm(feat.view(B * T, E), w, bias=b).view(B, T, w.shape[0])
+    logits = _ctc_head_logits(feat.detach(), weight.detach(), bias.detach())[0]
     return ctc_decode(logits, frame_lens, beam_size, blank) + (logits,)
 
 
@@ -1187,39 +1205,25 @@ def ctc_decode_lm(logits, frame_lens, beam_size, lm, lm_weight=0.0, length_bonus
     weights the first four are ctc_decode's bits.  No autograd."""
     lib = _lib.load()
     blank, eos, lm_weight, length_bonus = int(blank), int(eos), float(lm_weight), float(length_bonus)
-    if isinstance(beam_size, bool) or not isinstance(beam_size, int) or not 1 <= beam_size <= CTC_DECODE_MAX_BEAM:
-        raise ValueError('ctc_decode_lm: beam_size must be an int in 1..%d (the best path has no LM form), got %r'
-                         % (CTC_DECODE_MAX_BEAM, beam_size))
     if not (math.isfinite(lm_weight) and math.isfinite(length_bonus)):
         raise ValueError('ctc_decode_lm: lm_weight and length_bonus must be finite, got %r, %r'
                          % (lm_weight, length_bonus))
     if lm is None and lm_weight != 0.0:
         raise ValueError('ctc_decode_lm: lm_weight %g needs a language model' % lm_weight)
-    if logits.dim() != 3:
-        raise ValueError('ctc_decode_lm: logits must be [B, T, V], got %r' % (tuple(logits.shape),))
-    if frame_lens.dtype != torch.int32 or frame_lens.numel() != logits.shape[0]:
-        raise TypeError('ctc_decode_lm: frame_lens must be int32 [B]')
-    B, T, V = logits.shape
-    if not 0 <= blank < V:
-        raise ValueError('ctc_decode_lm: blank %d is no class of V=%d' % (blank, V))
-    if eos >= V:
-        raise ValueError('ctc_decode_lm: eos %d is no class of V=%d' % (eos, V))
-    if lm is not None and lm.input_size != V:
-        raise ValueError('ctc_decode_lm: the language model has %d classes, the logits %d' % (lm.input_size, V))
-    _need_gpu(logits, frame_lens)
-    logits = _f32c(logits.detach())
+
+    def classes(V):
+        if eos >= V:
+            raise ValueError('ctc_decode_lm: eos %d is no class of V=%d' % (eos, V))
+        if lm is not None and lm.input_size != V:
+            raise ValueError('ctc_decode_lm: the language model has %d classes, the logits %d' % (lm.input_size, V))
+    logits, (B, T, V), out = _prefix_search_entry('ctc_decode_lm', logits, frame_lens, beam_size, blank,
+                                                  ('scores', 'ctc_scores', 'lm_scores'), term='LM', classes=classes)
     s, keep = _charlm_struct(lm) if lm is not None else (None, None)
     H = lm.hidden_size if lm_weight != 0.0 else 0
     need = int(lib.ssasr_ctc_decode_lm_ws_bytes(B, T, V, beam_size, H))
     if need <= 0:
         raise ValueError('ctc_decode_lm: shape B=%d T=%d V=%d beam_size=%d H=%d has no kernel' % (B, T, V, beam_size, H))
-    dev = logits.device
-    ws = torch.empty((need + 15) // 16 * 2, device=dev, dtype=torch.int64)
-    out = {'chars': torch.empty(B, beam_size, T, device=dev, dtype=torch.int32),
-           'n_chars': torch.empty(B, beam_size, device=dev, dtype=torch.int32),
-           'n_hyps': torch.empty(B, device=dev, dtype=torch.int32)}
-    for name in ('scores', 'ctc_scores', 'lm_scores'):
-        out[name] = torch.empty(B, beam_size, device=dev, dtype=torch.float32)
+    ws = torch.empty((need + 15) // 16 * 2, device=logits.device, dtype=torch.int64)
     check(lib.ssasr_ctc_decode_lm(_p(logits), _p(frame_lens.contiguous()), B, T, V, beam_size, blank, _p(ws),
                                   ws.numel() * 8, _p(out['chars']), _p(out['n_chars']), _p(out['scores']),
                                   _p(out['n_hyps']), C.byref(s) if s is not None else None, lm_weight, length_bonus,
@@ -1231,10 +1235,7 @@ def ctc_decode_lm(logits, frame_lens, beam_size, lm, lm_weight=0.0, length_bonus
 def ctc_head_decode_lm(feat, weight, bias, frame_lens, beam_size, lm, lm_weight=0.0, length_bonus=0.0, eos=1, blank=0):
     """ctc_decode_lm on the head's logits, the product issued as ctc_head_decode issues it.  -> ctc_decode_lm's dict
     with the logits [B, T, V] they were decoded from under 'logits'.  No autograd."""
-    _need_gpu(feat, weight, bias)
-    feat, w, b = _f32c(feat.detach()), _f32c(weight.detach()), _f32c(bias.detach())
-    B, T, E = feat.shape
-    logits = gemm(feat.view(B * T, E), w, bias=b).view(B, T, w.shape[0])
+    logits = _ctc_head_logits(feat.detach(), weight.detach(), bias.detach())[0]
     out = ctc_decode_lm(logits, frame_lens, beam_size, lm, lm_weight, length_bonus, eos, blank)
     out['logits'] = logits
     return out
@@ -1250,9 +1251,6 @@ def ctc_decode_graph(logits, frame_lens, beam_size, graph, graph_weight=0.0, len
     from .char_graph import CharGraph
     lib = _lib.load()
     blank, graph_weight, length_bonus = int(blank), float(graph_weight), float(length_bonus)
-    if isinstance(beam_size, bool) or not isinstance(beam_size, int) or not 1 <= beam_size <= CTC_DECODE_MAX_BEAM:
-        raise ValueError('ctc_decode_graph: beam_size must be an int in 1..%d (the best path has no graph form), got %r'
-                         % (CTC_DECODE_MAX_BEAM, beam_size))
     if not (math.isfinite(graph_weight) and graph_weight >= 0.0 and math.isfinite(length_bonus)):
         raise ValueError('ctc_decode_graph: graph_weight must be finite and >= 0 and length_bonus finite, got %r, %r'
                          % (graph_weight, length_bonus))
@@ -1260,28 +1258,18 @@ def ctc_decode_graph(logits, frame_lens, beam_size, graph, graph_weight=0.0, len
         raise ValueError('ctc_decode_graph: graph_weight %g needs a graph' % graph_weight)
     if graph is not None and not isinstance(graph, CharGraph):
         raise TypeError('ctc_decode_graph: graph must be a char_graph.CharGraph, got %s' % type(graph).__name__)
-    if logits.dim() != 3:
-        raise ValueError('ctc_decode_graph: logits must be [B, T, V], got %r' % (tuple(logits.shape),))
-    if frame_lens.dtype != torch.int32 or frame_lens.numel() != logits.shape[0]:
-        raise TypeError('ctc_decode_graph: frame_lens must be int32 [B]')
-    B, T, V = logits.shape
-    if not 0 <= blank < V:
-        raise ValueError('ctc_decode_graph: blank %d is no class of V=%d' % (blank, V))
-    if graph is not None and graph.n_classes != V:
-        raise ValueError('ctc_decode_graph: the graph has %d classes, the logits %d' % (graph.n_classes, V))
-    _need_gpu(logits, frame_lens)
-    logits = _f32c(logits.detach())
+
+    def classes(V):
+        if graph is not None and graph.n_classes != V:
+            raise ValueError('ctc_decode_graph: the graph has %d classes, the logits %d' % (graph.n_classes, V))
+    logits, (B, T, V), out = _prefix_search_entry('ctc_decode_graph', logits, frame_lens, beam_size, blank,
+                                                  ('scores', 'ctc_scores', 'graph_scores'), term='graph',
+                                                  classes=classes)
     s, keep = graph.to(logits.device) if graph is not None else (None, None)
     need = int(lib.ssasr_ctc_decode_graph_ws_bytes(B, T, V, beam_size))
     if need <= 0:
         raise ValueError('ctc_decode_graph: shape B=%d T=%d V=%d beam_size=%d has no kernel' % (B, T, V, beam_size))
-    dev = logits.device
-    ws = torch.empty((need + 7) // 8, device=dev, dtype=torch.int64)
-    out = {'chars': torch.empty(B, beam_size, T, device=dev, dtype=torch.int32),
-           'n_chars': torch.empty(B, beam_size, device=dev, dtype=torch.int32),
-           'n_hyps': torch.empty(B, device=dev, dtype=torch.int32)}
-    for name in ('scores', 'ctc_scores', 'graph_scores'):
-        out[name] = torch.empty(B, beam_size, device=dev, dtype=torch.float32)
+    ws = torch.empty((need + 7) // 8, device=logits.device, dtype=torch.int64)
     check(lib.ssasr_ctc_decode_graph(_p(logits), _p(frame_lens.contiguous()), B, T, V, beam_size, blank, _p(ws),
                                      ws.numel() * 8, _p(out['chars']), _p(out['n_chars']), _p(out['scores']),
                                      _p(out['n_hyps']), C.byref(s) if s is not None else None, graph_weight,
@@ -1293,10 +1281,7 @@ def ctc_decode_graph(logits, frame_lens, beam_size, graph, graph_weight=0.0, len
 def ctc_head_decode_graph(feat, weight, bias, frame_lens, beam_size, graph, graph_weight=0.0, length_bonus=0.0, blank=0):
     """ctc_decode_graph on the head's logits, the product issued as ctc_head_decode issues it.  -> ctc_decode_graph's
     dict with the logits [B, T, V] they were decoded from under 'logits'.  No autograd."""
-    _need_gpu(feat, weight, bias)
-    feat, w, b = _f32c(feat.detach()), _f32c(weight.detach()), _f32c(bias.detach())
-    B, T, E = feat.shape
-    logits = gemm(feat.view(B * T, E), w, bias=b).view(B, T, w.shape[0])
+    logits = _ctc_head_logits(feat.detach(), weight.detach(), bias.detach())[0]
     out = ctc_decode_graph(logits, frame_lens, beam_size, graph, graph_weight, length_bonus, blank)
     out['logits'] = logits
     return out

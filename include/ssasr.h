@@ -1088,6 +1088,62 @@ int ssasr_ctc_decode_graph(const float* logits, const int32_t* frame_lens, int64
                            int32_t* n_hyps, const ssasr_char_graph* graph, float graph_weight, float length_bonus,
                            float* ctc_scores, float* graph_scores, void* stream);
 
+/* ---- CTC decoding over a lexicon with a word n-gram LM inside the prefix search (added under ABI 16) ---------------
+ * BUILD-DEFINED.  A word graph over V classes with a space class sp (not the blank) has two parts.
+ * The TRIE of the lexicon's spellings, N nodes, root 0: child [N][V] int32 (the node after class c; any value where the
+ * arc is -inf), carc [N][V] float (finite, or -inf = FORBIDDEN; the columns sp and blank are never read), word [N]
+ * int32 (the id of the word that ends at the node, -1: none; word[0] = -1) and pen [N] float (finite).
+ * The WORD LM of H states over W words in back-off form: off [H + 1] int32 delimits the states' rows; wid [E] int32,
+ * strictly ascending inside a row; wlp [E] float (finite); wnext [E] int32 (the state after the word); bow [H] float
+ * (finite); bnext [H] int32 (the back-off state, -1 for state 0); eos [H] float (finite): log P(</s> | h), fully
+ * resolved.  State 0 is the empty history and its row is DENSE: off[1] - off[0] == W and wid[e] == e there; it is
+ * indexed directly, so a look-up always ends in it.
+ *   lookup(h, w): acc = 0 in double; search w in h's row: found at e -> (acc + wlp[e], wnext[e]); else acc += bow[h],
+ *   h = bnext[h], again.  At most SSASR_WORD_MAX_ORDER rounds; after them, or at bnext < 0, the result is -inf (a
+ *   malformed table: word_graph.WordGraph never builds one).
+ * A text's state is (n, h), the empty text's (0, 0).  For c != sp the arc is carc[n][c] and the state (child[n][c], h).
+ * For c == sp with word[n] < 0 the arc is -inf (the root too: no leading or doubled space); otherwise, with
+ * (lp, h') = lookup(h, word[n]), the arc is (float)((double)pen[n] + lp) and the state (0, h').
+ *   G(text) = the sum of the arcs in double.  fin(n, h) = pen[n] + eos[h] where word[n] < 0 (the root after a trailing
+ *   space, the empty text, or mid-word, where pen carries the builder's finite `unfinished` penalty);
+ *   fin(n, h) = (that space arc) + eos[h'] where word[n] >= 0.
+ * The search, the keys, the ties, the end ranking and the outputs are ssasr_ctc_decode_graph's word for word with this
+ * G and fin: key = logaddexp(g_b', g_n') + graph_weight G + length_bonus |w|, total = key + graph_weight fin, both
+ * state components taken when the extended text enters a beam; scores / ctc_scores / graph_scores (G + fin) [B][K].
+ * A term whose weight is exactly 0 is left out; at graph_weight == 0 the tables are unread (graph may be NULL), and
+ * at graph_weight == 0 && length_bonus == 0 the outputs are ssasr_ctc_decode's, bit for bit.
+ * Accepted: ssasr_ctc_decode_graph's arguments, with graph a HOST pointer to a struct of DEVICE tables: no NULL table,
+ * graph->V == V, 0 <= sp < V and sp != blank, N, H and W in 1 .. 1,048,576, E >= W; finite graph_weight >= 0 and finite
+ * length_bonus.  Argument errors return before any HIP call.  The tables' CONTENTS cannot be checked here: the kernel
+ * clamps every node, state, word id and row bound it reads into range, so a malformed table gives wrong scores and
+ * never a read outside the tables (word_graph.WordGraph validates them before the upload).
+ * One launch of 256 threads per utterance, no exchange between workgroups, no spins, no atomics, no barrier beyond
+ * ssasr_ctc_decode_graph's; every loop is bounded by SSASR_WORD_MAX_ORDER, 32 search rounds, K, V or T.  LDS holds
+ * ssasr_ctc_decode_graph's 40 KB with the pair (n, h) per member and h' per row: the tables are read only for the
+ * members that newly enter a beam, one wave each -- two dense rows and, where a word ends at the node, one look-up by
+ * the whole wave (64 cuts of the row per round) -- and once per member after the last frame for fin.
+ * The workspace holds the two beams' texts [B][2][K][T] int32. */
+#define SSASR_WORD_MAX_ORDER 8
+typedef struct ssasr_word_graph {
+  const int32_t* child;
+  const float* carc;
+  const int32_t* word;
+  const float* pen;
+  const int32_t* off;
+  const int32_t* wid;
+  const float* wlp;
+  const int32_t* wnext;
+  const float* bow;
+  const int32_t* bnext;
+  const float* eos;
+  int32_t N, V, H, W, E, sp;
+} ssasr_word_graph;
+int64_t ssasr_ctc_decode_word_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K);
+int ssasr_ctc_decode_word(const float* logits, const int32_t* frame_lens, int64_t B, int64_t T, int64_t V, int64_t K,
+                          int blank, void* ws, int64_t ws_bytes, int32_t* chars, int32_t* n_chars, float* scores,
+                          int32_t* n_hyps, const ssasr_word_graph* graph, float graph_weight, float length_bonus,
+                          float* ctc_scores, float* graph_scores, void* stream);
+
 /* The greedy decode loop of ASR.decode (src/asr.py:112-173, driven by ASRTester.exec, src/trainer.py:578-592)
  * for N encoded utterances as ONE launch: per utterance and step the attention (src/asr.py:383-390), both
  * Speller cells, char_trans and log_softmax (:149-153), one CharLM step fed with the previously emitted

@@ -54,6 +54,14 @@ class CharGraph(C.Structure):
     _fields_ = [('next', P), ('arc', P), ('fin', P), ('S', C.c_int32), ('V', C.c_int32), ('start', C.c_int32)]
 
 
+WORD_GRAPH_TABLES = ('child', 'carc', 'word', 'pen', 'off', 'wid', 'wlp', 'wnext', 'bow', 'bnext', 'eos')
+
+
+class WordGraph(C.Structure):
+    """struct ssasr_word_graph (include/ssasr.h)."""
+    _fields_ = [(n, P) for n in WORD_GRAPH_TABLES] + [(n, C.c_int32) for n in ('N', 'V', 'H', 'W', 'E', 'sp')]
+
+
 # what struct ssasr_infer and struct ssasr_beam share, around the beam's K and between each one's own tail
 _DECODE_DIMS = ('N', 'T', 'E', 'A', 'D', 'V', 'max_steps')
 _DECODE_COMMON = ([(n, P) for n in ('feat', 'enc_len', 'comp', 'w_psi', 'b_psi', 'w_phi',
@@ -167,6 +175,9 @@ SIGNATURES = {
     'ssasr_ctc_decode_graph_ws_bytes': (I64, [I64, I64, I64, I64]),
     'ssasr_ctc_decode_graph': (I32, [P, P, I64, I64, I64, I64, I32, P, I64, P, P, P, P, C.POINTER(CharGraph), F32, F32,
                                      P, P, P]),
+    'ssasr_ctc_decode_word_ws_bytes': (I64, [I64, I64, I64, I64]),
+    'ssasr_ctc_decode_word': (I32, [P, P, I64, I64, I64, I64, I32, P, I64, P, P, P, P, C.POINTER(WordGraph), F32, F32,
+                                    P, P, P]),
     'ssasr_edit_score': (I32, [P, I64, P, P, I64, P, P, I64, I64, I64, I32, I32, P, P]),
     'ssasr_mbr_select': (I32, [P, I64, P, P, P, I64, I64, I64, I32, I32, I32, I32, F32, P, P, P, P]),
     'ssasr_mwer_ws_bytes': (I64, [I64, I64, I64]),

@@ -868,7 +868,7 @@ class ASR(nn.Module):
         return self._texts(*hyps, mapper)
 
     def decode_ctc(self, xs, x_lens, mapper, *, beam_size=8, rnn_lm=None, lm_weight=0.0, length_bonus=0.0, graph=None,
-                   graph_weight=0.0):
+                   graph_weight=0.0, word_graph=None):
         """BUILD-DEFINED: transcripts from the ctc_head's posteriors alone, for a list of single utterances in ONE
         launch with no Speller step (ssasr_ctc_decode, include/ssasr.h): per utterance the list of (text, score), best
         first.  beam_size 0: the best path (per frame the most probable class, repeats merged, blanks removed; score =
@@ -886,7 +886,11 @@ class ASR(nn.Module):
         CTC score + graph_weight * G(text) + length_bonus * len(text) at every frame, and by that + graph_weight *
         fin[state(text)] at the end; last_ctc_decode gains the CTC part and the graph part (G + fin) after the logits.
         At graph_weight 0 the graph plays no part.  Together with rnn_lm at a non-zero lm_weight it is a ValueError:
-        the two terms in one search are not built."""
+        the two terms in one search are not built.
+        word_graph: a word_graph.WordGraph in place of `graph` (ssasr_ctc_decode_word, include/ssasr.h): the texts are
+        restricted to the words of its lexicon and ranked with its word n-gram LM at graph_weight, G and fin being the
+        word graph's; last_ctc_decode gains the same two tensors.  Together with `graph`, or with rnn_lm at a non-zero
+        lm_weight, it is a ValueError."""
         head = getattr(self, 'ctc_head', None)
         if head is None:
             raise ValueError(self._NO_CTC_HEAD % type(self).__name__)
@@ -895,15 +899,20 @@ class ASR(nn.Module):
         if len(xs) != len(x_lens) or not len(xs):
             raise ValueError('decode_ctc: %d utterances, %d lengths' % (len(xs), len(x_lens)))
         fused = self._ctc_lm_terms(rnn_lm, lm_weight, length_bonus, beam_size)
-        graph_weight = self._ctc_graph_weight(graph, graph_weight, fused, beam_size)
+        if word_graph is not None and graph is not None:
+            raise ValueError('decode_ctc: graph and word_graph in one search are not built; give one of them')
+        graph_weight = self._ctc_graph_weight(graph, graph_weight, fused, beam_size, word_graph)
+        if word_graph is not None:
+            graph = word_graph
         if graph_weight != 0.0 and graph.n_classes != head.weight.shape[0]:
             raise ValueError('decode_ctc: the graph has %d classes, the ctc_head %d'
                              % (graph.n_classes, head.weight.shape[0]))
         with torch.no_grad():
             packed, enc_lens = self._encode_packed(xs, x_lens)
             if graph_weight != 0.0:
-                out = ops.ctc_head_decode_graph(packed, head.weight, head.bias, enc_lens, beam_size, graph, graph_weight,
-                                                float(length_bonus), ops.CTC_BLANK)
+                decode = ops.ctc_head_decode_graph if word_graph is None else ops.ctc_head_decode_word
+                out = decode(packed, head.weight, head.bias, enc_lens, beam_size, graph, graph_weight,
+                             float(length_bonus), ops.CTC_BLANK)
                 self.last_ctc_decode = tuple(out[k] for k in ('chars', 'n_chars', 'scores', 'n_hyps', 'logits',
                                                               'ctc_scores', 'graph_scores'))
             elif fused is None:
@@ -936,18 +945,21 @@ class ASR(nn.Module):
         return tuple(terms)
 
     @staticmethod
-    def _ctc_graph_weight(graph, graph_weight, fused, beam_size):
-        """decode_ctc's graph keywords checked against the rest (fused: _ctc_lm_terms' result): the weight as a
-        float, 0.0 when no graph term runs."""
+    def _ctc_graph_weight(graph, graph_weight, fused, beam_size, word_graph=None):
+        """decode_ctc's graph keywords checked against the rest (fused: _ctc_lm_terms' result; word_graph: given in
+        place of graph): the weight as a float, 0.0 when no graph term runs."""
         from .char_graph import CharGraph
+        from .word_graph import WordGraph
         if isinstance(graph_weight, bool) or not isinstance(graph_weight, (int, float)) or \
                 not (math.isfinite(graph_weight) and graph_weight >= 0.0):
             raise ValueError('decode_ctc: graph_weight must be a finite number >= 0, got %r' % (graph_weight,))
         if graph is not None and not isinstance(graph, CharGraph):
             raise ValueError('decode_ctc: graph must be a char_graph.CharGraph, got %s' % type(graph).__name__)
+        if word_graph is not None and not isinstance(word_graph, WordGraph):
+            raise ValueError('decode_ctc: word_graph must be a word_graph.WordGraph, got %s' % type(word_graph).__name__)
         if graph_weight == 0.0:
             return 0.0
-        if graph is None:
+        if graph is None and word_graph is None:
             raise ValueError('decode_ctc: graph_weight %g needs graph' % graph_weight)
         if beam_size < 1:
             raise ValueError('decode_ctc: beam_size 0, the best path, has no graph term; use beam_size >= 1')

@@ -614,6 +614,170 @@ __global__ __launch_bounds__(DEC_NT) void ctc_prefix_beam_graph_kernel(GraphArgs
 
 constexpr int GRAPH_MAX_STATES = 1 << 20;
 
+// ---- the prefix beam search over a lexicon with a word n-gram LM (include/ssasr.h, ssasr_ctc_decode_word) ----------
+// ctc_prefix.h's frame body with WordTerm.  A member's state is the pair (trie node, word-LM state), two int32 in LDS;
+// its two rows sit in LDS [slot][64] exactly as GraphTerm's do, filled in after_commit by one wave per new member from
+// child[node][.] / carc[node][.].  The one entry that is no dense read is the space class's: where a word ends at the
+// node the wave looks word[node] up in the LM state's row, backing off until it is found (state 0's row is dense, so
+// that ends), and stores the arc (float)(pen[node] + lp) in the row and the LM state behind it beside the row (hsp),
+// so the candidate loop and the winners' update read LDS alone.  The look-up in a row is a 64-way search: every lane
+// probes one cut of the row, the ballot picks the segment, and a row of 200k words is down to <= 64 entries after two
+// rounds; the last round compares them all at once.  The end term does the same look-up once per member, one thread
+// each with a binary search, since no barrier lies between the last frame's hook and the ranking.  Every node, state
+// and row bound read from a table is clamped into range: a malformed table gives wrong scores, no stray read.
+constexpr int WORD_MAX_NODES = 1 << 20;
+constexpr int WORD_SEARCH_ROUNDS = 32;
+
+struct WordArgs {
+  DecodeArgs d;
+  const int32_t* child;      // [N][V]
+  const float* carc;         // [N][V]
+  const int32_t* word;       // [N]
+  const float* pen;          // [N]
+  const int32_t* off;        // [H + 1]
+  const int32_t* wid;        // [E]
+  const float* wlp;          // [E]
+  const int32_t* wnext;      // [E]
+  const float* bow;          // [H]
+  const int32_t* bnext;      // [H]
+  const float* eos;          // [H]
+  int N, H, W, E, sp;
+  float graph_weight, length_bonus;
+  float *ctc_scores, *graph_scores;   // [B][K]
+};
+
+struct WordHit {
+  double lp;                 // the backed-off log-probability, -inf: a malformed table
+  int next;                  // the LM state after the word
+};
+
+struct WordTerm : ctc_prefix::Scored {
+  struct Mem : ctc_prefix::ScoredMem {
+    int node[2][ctc_prefix::kMaxK];                          // the trie node after the text
+    int hst[2][ctc_prefix::kMaxK];                           // the word LM's state after the text's last space
+    float arow[ctc_prefix::kMaxK][64];                       // [slot]: carc[node][.], the space entry looked up
+    int nrow[ctc_prefix::kMaxK][64];                         // [slot]: child[node][.], the space entry the root
+    int hsp[ctc_prefix::kMaxK];                              // [slot]: the LM state behind the space arc
+  };
+  const WordArgs& g;
+
+  __device__ explicit WordTerm(const WordArgs& wa)
+      : Scored{wa.graph_weight != 0.f, wa.length_bonus != 0.f, (double)wa.graph_weight, (double)wa.length_bonus,
+               wa.ctc_scores, wa.graph_scores},
+        g(wa) {}
+
+  // the entry of word w in [lo, hi), -1: none.  The whole wave calls it with the same arguments.
+  __device__ int find_wave(int lo, int hi, int w) const {
+    const int lane = threadIdx.x & 63;
+    for (int r = 0; r < WORD_SEARCH_ROUNDS && hi - lo > 64; ++r) {
+      const int step = (hi - lo + 63) >> 6;                  // 64 cuts; the segment after the last one <= w has w
+      const int64_t i = lo + (int64_t)lane * step;
+      const int cnt = __popcll(__ballot(i < hi && g.wid[i < hi ? i : lo] <= w));
+      if (cnt == 0) return -1;
+      lo += (cnt - 1) * step;                                // cnt lanes had i < hi: lo stays below hi
+      hi = min(lo + step, hi);
+    }
+    const int i = lo + lane;
+    const unsigned long long hit = __ballot(i < hi && g.wid[i < hi ? i : lo] == w);
+    return hit ? lo + __ffsll((long long)hit) - 1 : -1;
+  }
+  // the same by one thread
+  __device__ int find_thread(int lo, int hi, int w) const {
+    for (int r = 0; r < WORD_SEARCH_ROUNDS && lo < hi; ++r) {
+      const int mid = lo + ((hi - lo) >> 1);
+      const int v = g.wid[mid];
+      if (v == w) return mid;
+      if (v < w) lo = mid + 1; else hi = mid;
+    }
+    return -1;
+  }
+  // lookup(h, w) of the header: WAVE: by the whole wave, else by the calling thread; the same sums in the same order
+  template <bool WAVE>
+  __device__ WordHit lookup(int h, int w) const {
+    double acc = 0.0;
+    w = min(w, g.W - 1);
+    for (int r = 0; r < SSASR_WORD_MAX_ORDER; ++r) {
+      const int lo = min(max(g.off[h], 0), g.E), hi = min(max(g.off[h + 1], lo), g.E);
+      int e;
+      if (h == 0) e = min(lo + w, g.E - 1);                  // the dense row
+      else if (lo >= hi) e = -1;
+      else e = WAVE ? find_wave(lo, hi, w) : find_thread(lo, hi, w);
+      if (e >= 0) return WordHit{acc + (double)g.wlp[e], min(max(g.wnext[e], 0), g.H - 1)};
+      acc += (double)g.bow[h];
+      const int b = g.bnext[h];
+      if (b < 0) break;
+      h = min(b, g.H - 1);
+    }
+    return WordHit{ctc_prefix::kNegInf, 0};
+  }
+  // the space arc out of (node, h), a word ending at the node
+  template <bool WAVE>
+  __device__ float space_arc(int node, int h, int w, int& h_next) const {
+    const WordHit hit = lookup<WAVE>(h, w);
+    h_next = hit.next;
+    return (float)((double)g.pen[node] + hit.lp);
+  }
+
+  __device__ void load_rows(Mem& m, int slot, int node, int h, int V) const {   // one wave
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)node * V;
+    const bool dense = lane < V && lane != g.sp && lane != g.d.blank;
+    float a = dense ? g.carc[row + lane] : 0.f;
+    const int nx = dense ? g.child[row + lane] : 0;
+    const int w = g.word[node];
+    int h_next = 0;
+    if (w >= 0) {                                            // the same for the whole wave
+      const float sa = space_arc<true>(node, h, w, h_next);
+      if (lane == g.sp) a = sa;
+    } else if (lane == g.sp) {
+      a = -INFINITY;
+    }
+    m.arow[slot][lane] = a;
+    m.nrow[slot][lane] = nx;
+    if (lane == 0) m.hsp[slot] = h_next;
+  }
+  __device__ void init(Mem& m, int V) const {                // the empty text: the root, the empty history
+    if (threadIdx.x == 0) { m.node[0][0] = 0; m.hst[0][0] = 0; }
+    if (on && threadIdx.x < 64) load_rows(m, 0, 0, 0, V);
+  }
+  __device__ double step(const Mem& m, int cur, int u, int c) const { return (double)m.arow[m.slot[cur][u]][c]; }
+  __device__ void keep(Mem& m, int cur, int nxt, int j, int w) const {
+    m.node[nxt][j] = m.node[cur][w];
+    m.hst[nxt][j] = m.hst[cur][w];
+  }
+  __device__ void inherit(Mem& m, int cur, int nxt, int j, int u, int c) const {
+    const int sl = m.slot[cur][u];
+    m.node[nxt][j] = on ? min(max(m.nrow[sl][c], 0), g.N - 1) : 0;
+    m.hst[nxt][j] = on ? (c == g.sp ? m.hsp[sl] : m.hst[cur][u]) : 0;
+  }
+  // the new members' rows: a wave per member; two barriers of the next frame lie before their first reader
+  template <class S>
+  __device__ void after_commit(S& s, int, int nxt, int, int V) const {
+    Mem& m = s.tm;
+    const int ne = on ? m.n_ext : 0;
+    for (int e = threadIdx.x >> 6; e < ne; e += DEC_WAVES) {
+      const int j = m.ext[e];
+      load_rows(m, m.slot[nxt][j], m.node[nxt][j], m.hst[nxt][j], V);
+    }
+  }
+  __device__ bool has_end() const { return true; }
+  // fin(node, h): the rows of the last frame's new members may still be in flight, so the member looks up again
+  __device__ double end(const Mem& m, int cur, int j) const {
+    const int node = m.node[cur][j], h = m.hst[cur][j];
+    const int w = g.word[node];
+    if (w < 0) return (double)g.pen[node] + (double)g.eos[h];
+    int h_next;
+    const float sa = space_arc<false>(node, h, w, h_next);
+    return (double)sa + (double)g.eos[h_next];
+  }
+};
+
+__global__ __launch_bounds__(DEC_NT) void ctc_prefix_beam_word_kernel(WordArgs g) {
+  __shared__ ctc_prefix::State<DEC_NT, WordTerm> s;
+  WordTerm term(g);
+  ctc_prefix::search(g.d, term, s);
+}
+
 }  // namespace
 
 extern "C" int64_t ssasr_ctc_decode_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K) {
@@ -664,6 +828,48 @@ extern "C" int ssasr_ctc_decode_graph(const float* logits, const int32_t* frame_
   }
   hipLaunchKernelGGL(ctc_prefix_beam_graph_kernel, dim3((unsigned)B), dim3(DEC_NT), 0,
                      (hipStream_t)stream, g);
+  SSASR_LAUNCH_CHECK();
+  return SSASR_OK;
+}
+
+extern "C" int64_t ssasr_ctc_decode_word_ws_bytes(int64_t B, int64_t T, int64_t V, int64_t K) {
+  if (!ctc_prefix::shape_ok(B, T, V, K)) return 0;
+  return B * 2 * K * T * 4;
+}
+
+extern "C" int ssasr_ctc_decode_word(const float* logits, const int32_t* frame_lens, int64_t B, int64_t T, int64_t V,
+                                     int64_t K, int blank, void* ws, int64_t ws_bytes, int32_t* chars,
+                                     int32_t* n_chars, float* scores, int32_t* n_hyps, const ssasr_word_graph* graph,
+                                     float graph_weight, float length_bonus, float* ctc_scores, float* graph_scores,
+                                     void* stream) {
+  if (!logits || !frame_lens || !ws || !chars || !n_chars || !scores || !n_hyps || !ctc_scores || !graph_scores)
+    return SSASR_EARG;
+  if (!std::isfinite(graph_weight) || graph_weight < 0.f || !std::isfinite(length_bonus)) return SSASR_EARG;
+  if (!ctc_prefix::shape_ok(B, T, V, K) || blank < 0 || blank >= V) return SSASR_EARG;
+  if (graph_weight != 0.f && !graph) return SSASR_EARG;
+  if (graph) {
+    const ssasr_word_graph& w = *graph;
+    if (!w.child || !w.carc || !w.word || !w.pen || !w.off || !w.wid || !w.wlp || !w.wnext || !w.bow || !w.bnext ||
+        !w.eos)
+      return SSASR_EARG;
+    if (w.V != V || w.sp < 0 || w.sp >= V || w.sp == blank) return SSASR_EARG;
+    if (w.N < 1 || w.N > WORD_MAX_NODES || w.H < 1 || w.H > WORD_MAX_NODES || w.W < 1 || w.W > WORD_MAX_NODES ||
+        w.E < w.W)
+      return SSASR_EARG;
+  }
+  if ((reinterpret_cast<uintptr_t>(ws) & 7) || ws_bytes < ssasr_ctc_decode_word_ws_bytes(B, T, V, K)) return SSASR_EARG;
+  WordArgs g{};
+  g.d = ctc_prefix::make_args(logits, frame_lens, T, V, K, blank, ws, chars, n_chars, scores, n_hyps);
+  g.graph_weight = graph_weight; g.length_bonus = length_bonus;
+  g.ctc_scores = ctc_scores; g.graph_scores = graph_scores;
+  g.N = g.H = g.W = g.E = 1;
+  if (graph && graph_weight != 0.f) {                        // weight 0: the tables are unread
+    g.child = graph->child; g.carc = graph->carc; g.word = graph->word; g.pen = graph->pen;
+    g.off = graph->off; g.wid = graph->wid; g.wlp = graph->wlp; g.wnext = graph->wnext;
+    g.bow = graph->bow; g.bnext = graph->bnext; g.eos = graph->eos;
+    g.N = graph->N; g.H = graph->H; g.W = graph->W; g.E = graph->E; g.sp = graph->sp;
+  }
+  hipLaunchKernelGGL(ctc_prefix_beam_word_kernel, dim3((unsigned)B), dim3(DEC_NT), 0, (hipStream_t)stream, g);
   SSASR_LAUNCH_CHECK();
   return SSASR_OK;
 }

@@ -1249,32 +1249,59 @@ def ctc_decode_graph(logits, frame_lens, beam_size, graph, graph_weight=0.0, len
     n_chars [B, K] int32, scores / ctc_scores / graph_scores [B, K] float32 (the fused total, the CTC part, G + fin),
     n_hyps [B] int32, best first.  At zero weights the first four are ctc_decode's bits.  No autograd."""
     from .char_graph import CharGraph
+    return _prefix_search_graph('ctc_decode_graph', CharGraph, 'char_graph.CharGraph', logits, frame_lens, beam_size,
+                                graph, graph_weight, length_bonus, blank)
+
+
+def _prefix_search_graph(name, cls, cls_name, logits, frame_lens, beam_size, graph, graph_weight, length_bonus, blank):
+    """ctc_decode_graph and ctc_decode_word (`name`: also the C entry's, behind 'ssasr_'): the checks of the weights and
+    of the graph (an instance of `cls`, None allowed at weight 0), the upload, the workspace and the launch."""
     lib = _lib.load()
     blank, graph_weight, length_bonus = int(blank), float(graph_weight), float(length_bonus)
     if not (math.isfinite(graph_weight) and graph_weight >= 0.0 and math.isfinite(length_bonus)):
-        raise ValueError('ctc_decode_graph: graph_weight must be finite and >= 0 and length_bonus finite, got %r, %r'
-                         % (graph_weight, length_bonus))
+        raise ValueError('%s: graph_weight must be finite and >= 0 and length_bonus finite, got %r, %r'
+                         % (name, graph_weight, length_bonus))
     if graph is None and graph_weight != 0.0:
-        raise ValueError('ctc_decode_graph: graph_weight %g needs a graph' % graph_weight)
-    if graph is not None and not isinstance(graph, CharGraph):
-        raise TypeError('ctc_decode_graph: graph must be a char_graph.CharGraph, got %s' % type(graph).__name__)
+        raise ValueError('%s: graph_weight %g needs a graph' % (name, graph_weight))
+    if graph is not None and not isinstance(graph, cls):
+        raise TypeError('%s: graph must be a %s, got %s' % (name, cls_name, type(graph).__name__))
 
     def classes(V):
         if graph is not None and graph.n_classes != V:
-            raise ValueError('ctc_decode_graph: the graph has %d classes, the logits %d' % (graph.n_classes, V))
-    logits, (B, T, V), out = _prefix_search_entry('ctc_decode_graph', logits, frame_lens, beam_size, blank,
+            raise ValueError('%s: the graph has %d classes, the logits %d' % (name, graph.n_classes, V))
+        if graph is not None and getattr(graph, 'space', None) == blank:
+            raise ValueError('%s: the graph\'s space class %d is the blank' % (name, blank))
+    logits, (B, T, V), out = _prefix_search_entry(name, logits, frame_lens, beam_size, blank,
                                                   ('scores', 'ctc_scores', 'graph_scores'), term='graph',
                                                   classes=classes)
     s, keep = graph.to(logits.device) if graph is not None else (None, None)
-    need = int(lib.ssasr_ctc_decode_graph_ws_bytes(B, T, V, beam_size))
+    need = int(getattr(lib, 'ssasr_%s_ws_bytes' % name)(B, T, V, beam_size))
     if need <= 0:
-        raise ValueError('ctc_decode_graph: shape B=%d T=%d V=%d beam_size=%d has no kernel' % (B, T, V, beam_size))
+        raise ValueError('%s: shape B=%d T=%d V=%d beam_size=%d has no kernel' % (name, B, T, V, beam_size))
     ws = torch.empty((need + 7) // 8, device=logits.device, dtype=torch.int64)
-    check(lib.ssasr_ctc_decode_graph(_p(logits), _p(frame_lens.contiguous()), B, T, V, beam_size, blank, _p(ws),
-                                     ws.numel() * 8, _p(out['chars']), _p(out['n_chars']), _p(out['scores']),
-                                     _p(out['n_hyps']), C.byref(s) if s is not None else None, graph_weight,
-                                     length_bonus, _p(out['ctc_scores']), _p(out['graph_scores']), _stream()),
-          'ssasr_ctc_decode_graph')
+    check(getattr(lib, 'ssasr_' + name)(_p(logits), _p(frame_lens.contiguous()), B, T, V, beam_size, blank, _p(ws),
+                                        ws.numel() * 8, _p(out['chars']), _p(out['n_chars']), _p(out['scores']),
+                                        _p(out['n_hyps']), C.byref(s) if s is not None else None, graph_weight,
+                                        length_bonus, _p(out['ctc_scores']), _p(out['graph_scores']), _stream()),
+          'ssasr_' + name)
+    return out
+
+
+def ctc_decode_word(logits, frame_lens, beam_size, graph, graph_weight=0.0, length_bonus=0.0, blank=0):
+    """ssasr_ctc_decode_word: ctc_decode's prefix beam search over a lexicon with a word n-gram LM
+    (word_graph.WordGraph) in the ranking, in one launch (include/ssasr.h).  The arguments and the dict returned are
+    ctc_decode_graph's, graph_scores holding G + fin of the word graph.  No autograd."""
+    from .word_graph import WordGraph
+    return _prefix_search_graph('ctc_decode_word', WordGraph, 'word_graph.WordGraph', logits, frame_lens, beam_size,
+                                graph, graph_weight, length_bonus, blank)
+
+
+def ctc_head_decode_word(feat, weight, bias, frame_lens, beam_size, graph, graph_weight=0.0, length_bonus=0.0, blank=0):
+    """ctc_decode_word on the head's logits, the product issued as ctc_head_decode issues it.  -> ctc_decode_word's
+    dict with the logits [B, T, V] they were decoded from under 'logits'.  No autograd."""
+    logits = _ctc_head_logits(feat.detach(), weight.detach(), bias.detach())[0]
+    out = ctc_decode_word(logits, frame_lens, beam_size, graph, graph_weight, length_bonus, blank)
+    out['logits'] = logits
     return out
 
 

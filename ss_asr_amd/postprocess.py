@@ -502,6 +502,16 @@ def ctc_prefix_beam_graph_reference(lp, K, graph, graph_weight=0.0, length_bonus
             walked[w] = (g + arc[s][w[-1]], nxt[s][w[-1]])
         return walked[w]
 
+    return _prefix_beam_ranked(rows, K, blank, V, lae, zero, neg, gw, beta, walk if use_g else None,
+                               lambda s: fin[s], trace, parts)
+
+
+def _prefix_beam_ranked(rows, K, blank, V, lae, zero, neg, gw, beta, walk, fin_of, trace, parts):
+    """The search of ctc_prefix_beam_graph_reference and ctc_prefix_beam_word_reference over the frames `rows`:
+    walk(w) -> (G(w), state(w)) (None: no graph term) and fin_of(state) are the graph's; lae, zero and neg carry the
+    dtype.  -> ([(text, total)] best first, gap); parts as those two take it."""
+    use_g = walk is not None
+
     def key_of(w, total):
         if not total > neg:
             return neg
@@ -542,7 +552,7 @@ def ctc_prefix_beam_graph_reference(lp, K, graph, graph_weight=0.0, length_bonus
             total, part = key_of(w, ctc), zero
             if use_g:
                 part, s = walk(w)
-                part, total = part + fin[s], total + gw * fin[s]
+                part, total = part + fin_of(s), total + gw * fin_of(s)
             out.append((w, float(total), float(ctc), float(part)))
     out.sort(key=lambda e: (-e[1], e[0]))
     for a, b in zip(out, out[1:]):
@@ -550,6 +560,57 @@ def ctc_prefix_beam_graph_reference(lp, K, graph, graph_weight=0.0, length_bonus
     if parts is not None:
         parts.extend((e[2], e[3]) for e in out)
     return [(e[0], e[1]) for e in out], gap
+
+
+def ctc_prefix_beam_word_reference(lp, K, graph, graph_weight=0.0, length_bonus=0.0, blank=0, dtype=np.float64,
+                                   trace=None, parts=None):
+    """BUILD-DEFINED: CTC prefix beam search over a lexicon with a word n-gram LM in the ranking, ssasr_ctc_decode_word
+    (include/ssasr.h) restated over Python tuples as texts -- what the kernel is defined and tested against.  Every
+    argument, the search, the keys, the ties, the end ranking, gap and parts are ctc_prefix_beam_graph_reference's;
+    graph: a word_graph.WordGraph (None at graph_weight 0), whose float32 tables are evaluated in `dtype`:
+      a text's state is (n, h), the empty text's (0, 0); class c != space: arc carc[n][c], state (child[n][c], h);
+      the space where word[n] < 0: -inf; else, with (lp, h') = lookup(h, word[n]) summed in float64, the arc is
+      float32(pen[n] + lp) and the state (0, h');
+      G(w) = the sum of the arcs; fin(n, h) = pen[n] + eos[h] where word[n] < 0, else (the space arc) + eos[h']."""
+    lp = np.asarray(lp, dtype=dtype)
+    K, blank = int(K), int(blank)
+    if lp.ndim != 2:
+        raise ValueError('ctc_prefix_beam_word_reference: lp must be [T, V], got %r' % (lp.shape,))
+    if K < 1:
+        raise ValueError('ctc_prefix_beam_word_reference: K must be >= 1, got %d' % K)
+    V = lp.shape[1]
+    gw, beta = float(np.float32(graph_weight)), float(np.float32(length_bonus))
+    if not (math.isfinite(gw) and math.isfinite(beta)) or gw < 0:
+        raise ValueError('ctc_prefix_beam_word_reference: graph_weight must be finite and >= 0, length_bonus finite')
+    if np.dtype(dtype) == np.float64:                           # Python floats ARE float64, and ten times faster
+        rows, zero, neg, cast = lp.tolist(), 0.0, -math.inf, float
+
+        def lae(a, b):
+            if a < b:
+                a, b = b, a
+            return a if b == -math.inf else a + math.log1p(math.exp(b - a))
+    else:
+        rows, zero, neg, lae, cast = [list(row) for row in lp], dtype(0), dtype(-np.inf), np.logaddexp, dtype
+        gw, beta = dtype(gw), dtype(beta)
+    walk = None
+    if gw != 0:
+        if graph is None:
+            raise ValueError('ctc_prefix_beam_word_reference: graph_weight %g needs a graph' % gw)
+        if graph.n_classes != V or graph.space == blank:
+            raise ValueError('ctc_prefix_beam_word_reference: the graph has %d classes and the space %d, lp %d classes '
+                             'and the blank %d' % (graph.n_classes, graph.space, V, blank))
+        walked = {(): (zero, (0, 0))}
+
+        def walk(w):
+            """(G(w), (n, h))"""
+            if w not in walked:
+                g, state = walk(w[:-1])
+                arc, state = graph.step(*state, w[-1])
+                walked[w] = (g + cast(arc), state)
+            return walked[w]
+
+    return _prefix_beam_ranked(rows, K, blank, V, lae, zero, neg, gw, beta, walk,
+                               lambda state: cast(graph.fin(*state)), trace, parts)
 
 
 def _segment_frame(dp, lp_t, lab, pen, neg, zero):

@@ -692,7 +692,11 @@ class ASRTester(Solver):
     beam_size >= 1): contextual biasing towards the phrases, a count-based n-gram LM, or with both their product;
     everything is validated in set_model, length_bonus goes with it, and `decode_file` gains `_hw<n>x<bonus>` /
     `_ng<weight>` (and `_clb<length_bonus>`) only when a key is present.  Together with asr.decode_rescore or a
-    non-zero lm_weight they are an error (not built).  It composes with
+    non-zero lm_weight they are an error (not built).  The optional keys word_lm (the path of a
+    word_graph.WordGraph.save file) with word_lm_weight (>= 0, absent: 0.5) restrict the texts to a lexicon and rank
+    them with a word n-gram LM INSIDE the prefix search (ssasr_ctc_decode_word; beam_size >= 1; length_bonus goes with
+    it); `decode_file` gains `_wlm<weight>` (and `_clb<length_bonus>`) only when the key is present; together with
+    hotwords / ngram_lm, a non-zero lm_weight or asr.decode_rescore they are an error (not built).  It composes with
     decode_score, decode_mbr (which then needs THIS beam_size >= 2) and decode_align; together with a positive
     asr.decode_ctc_weight or any of the beam search's terms it is an error.
     asr.decode_rescore: {ctc_weight: 0.3, length_bonus: 0.0} (absent: off; ctc_weight a number in [0, 1], length_bonus
@@ -764,9 +768,11 @@ class ASRTester(Solver):
             return None
         if conf is True:
             conf = {}
-        if not isinstance(conf, dict) or set(conf) - ({'beam_size', 'lm_weight', 'length_bonus'} | set(ASRTester.GRAPH_KEYS)):
+        if not isinstance(conf, dict) or \
+                set(conf) - ({'beam_size', 'lm_weight', 'length_bonus'} | set(ASRTester.GRAPH_KEYS) | set(ASRTester.WORD_KEYS)):
             raise ValueError('asr.decode_ctc_only must be a mapping with the key beam_size (and, optionally, lm_weight, '
-                             'length_bonus, hotwords, hotword_bonus, ngram_lm and ngram_weight), got {!r}'.format(conf))
+                             'length_bonus, hotwords, hotword_bonus, ngram_lm, ngram_weight, word_lm and '
+                             'word_lm_weight), got {!r}'.format(conf))
         beam = conf.get('beam_size', 8)
         if isinstance(beam, bool) or not isinstance(beam, int) or not 0 <= beam <= 32:
             raise ValueError('asr.decode_ctc_only.beam_size must be an integer in 0..32, got {!r}'.format(beam))
@@ -856,6 +862,51 @@ class ASRTester(Solver):
                              'not built; give one of them')
         return out
 
+    WORD_KEYS = ('word_lm', 'word_lm_weight')
+
+    @staticmethod
+    def ctc_only_word(asr_config):
+        """The word-graph keys of asr.decode_ctc_only, validated: None when neither is present, else {'word_lm': path,
+        'word_lm_weight': float}."""
+        import math
+        beam = ASRTester.ctc_only_beam(asr_config)
+        conf = asr_config.get('decode_ctc_only')
+        conf = conf if isinstance(conf, dict) else {}
+        if not set(conf) & set(ASRTester.WORD_KEYS):
+            return None
+        path, weight = conf.get('word_lm'), conf.get('word_lm_weight', 0.5)
+        if path is None:
+            raise ValueError('asr.decode_ctc_only.word_lm_weight needs asr.decode_ctc_only.word_lm, got {!r}'.format(conf))
+        if not isinstance(path, str) or not path:
+            raise ValueError('asr.decode_ctc_only.word_lm must be the path of a WordGraph.save file, got {!r}'.format(path))
+        if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not math.isfinite(weight) or weight < 0:
+            raise ValueError('asr.decode_ctc_only.word_lm_weight must be a finite number >= 0, got {!r}'.format(weight))
+        if beam == 0:
+            raise ValueError('asr.decode_ctc_only: beam_size 0, the best path, has no word LM; got {!r}'.format(conf))
+        clash = sorted(set(conf) & {'hotwords', 'ngram_lm'})
+        if clash:
+            raise ValueError('asr.decode_ctc_only: word_lm together with {} in one search is not built; give one of '
+                             'them'.format(' / '.join(clash)))
+        if asr_config.get('decode_rescore') not in (None, False):
+            raise ValueError('asr.decode_ctc_only: word_lm with asr.decode_rescore is not built (ASR.rescore has no '
+                             'graph term)')
+        if ASRTester.ctc_only_lm(asr_config)['lm_weight'] != 0:
+            raise ValueError('asr.decode_ctc_only: word_lm together with a CharLM lm_weight in one search is not built; '
+                             'give one of them')
+        return {'word_lm': path, 'word_lm_weight': float(weight)}
+
+    def load_word_graph(self, conf):
+        """(WordGraph, graph_weight) of ctc_only_word's keys, checked against the model's classes and space."""
+        from .word_graph import WordGraph
+        if not os.path.isfile(conf['word_lm']):
+            raise ValueError('asr.decode_ctc_only.word_lm: no file {!r}'.format(conf['word_lm']))
+        wg = WordGraph.load(conf['word_lm'])
+        V, space = self.mapper.get_dim(), self.mapper.char_to_ind(' ')
+        if wg.n_classes != V or wg.space != space or wg.blank != ops.CTC_BLANK:
+            raise ValueError('asr.decode_ctc_only.word_lm: the graph has {} classes, the space {} and the blank {}, the '
+                             'model {}, {} and {}'.format(wg.n_classes, wg.space, wg.blank, V, space, ops.CTC_BLANK))
+        return wg, conf['word_lm_weight']
+
     def build_ctc_graph(self, conf, name='asr.decode_ctc_only.{}'.format):
         """(CharGraph, graph_weight) of ctc_only_graph's (or, with its name(key), beam_graph's) keys: the hotwords'
         graph at weight 1, the n-gram graph at ngram_weight, or the product of the two, each factor pre-scaled, at
@@ -924,6 +975,8 @@ class ASRTester(Solver):
         self.decode_ctc_lm = self.ctc_only_lm(self.config['asr'])
         graph_conf = self.ctc_only_graph(self.config['asr'])
         self.decode_ctc_graph = None if graph_conf is None else self.build_ctc_graph(graph_conf)
+        word_conf = self.ctc_only_word(self.config['asr'])
+        self.decode_ctc_word = None if word_conf is None else self.load_word_graph(word_conf)
         beam_graph_conf = self.beam_graph(self.config['asr'])
         self.decode_beam_graph = None if beam_graph_conf is None else self.build_ctc_graph(
             beam_graph_conf, 'asr.decode_{}'.format)
@@ -972,6 +1025,10 @@ class ASRTester(Solver):
                     self.decode_file += '_hw{:}x{:}'.format(len(graph_conf['hotwords']), graph_conf['hotword_bonus'])
                 if graph_conf['ngram_lm'] is not None:
                     self.decode_file += '_ng{:}'.format(graph_conf['ngram_weight'])
+                if self.decode_ctc_lm['length_bonus'] != 0:
+                    self.decode_file += '_clb{:}'.format(self.decode_ctc_lm['length_bonus'])
+            if word_conf is not None:
+                self.decode_file += '_wlm{:}'.format(word_conf['word_lm_weight'])
                 if self.decode_ctc_lm['length_bonus'] != 0:
                     self.decode_file += '_clb{:}'.format(self.decode_ctc_lm['length_bonus'])
         if self.decode_rescore is not None:
@@ -1035,6 +1092,12 @@ class ASRTester(Solver):
                                                        length_bonus=self.decode_ctc_lm['length_bonus'],
                                                        graph=self.decode_ctc_graph[0],
                                                        graph_weight=self.decode_ctc_graph[1])]
+                elif ctc_only is not None and self.decode_ctc_word is not None:
+                    texts = [hyps[0][0] for hyps in
+                             self.asr_model.decode_ctc(xs, x_lens, self.mapper, beam_size=ctc_only,
+                                                       length_bonus=self.decode_ctc_lm['length_bonus'],
+                                                       word_graph=self.decode_ctc_word[0],
+                                                       graph_weight=self.decode_ctc_word[1])]
                 elif ctc_only is not None:
                     texts = [hyps[0][0] for hyps in
                              self.asr_model.decode_ctc(xs, x_lens, self.mapper, beam_size=ctc_only, rnn_lm=self.lm,
